@@ -7,8 +7,16 @@ wall-clock", on BASELINE.json's "Weather MLP (3-layer, 128-h)" (configs 0-2).  D
 layer, cross-entropy, Adam(lr=0.01), batch 4 PER RANK (weak scaling) - the reference training step
 (jobs/train_lightning_ddp.py:57-62,66-71,88,122) with BASELINE's 3-layer 128-h model -
 DistributedSampler sharding, per-step gradient all-reduce across ranks plus the sync_dist
-train_loss.  At one rank the reference-exact WeatherClassifier 5->64->2 is measured too, with the
-same steps / warmup, and reported under extra.reference_model_*.  Other configs:
+train_loss.
+
+A plain run does what the headline figure needs and no more: set up, W warmup steps, the K timed
+steps, the result line.  --full adds everything else the benchmark measures: the validation pass
+(extra.val_loss / val_acc), one real measured epoch of the weather models (extra.epoch_*), the
+reference-exact WeatherClassifier 5->64->2 with the same steps / warmup at one rank
+(extra.reference_model_*), and the peer-access report of a multi-rank run (extra.xgmi_peers).
+--dump-outputs DIR writes what the timed steps handed back (per-step losses, parameters and Adam
+moments after the last timed step) as DIR/<name>.npy; the inputs are seeded, so two builds run with
+the same arguments can be compared array for array.  Other configs:
   --model weather              the reference-exact WeatherClassifier 5-64-2 as the headline
   --model tabular-mlp-4x1024   100M x 256 synthetic rows (bf16, HBM-resident), 256-1024-1024-1024-2
                                MLP, MSE, Adam(1e-3), batch 4096 per rank, graph-captured MFMA step
@@ -23,6 +31,7 @@ Timed region: exactly K optimizer steps, bracketed by barrier + device synchroni
 sides, max over ranks.
 
     python bench.py --gpus 1 --steps 20000 --warmup 2000
+    python bench.py --gpus 1 --steps 20000 --warmup 2000 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29511 bench.py --gpus 8
 """
@@ -64,8 +73,14 @@ def parse():
     p.add_argument("--warmup", type=int, default=None, help="untimed steps (default 2000; tabular 20)")
     p.add_argument("--model", default="weather-mlp-3x128",
                    help="weather-mlp-3x128 (BASELINE) | weather (reference 5-64-2) | tabular-mlp-4x1024 | tabtransformer")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: validation, the measured epoch, the "
+                        "5-64-2 reference model, the multi-rank peer-access report")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write their outputs (losses, parameters, Adam moments) as "
+                        "DIR/<name>.npy (float32, at most 64 MB in all)")
     p.add_argument("--no-reference-model", action="store_true",
-                   help="skip the extra 5-64-2 measurement of a single-rank weather-mlp-3x128 run")
+                   help="--full: skip the extra 5-64-2 measurement of a single-rank weather-mlp-3x128 run")
     p.add_argument("--batch", type=int, default=None, help="per-rank batch (reference: 4; tabular: 4096)")
     p.add_argument("--rows", type=int, default=0,
                    help="synthetic dataset rows (0 = sized to the run; tabular: 100M per BASELINE config 4)")
@@ -79,8 +94,8 @@ def parse():
     p.add_argument("--reserve-pattern", default="spread", choices=("spread", "low", "high"),
                    help="which CU mask bits --reserve-cus takes: evenly spaced, the first N or the last N")
     p.add_argument("--no-epoch", action="store_true",
-                   help="skip the measured epoch (weather models on GPU: one real epoch of --epoch-rows rows, "
-                        "train + validation, timed after the step window)")
+                   help="--full: skip the measured epoch (weather models on GPU: one real epoch of --epoch-rows "
+                        "rows, train + validation, timed after the step window)")
     a = p.parse_args()
     tab = a.model in TABULAR
     tt = a.model in TRANSFORMER
@@ -196,6 +211,25 @@ def _warmup(loop, n_items, warmup, loss):
                 snap = None
                 # back to the full limit (launches rebound with it)
                 loop.xg_timeout_s, loop._bound, loop._fast_run = full_timeout, None, None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(dirname, tensors):
+    """--dump-outputs: each tensor flattened to float32 in DIR/<name>.npy.  The arrays share the
+    64 MB limit evenly; a longer one is cut to a fixed seeded sample of its elements (ascending
+    positions, the same positions in every run)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_LIMIT_BYTES // 4 // len(tensors)
+    for name, t in tensors.items():
+        x = t.detach().reshape(-1).to("cpu", torch.float32).numpy()
+        if x.size > cap:
+            x = x[np.sort(np.random.default_rng(0).choice(x.size, cap, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(x))
 
 
 def _params_in_sync(ctx, p):
@@ -459,7 +493,13 @@ def _measure(a, ctx, stack):
     first_l = float(losses[: max(1, a.warmup // 10)].mean())
     last_l = float(losses[-max(1, a.steps // 10):].mean())
     eng.global_step = total_steps
-    val_loss, val_acc = loop.validate(limit=(64 * a.batch) if (tab or tt) else None)
+    if a.dump_outputs and ctx.rank == 0:
+        # what a caller of run_steps() gets back: the timed steps' losses and the state they left
+        opt = eng.optimizer if (tt or cpu) else eng
+        _dump_outputs(a.dump_outputs, {"loss": losses[a.warmup:], "params": eng.flat_p if (tt or cpu) else eng.p,
+                                       "adam_m": opt.m, "adam_v": opt.v})
+    val_loss, val_acc = (loop.validate(limit=(64 * a.batch) if (tab or tt) else None) if a.full
+                         else (None, None))
 
     samples = a.steps * a.batch * ctx.world_size
     sps = samples / dt
@@ -505,8 +545,6 @@ def _measure(a, ctx, stack):
             "epoch_rows": a.epoch_rows,
             "loss_first": round(first_l, 4),
             "loss_last": round(last_l, 4),
-            "val_loss": round(val_loss, 4),
-            "val_acc": round(val_acc, 4),
             "losses_finite": finite,
             "params_in_sync": in_sync,
             "xgmi_exchange_ok": xg_ok,
@@ -514,7 +552,9 @@ def _measure(a, ctx, stack):
             "device": torch.cuda.get_device_name(ctx.device) if not cpu else "cpu",
         },
     }
-    if not (tab or tt or cpu) and not a.no_epoch and a.epoch_rows > 0:
+    if a.full:
+        out["extra"].update({"val_loss": round(val_loss, 4), "val_acc": round(val_acc, 4)})
+    if a.full and not (tab or tt or cpu) and not a.no_epoch and a.epoch_rows > 0:
         out["extra"].update(_measure_epoch(a, ctx, eng))
     if tab:
         flops = 6.0 * sum(eng.dims[i] * eng.dims[i + 1] for i in range(len(eng.dims) - 1)) * a.batch
@@ -596,18 +636,20 @@ def main():
     ctx = init_distributed("cpu" if cpu else "gpu")
     seed_everything(42)
     out, ok, eng = measure(a, ctx)
-    if not cpu and ctx.world_size > 1:
+    if a.full and not cpu and ctx.world_size > 1:
         from dct_amd.parallel.xgmi import peer_report
 
         bus, mat, peers_ok = peer_report(ctx)
         out["extra"]["xgmi_peers"] = {"rank_devices": bus, "can_access_peer": mat, "all_rank_pairs_ok": peers_ok}
-    if (a.model == "weather-mlp-3x128" and not cpu and ctx.world_size == 1 and not a.no_reference_model):
+    if (a.full and a.model == "weather-mlp-3x128" and not cpu and ctx.world_size == 1
+            and not a.no_reference_model):
         # the reference-exact model (jobs/train_lightning_ddp.py:57-62) with the same K / W
         del eng
         seed_everything(42)
         a_ref = copy.copy(a)
         a_ref.model = "weather"
         a_ref.no_epoch = True
+        a_ref.dump_outputs = None  # the dump is the headline model's
         ref, ok_ref, _ = measure(a_ref, ctx)
         out["extra"].update({
             "reference_model": ref["config"]["model"],

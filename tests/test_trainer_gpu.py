@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 from torch.utils.data import DataLoader, random_split
@@ -64,9 +65,9 @@ def test_fused_matches_autograd_engine_without_dropout():
     assert abs(l_f - l_a) < 5e-3
 
 
-def test_bench_contract_single_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "400", "--warmup", "40"],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+def test_bench_contract_single_gpu(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "400", "--warmup", "40",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
@@ -75,6 +76,13 @@ def test_bench_contract_single_gpu():
         assert k in out
     assert out["n_gpus"] == 1 and out["steps"] == 400 and out["value"] > 0
     assert out["extra"]["losses_finite"]
+    # a plain run: no validation, measured epoch or reference model (those are --full)
+    assert not {"val_loss", "epoch_wall_clock_s_measured", "reference_model_value"} & set(out["extra"])
+    # --dump-outputs: the timed steps' losses and the state they left, float32
+    n_params = 5 * 128 + 128 + 128 * 128 + 128 + 128 * 2 + 2
+    for name, n in (("loss", 400), ("params", n_params), ("adam_m", n_params), ("adam_v", n_params)):
+        x = np.load(os.path.join(str(tmp_path), name + ".npy"))
+        assert x.dtype == np.float32 and x.shape == (n,) and np.isfinite(x).all(), name
 
 
 @pytest.mark.parametrize("hidden", [(64,), (128, 128)])
