@@ -13,6 +13,10 @@ struct Knobs {
   int mlp_force_lds = 0;    // DCT_MLP_KERNEL=lds: the LDS/block kernels even where the wave kernel fits
   int mlp_block = -1;       // DCT_MLP_BLOCK: -1 auto, 0 generic LDS trainer, 3 force mlp_block3, 8 mlp_block5's
                             // two-micro-batch kernels at every batch (tests: == the one-micro-batch kernels at B <= 4)
+  int b5_sched = -1;        // DCT_B5_SCHED: mlp_block5's one-rank batch <= 4 train kernels: -1 the default step
+                            // schedule (blk5::SCHED_DEFAULT), 0 the previous one (the reference of the bit-for-bit
+                            // test and of same-binary A/Bs), 1 the default one; 256 + mask: one of the item
+                            // masks an A/B build (-DB5_SCHED_AB) carries, the default schedule elsewhere
   // wide-MLP step executor (mlp_executor.cpp; copied into each executor at construction)
   int fused_head = 1;       // DCT_FUSED_HEAD=0: the four-kernel head chain
   int dw_into_adam = 1;     // DCT_DW_INTO_ADAM=0: dW through g and the reduce pass

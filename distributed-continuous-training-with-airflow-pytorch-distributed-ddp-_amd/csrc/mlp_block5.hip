@@ -2,6 +2,7 @@
 // host-side checks of the 3x128 weather trainer; device code in mlp_block5_impl.h.  Compiled with
 // the max-ILP machine scheduler (_build.py FILE_FLAGS): 3.90 -> 3.80 us/step at one rank
 // (profiles/b5_sched_strategy_ab_r4.log).
+#include "knobs.h"
 #include "mlp_block5_impl.h"
 
 namespace dct {
@@ -45,9 +46,37 @@ size_t mlp_block5_xg_bytes(int world) {
   }
 }
 
+// one-rank batch <= 4 train launch under the step schedule DCT_B5_SCHED selects (knobs.h): 0 the
+// previous schedule, anything else the default one.  An A/B build (-DB5_SCHED_AB) also carries the
+// single-item and leave-one-out masks of the headline variant (CE, no weight decay): 256 + mask.
+template <bool WD, int LK, bool PROF = false>
+static void b5_launch_sched(int sched, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
+  using namespace blk5;
+  if (sched == 0) return b5_launch<WD, LK, PROF>(bytes, st, sh, a);
+#ifdef B5_SCHED_AB
+  if constexpr (!WD && LK == 0 && !PROF) {
+    constexpr int D = SCHED_DEFAULT;
+    constexpr int NWT = D & ~(SCH_WT1 | SCH_WT2);  // the default without hoisted transposes
+    constexpr int masks[] = {SCH_DROP, SCH_ADAM_TAB, SCH_WT1, SCH_WT2, SCH_WT1 | SCH_WT2, NWT, NWT | SCH_WT2,
+                             NWT | SCH_WT1 | SCH_WT2, D & ~SCH_DROP, D & ~SCH_ADAM_TAB};
+    bool done = false;
+    b5x::static_for<sizeof(masks) / sizeof(masks[0])>([&](auto i) {
+      constexpr int M = masks[decltype(i)::value];
+      if (!done && sched == 256 + M && M != D) {
+        b5_launch<WD, LK, false, true, true, 1, -1, 1, M>(bytes, st, sh, a);
+        done = true;
+      }
+    });
+    if (done) return;
+  }
+#endif
+  b5_launch<WD, LK, PROF, true, true, 1, -1, 1, SCHED_DEFAULT>(bytes, st, sh, a);
+}
+
 hipError_t mlp_launch_block5(const MlpShape& sh, const MlpArgs& a, hipStream_t st) {
   const size_t bytes = (size_t)blk5::LDS_FLOATS * sizeof(float);
   const bool wd = a.wd != 0.f;
+  const int sched = knobs().b5_sched;
   if (a.B > blk5::B || sh.mlp_block == 8) {
     mlp_launch_block5_b8(bytes, st, sh, a);  // two micro-batches per step, every world size
   } else if (a.xg_world > 1) {
@@ -56,14 +85,14 @@ hipError_t mlp_launch_block5(const MlpShape& sh, const MlpArgs& a, hipStream_t s
     if (a.loss_kind == 0) b5_launch<false, 0, false, true, false>(bytes, st, sh, a);
     else b5_launch<false, 1, false, true, false>(bytes, st, sh, a);
   } else if (a.prof) {  // per-phase cycle stamps (tools/prof_block.py)
-    if (a.loss_kind == 0) b5_launch<true, 0, true>(bytes, st, sh, a);
-    else b5_launch<true, 1, true>(bytes, st, sh, a);
+    if (a.loss_kind == 0) b5_launch_sched<true, 0, true>(sched, bytes, st, sh, a);
+    else b5_launch_sched<true, 1, true>(sched, bytes, st, sh, a);
   } else if (a.loss_kind == 0) {
-    if (wd) b5_launch<true, 0>(bytes, st, sh, a);
-    else b5_launch<false, 0>(bytes, st, sh, a);
+    if (wd) b5_launch_sched<true, 0>(sched, bytes, st, sh, a);
+    else b5_launch_sched<false, 0>(sched, bytes, st, sh, a);
   } else {
-    if (wd) b5_launch<true, 1>(bytes, st, sh, a);
-    else b5_launch<false, 1>(bytes, st, sh, a);
+    if (wd) b5_launch_sched<true, 1>(sched, bytes, st, sh, a);
+    else b5_launch_sched<false, 1>(sched, bytes, st, sh, a);
   }
   return hipGetLastError();
 }

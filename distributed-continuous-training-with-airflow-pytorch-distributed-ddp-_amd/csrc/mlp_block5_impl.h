@@ -59,6 +59,21 @@ constexpr int LDS_FLOATS = Lds<MBMAX>::TOTAL > 2 * STG ? Lds<MBMAX>::TOTAL : 2 *
 static_assert(LDS_FLOATS * 4 <= 160 * 1024, "fits the CU");
 using Stg = bku::Stage<H, NT>;
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+// Step-schedule items of the one-rank batch <= 4 train kernels (template parameter SCH, a mask):
+// work that does not depend on this step's gradients leaves the contended backward (where every
+// instruction of either SIMD partner is on the younger wave's path) for the barrier A -> B window,
+// in which both waves of a SIMD mostly wait on LDS and on each other.  Every item keeps each value's
+// instruction sequence, so the results are bit for bit those of SCH = 0.
+//   DROP        next step's dropout factors: hashed behind the A -> B window's LDS reads
+//   ADAM_TAB    Adam's per-step scalars A / E: lane i evaluates them for step t + i once every 64
+//               steps, one readlane each per step (instead of 2 exp, 2 rcp, 1 rsq + ~8 VALU per step)
+//   WT1 * n     dZ1's quad transposes of the first n = 0..3 W1 k-blocks (8 MFMAs, 8 registers each): in the
+//               window (SCH_WT2 = 2 blocks, SCH_WT1 | SCH_WT2 = 3)
+// Measured and not kept (profiles/b5_sched_ab_r7.log): the next input tile read before the dW1 pass
+// (alone +1.2 %), W1 Adam beside the dW1 MFMAs as scalar fmas instead of packed (+10 %), two or three
+// hoisted transpose blocks with the other items (slower than one).
+constexpr int SCH_DROP = 1, SCH_ADAM_TAB = 2, SCH_WT1 = 8, SCH_WT2 = 16;
+constexpr int SCHED_DEFAULT = SCH_DROP | SCH_ADAM_TAB | SCH_WT1;
 }  // namespace blk5
 
 // ---- data parallelism inside the persistent launch (XW = 2 / 4 / 8 ranks, one per GPU) ---------
@@ -236,13 +251,18 @@ __device__ __forceinline__ void adam_v2(v2f& p, v2f g, v2f& m, v2f& v, float b1,
 // the previous step's all-reduced loss to loss_out[cursor - 1]; no moments read or written);
 // XW > 1: train mode of one rank of XW data-parallel ranks (b5x above); RK >= 0: that rank as a
 // compile-time constant (every ownership test folds, the all-gather loads land straight in the W1
-// registers; fewer live registers and spills than the runtime-rank kernel, RK = -1)
-template <bool WD, int LK, bool PROF = false, bool DXM = true, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1>
+// registers; fewer live registers and spills than the runtime-rank kernel, RK = -1);
+// SCH: step-schedule items (blk5::SCH_*; one-rank train mode at MB = 1 only, 0 = the previous schedule)
+template <bool WD, int LK, bool PROF = false, bool DXM = true, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1,
+          int SCH = 0>
 __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, MlpArgs a) {
   using namespace blk5;
   using namespace bku;
   static_assert(XW == 1 || (ADAM && XW >= 2 && XW <= 8), "exchange: train mode, 2..8 ranks");
   static_assert(MB >= 1 && MB <= MBMAX, "micro-batches per step");
+  static_assert(SCH == 0 || (XW == 1 && MB == 1 && ADAM), "step-schedule items: one-rank train mode, one micro-batch");
+  constexpr bool S_DROP = (SCH & SCH_DROP) != 0, S_TAB = (SCH & SCH_ADAM_TAB) != 0;
+  constexpr int HQ = DXM ? (SCH / SCH_WT1) & 3 : 0;  // hoisted W1 transpose blocks
   using LY = Lds<MB>;
   constexpr int RB = LY::RB, XT = LY::XT, LAB = LY::LAB, MSK = LY::MSK, LOGP = LY::LOGP, H1W = LY::H1W;
   constexpr int H1X = LY::H1X, PART = LY::PART, W2L = LY::W2L, B2L = LY::B2L, ABT = LY::ABT, TOTAL = LY::TOTAL;
@@ -496,6 +516,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   for (int i = 0; i < 4; ++i) eye[i] = r0 == i ? 1.f : 0.f;
   const int cb = (l >> 2) & 1;  // loss role: class cb of row r0 (wave share l / 8)
   int xb = 0;
+  float tabA = 0.f, tabE = 0.f;  // SCH_ADAM_TAB: lane i's Adam scalars of step (64-step block start) + i
   if (a.tune == 1 && w >= NW / 2) __builtin_amdgcn_s_setprio(1);
   if (a.tune == 2 && w < NW / 2) __builtin_amdgcn_s_setprio(1);
   if constexpr (PROF) {
@@ -524,6 +545,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     float h2 = 0.f, h1 = 0.f;
     float gw0s = 0.f, gw1s = 0.f, gb1s = 0.f, gbs = 0.f, g0s = 0.f, g1s = 0.f, db0s = 0.f;
     float aA = 0.f, aE = 0.f;
+    float f1n = 0.f, f2n = 0.f;           // SCH_DROP: next step's dropout factors (from the A -> B window)
+    f32x4_t wth[HQ > 0 ? HQ : 1][2];     // SCH_WT*: transposed W1 quads of k-blocks q < HQ
     v2f GO[NO];  // XW > 1 (reduce-scatter): gradients of the W1 pairs this rank owns
 #pragma unroll
     for (int t2 = 0; t2 < NO; ++t2) GO[t2] = (v2f){0.f, 0.f};
@@ -662,6 +685,44 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         float q[NW];
 #pragma unroll
         for (int ww = 0; ww < NW; ++ww) q[ww] = pr[4 * ww];
+        if constexpr (SCH != 0) {
+          // ---- gradient-free work of the step, issued behind the LDS reads above and in front of
+          // their first use (pinned: the scheduler otherwise sinks it back into the backward)
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr (HQ > 0) {
+#pragma unroll
+            for (int qq = 0; qq < HQ; ++qq)
+#pragma unroll
+              for (int j = 0; j < 2; ++j) {
+                const float wq[4] = {W[j][2 * qq].x, W[j][2 * qq].y, W[j][2 * qq + 1].x, W[j][2 * qq + 1].y};
+                wth[qq][j] = quad_transpose_mf(wq, eye);
+              }
+          }
+          if constexpr (S_DROP) {
+            // (the asm statements hold both ends: instruction selection may otherwise emit the hash in
+            // front of barrier A, and code sinking moves values only used next step back to the loop end)
+            uint32_t gnext = gstep + 1u;
+            asm volatile("" : "+s"(gnext));
+            f1n = b5_drop(a.seed, gnext, el0[0], p_drop, scale);  // p_drop = 0: always 1
+            f2n = b5_drop(a.seed, gnext, el1[0], p_drop, scale);
+            asm volatile("" : "+v"(f1n), "+v"(f2n));
+          }
+          if constexpr (S_TAB) {
+            const int ti = s & 63;
+            if (ti == 0) {  // wave-uniform: the next 64 steps' scalars, one per lane
+              asm volatile("");  // a real branch: without it the block is if-converted and runs every step
+              const float tl = (float)(t + l);
+              const float step_size = a.lr * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, tl));
+              const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(l2b2, tl));
+              const float rss = __builtin_amdgcn_rcpf(step_size);
+              tabA = sqc2 * rbc2 * rss * rc1;
+              tabE = a.eps * rss * rc1;
+            }
+            aA = rl(tabA, ti);
+            aE = rl(tabE, ti);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
         const float z = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
         h2 = fmaxf(z + pb1, 0.f) * f2[hf];
         const float t0s = sum_bits2to5(pw2[0] * h2), t1s = sum_bits2to5(pw2[1] * h2);  // row r0's shares
@@ -734,7 +795,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       }
       B5STAMP(5)
 
-      if (last) {
+      if (last && !S_TAB) {
         const float step_size = a.lr * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, (float)t));
         const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(l2b2, (float)t));
         const float rss = __builtin_amdgcn_rcpf(step_size);
@@ -822,7 +883,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             const float wq[4] = {W[j][2 * q].x, W[j][2 * q].y, W[j][2 * q + 1].x, W[j][2 * q + 1].y};
-            const f32x4_t wt = quad_transpose_mf(wq, eye);
+            const f32x4_t wt = q < HQ ? wth[q < HQ ? q : 0][j] : quad_transpose_mf(wq, eye);
             acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[j] = mfma4(wt[i], dzt[j][i], acc[j]);
@@ -885,10 +946,15 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       if (abort_step) break;
     }
     // next step's dropout factors (independent work for the Adam stream below)
+    if constexpr (S_DROP) {
+      f1[0] = f1n;
+      f2[0] = f2n;
+    } else {
 #pragma unroll
-    for (int hf = 0; hf < MB; ++hf) {
-      f1[hf] = b5_drop(a.seed, gstep + 1u, el0[hf], p_drop, scale);  // p_drop = 0: always 1
-      f2[hf] = b5_drop(a.seed, gstep + 1u, el1[hf], p_drop, scale);
+      for (int hf = 0; hf < MB; ++hf) {
+        f1[hf] = b5_drop(a.seed, gstep + 1u, el0[hf], p_drop, scale);  // p_drop = 0: always 1
+        f2[hf] = b5_drop(a.seed, gstep + 1u, el1[hf], p_drop, scale);
+      }
     }
     B5STAMP(7)
     // dW1 + packed Adam (one rank) / + reduce-scatter pushes here, after dZ1 and dW0 (XW > 1: issued
@@ -1185,12 +1251,13 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
 #undef B5STAMP
 
 // one launch of an instantiation; its dynamic-LDS limit (two 64-KB staging tiles) is raised once
-template <bool WD, int LK, bool PROF = false, bool DXM = true, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1>
+template <bool WD, int LK, bool PROF = false, bool DXM = true, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1,
+          int SCH = 0>
 inline void b5_launch(size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)mlp_block5_kernel<WD, LK, PROF, DXM, ADAM, XW, RK, MB>,
+  static const hipError_t attr = hipFuncSetAttribute((const void*)mlp_block5_kernel<WD, LK, PROF, DXM, ADAM, XW, RK, MB, SCH>,
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   (void)attr;
-  hipLaunchKernelGGL((mlp_block5_kernel<WD, LK, PROF, DXM, ADAM, XW, RK, MB>), dim3(1), dim3(blk5::NT), bytes, st, sh, a);
+  hipLaunchKernelGGL((mlp_block5_kernel<WD, LK, PROF, DXM, ADAM, XW, RK, MB, SCH>), dim3(1), dim3(blk5::NT), bytes, st, sh, a);
 }
 
 
