@@ -49,7 +49,19 @@ struct MlpPlan {
     const bool force_lds = dct::knobs().mlp_force_lds != 0;
     use_wave = (!force_lds && dct_mlp_wave_supported(dims.data(), (int)dims.size() - 1, 1)) ? 1 : 0;
     if (use_wave) supported = 1;
+    // batch-tiled trainer: the plan of batch 17..1024 (bmax 1024, which overflows the LDS trainer's
+    // budget: its own shape check decides), or forced at the small batches by DCT_MLP_BLOCK=tile
+    const bool tile_ok = dct_mlp_tile_supported(dims.data(), (int)dims.size() - 1) != 0;
+    if (bmax == 1024) {
+      use_tile = tile_ok ? 1 : 0;
+      supported = use_tile;
+      use_wave = 0;
+    } else if (dct::knobs().mlp_block == dct::MLP_BLOCK_TILE) {
+      use_tile = tile_ok ? 1 : 0;
+      if (!tile_ok) reinterpret_cast<dct::MlpShape*>(shape.data())->mlp_block = -1;
+    }
   }
+  int use_tile = 0;  // mlp_tile.hip runs this plan's training launches
   const dct::MlpShape* sh() const { return reinterpret_cast<const dct::MlpShape*>(shape.data()); }
 };
 
@@ -115,6 +127,8 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
     if (!xg_recv || !xg_peers || !xg_status || xg_rank < 0 || xg_rank >= xg_world)
       throw std::invalid_argument("in-kernel all-reduce: exchange buffers / rank missing");
   }
+  if (plan.use_tile && (xg_world > 1 || pending))
+    throw std::invalid_argument("the batch-tiled trainer has no in-kernel all-reduce and no update-then-grad step");
   if (pending && (mode != 1 || !plan.use_wave || !mo || !vo))
     throw std::invalid_argument("update-then-grad needs grad mode, m/v and the single-wave kernel");
   if (cursor && mode != 1) throw std::invalid_argument("cursor is only valid in grad mode");
@@ -125,7 +139,10 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
 
 static void launch_train(const MlpPlan& plan, const dct::MlpArgs& a, uintptr_t stream) {
   const dct::MlpShape* sh = plan.sh();
-  if (plan.use_wave && dct_mlp_wave_supported(sh->dims, sh->L, a.B))
+  if (plan.use_tile) {
+    if (!a.tile_ws) throw std::invalid_argument("the batch-tiled trainer needs its slot workspace");
+    check(dct_mlp_tile_train(sh->dims, sh->L, &a, reinterpret_cast<void*>(stream)), "mlp_tile_train");
+  } else if (plan.use_wave && dct_mlp_wave_supported(sh->dims, sh->L, a.B))
     check(dct_mlp_wave_train(sh->dims, sh->L, &a, reinterpret_cast<void*>(stream)), "mlp_wave_train");
   else
     check(dct_mlp_train(plan.shape.data(), &a, reinterpret_cast<void*>(stream)), "mlp_train");
@@ -214,6 +231,7 @@ PYBIND11_MODULE(_dct_native, m) {
       .def_readonly("threads", &MlpPlan::nt)
       .def_readonly("max_blocks_per_thread", &MlpPlan::maxblk)
       .def_readonly("use_wave", &MlpPlan::use_wave)
+      .def_readonly("use_tile", &MlpPlan::use_tile)
       .def_property_readonly("num_params", [](const MlpPlan& p) { return p.sh()->P; })
       .def_property_readonly("lds_bytes", [](const MlpPlan& p) { return p.sh()->lds_floats * 4; })
       .def_property_readonly("bmax", [](const MlpPlan& p) { return p.sh()->bmax; })
@@ -225,11 +243,13 @@ PYBIND11_MODULE(_dct_native, m) {
              float eps, float wd, float dropout, uint32_t seed, uint32_t step_base, uintptr_t loss_out, int mode,
              int loss_kind, uintptr_t step_counter, uintptr_t cursor, uintptr_t prof, uintptr_t pending,
              uintptr_t stage, uintptr_t stream, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
-             uintptr_t xg_status, int64_t xg_timeout, int xg_poll) {
-            const dct::MlpArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
+             uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t tile_ws, int64_t tile_ws_floats) {
+            dct::MlpArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
                                                    b1, b2, eps, wd, dropout, seed, step_base, loss_out, mode,
                                                    loss_kind, step_counter, cursor, prof, pending, stage, xg_recv,
                                                    xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll);
+            a.tile_ws = P<float>(tile_ws);
+            a.tile_ws_floats = tile_ws_floats;
             launch_train(plan, a, stream);
           },
           py::arg("p"), py::arg("m"), py::arg("v"), py::arg("grad_out"), py::arg("X"), py::arg("ldx"), py::arg("Y"),
@@ -238,19 +258,22 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("step_base"), py::arg("loss_out"), py::arg("mode"), py::arg("loss_kind"), py::arg("step_counter"),
           py::arg("cursor"), py::arg("prof") = 0, py::arg("pending") = 0, py::arg("stage") = 0,
           py::arg("stream") = 0, py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
-          py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL, py::arg("xg_poll") = 0)
+          py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL, py::arg("xg_poll") = 0,
+          py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0)
       .def(
           "prepare_train",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t X, int ldx, uintptr_t Y,
              uintptr_t idx, int n_items, int B, float lr, float b1, float b2, float eps, float wd, float dropout,
              uint32_t seed, uintptr_t loss_out, int64_t loss_len, int loss_kind, uintptr_t step_counter,
              uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank, uintptr_t xg_status,
-             int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks) {
+             int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks, uintptr_t tile_ws, int64_t tile_ws_floats) {
             auto l = std::make_unique<MlpLaunch>(MlpLaunch{plan});
             l->base = make_train_args(plan, p, mo, vo, 0, X, ldx, Y, idx, n_items, B, 1, 0, lr, b1, b2, eps, wd,
                                       dropout, seed, 0, loss_out, 0, loss_kind, step_counter, 0, 0, 0, 0, xg_recv,
                                       xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll);
             l->base.xg_ticks = P<unsigned long long>(xg_ticks);
+            l->base.tile_ws = P<float>(tile_ws);
+            l->base.tile_ws_floats = tile_ws_floats;
             l->n_items = n_items;
             l->loss_len = loss_out ? loss_len : 0;
             return l;
@@ -260,7 +283,7 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("dropout"), py::arg("seed"), py::arg("loss_out"), py::arg("loss_len"), py::arg("loss_kind"),
           py::arg("step_counter"), py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL,
-          py::arg("xg_poll") = 0, py::arg("xg_ticks") = 0)
+          py::arg("xg_poll") = 0, py::arg("xg_ticks") = 0, py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0)
       .def(
           "eval",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items,
@@ -676,6 +699,9 @@ PYBIND11_MODULE(_dct_native, m) {
     if (dims.size() != 4 || !dct::mlp_block5_shape_ok(dims.data(), 3, B)) return 0;
     return (int64_t)dct::mlp_block5_xg_bytes(world);
   }, py::arg("dims"), py::arg("batch"), py::arg("world"));
+  m.def("mlp_tile_ws_floats", [](const std::vector<int>& dims, int B) {
+    return (int64_t)dct_mlp_tile_ws_floats(dims.data(), (int)dims.size() - 1, B);
+  });
   m.def("mlp_xg_slab_granules", [](const std::vector<int>& dims) {
     return (int64_t)dct_mlp_xg_slab_granules(dims.data(), (int)dims.size() - 1);
   });

@@ -20,7 +20,8 @@ void knobs_reload() {
   Knobs k;
   const char* mk = std::getenv("DCT_MLP_KERNEL");
   k.mlp_force_lds = (mk && std::strcmp(mk, "lds") == 0) ? 1 : 0;
-  if (const char* b = std::getenv("DCT_MLP_BLOCK")) k.mlp_block = (b[0] == '0') ? 0 : (b[0] == '3' ? 3 : (b[0] == '8' ? 8 : -1));
+  if (const char* b = std::getenv("DCT_MLP_BLOCK"))
+    k.mlp_block = (std::strcmp(b, "tile") == 0) ? MLP_BLOCK_TILE : (b[0] == '0') ? 0 : (b[0] == '3' ? 3 : (b[0] == '8' ? 8 : -1));
   k.b5_sched = env_int("DCT_B5_SCHED", -1);
   if (k.b5_sched < 0) k.b5_sched = -1;
   k.fused_head = env_int("DCT_FUSED_HEAD", 1) != 0;

@@ -12,7 +12,8 @@ struct Knobs {
   // fused MLP trainers (mlp_fused.hip dispatch, bindings.cpp plan)
   int mlp_force_lds = 0;    // DCT_MLP_KERNEL=lds: the LDS/block kernels even where the wave kernel fits
   int mlp_block = -1;       // DCT_MLP_BLOCK: -1 auto, 0 generic LDS trainer, 3 force mlp_block3, 8 mlp_block5's
-                            // two-micro-batch kernels at every batch (tests: == the one-micro-batch kernels at B <= 4)
+                            // two-micro-batch kernels at every batch (tests: == the one-micro-batch kernels at B <= 4),
+                            // MLP_BLOCK_TILE ("tile") the batch-tiled trainer (mlp_tile.hip) at batch <= 16 too
   int b5_sched = -1;        // DCT_B5_SCHED: mlp_block5's one-rank batch <= 4 train kernels: -1 the default step
                             // schedule (blk5::SCHED_DEFAULT), 0 the previous one (the reference of the bit-for-bit
                             // test and of same-binary A/Bs), 1 the default one; 256 + mask: one of the item
@@ -31,6 +32,8 @@ struct Knobs {
   int reducer_flag_edges = 1;   // DCT_REDUCER_FLAG_EDGES: eager fork / join edges as device counters (1) or events (0)
   int rccl_one_rank = 0;    // DCT_RCCL_ONE_RANK=1: call RCCL for one-rank in-place collectives too
 };
+
+constexpr int MLP_BLOCK_TILE = 32;
 
 const Knobs& knobs();
 void knobs_reload();

@@ -116,6 +116,10 @@ struct MlpArgs {
   float k_l2b1, k_l2b2;  // log2(b1), log2(b2) (Adam bias corrections as one exp2 each)
   float k_rc1, k_rc2;  // 1 / (1 - b1), 1 / (1 - b2) (scaled-moment Adam)
   float k_sqc2;        // sqrt(1 - b2)
+  // batch-tiled trainer (mlp_tile.hip): slot workspace [ceil(B / 32)][Pp] partial gradients + loss of a step,
+  // the fold kernel's arrival counter in its last four floats
+  float* tile_ws;
+  long long tile_ws_floats;
 };
 
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
@@ -151,6 +155,10 @@ int dct_mlp_eval(const void* shape, const dct::MlpArgs* a, int grid, void* strea
 int dct_mlp_wave_supported(const int* dims, int L, int B);
 int dct_mlp_wave_train(const int* dims, int L, const dct::MlpArgs* a, void* stream);
 size_t dct_mlp_xg_slab_granules(const int* dims, int L);
+// batch-tiled trainer for per-rank batch 17..1024 (mlp_tile.hip; DCT_MLP_BLOCK=tile forces it at smaller batches)
+int dct_mlp_tile_supported(const int* dims, int L);
+long long dct_mlp_tile_ws_floats(const int* dims, int L, int B);
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream);
 int dct_adam_flat(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
                   float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
                   const int* step_counter, void* stream);

@@ -1,0 +1,479 @@
+// mlp_tile: batch-tiled fused fp32 trainer for the weather MLPs at per-rank batch 17..1024.
+//
+// The LDS / block / wave trainers keep a whole step in ONE workgroup, which stops paying at
+// batch > 16.  Here one optimizer step is a grid of T = ceil(B / R) workgroups, R = 32 rows per
+// workgroup (two M = 16 row blocks per MFMA column block, so every weight fragment a wave loads
+// feeds two MFMAs; 4 waves per workgroup), followed by a small fold launch:
+//
+//   step kernel (grid T): gather rows X[idx[...]] + labels -> layer 0 on the VALU (D0 <= 32) ->
+//     hidden x hidden forward on v_mfma_f32_16x16x4_f32 (exact fp32) -> head (C <= 4) + CE / MSE
+//     and dlogits / bs on the VALU -> dX and dW of the hidden x hidden layer on the MFMA, the
+//     narrow layers on the VALU -> the tile's partial gradients [P] and partial loss sum go to its
+//     own slot of the workspace [T][Pp] with plain vector stores.  Rows >= bs contribute zeros, a
+//     tile without a live row writes a zero slot.
+//   fold kernel (grid ceil((P + 1) / 256)): sums the T slots in ascending tile index (bit-identical
+//     whatever order the tiles finished in), then Adam (adam_elem, train mode) or grad_out (grad
+//     mode), the batch loss, and the device step counter / batch cursor.  The kernel boundary is
+//     what makes the slots visible across XCDs; no workgroup ever waits on another one.  The
+//     counters are advanced by the fold's last-arriving workgroup (an arrival counter that it
+//     leaves at zero, so a captured launch pair replays).
+//
+// Weights are read straight from the flat parameter buffer (L2 resident, <= 85 KB); activations
+// and dZ of the tile live in LDS with the two narrow layers' weights (91.5 KB for the 3-layer nets, 57.7 KB for the 2-layer ones).  No LDS-DMA loads.
+// Shapes: 2 or 3 linear layers, D0 1..32, hidden widths multiples of 16 in 16..128, C 2..4.
+// Dropout key: mix_hash(seed + (b >> 6) * 0x9E3779B9, gstep, (LI * 64 + (b & 63)) * 65536 + o),
+// b = row within the batch: rows < 64 draw the LDS kernel's mask (ops/fused_mlp.py
+// dropout_keep_mask is the host mirror).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mlp_fused_impl.h"
+
+namespace dct {
+namespace tile {
+
+constexpr int R = 32;     // rows per workgroup
+constexpr int NT = 256;   // 4 waves
+constexpr int LDH = 132;  // LDS row stride of the hidden activations / dZ (128 + 4)
+constexpr int LDX = 33;   // LDS row stride of the input tile and of W0
+constexpr int BMAX = 1024;
+constexpr int FOLD_NT = 256;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct Plan {
+  int L;        // 2 or 3 linear layers
+  int D0, H1, H2, C;  // H2 = 0 when L == 2
+  int K;        // width feeding the head (H2, or H1 when L == 2)
+  int woff[3], boff[3];  // torch flat offsets (layer 2 unused when L == 2; the head is layer L - 1)
+  int P, Pp;    // parameters, slot stride (floats)
+};
+
+static bool make_plan(Plan* tp, const int* dims, int L) {
+  if (L != 2 && L != 3) return false;
+  const int D0 = dims[0], C = dims[L];
+  if (D0 < 1 || D0 > 32 || C < 2 || C > 4) return false;
+  for (int l = 1; l < L; ++l)
+    if (dims[l] < 16 || dims[l] > 128 || dims[l] % 16 != 0) return false;
+  *tp = Plan{};
+  tp->L = L;
+  tp->D0 = D0;
+  tp->H1 = dims[1];
+  tp->H2 = (L == 3) ? dims[2] : 0;
+  tp->C = C;
+  tp->K = dims[L - 1];
+  int flat = 0;
+  for (int l = 0; l < L; ++l) {
+    tp->woff[l] = flat;
+    flat += dims[l] * dims[l + 1];
+    tp->boff[l] = flat;
+    flat += dims[l + 1];
+  }
+  tp->P = flat;
+  tp->Pp = (flat + 1 + 3) & ~3;
+  return true;
+}
+
+// LDS carve (floats)
+struct Lds {
+  int x0, w0, wl, a1, dz1, a2, dz2, dzl, lossr, lab, total;
+};
+__host__ __device__ inline Lds lds_layout(int L) {
+  Lds o;
+  int off = 0;
+  o.x0 = off; off += R * LDX;
+  o.w0 = off; off += 128 * LDX;
+  o.wl = off; off += 4 * 128 + 4;  // head weights [C][K] + bias
+  o.a1 = off; off += R * LDH;
+  o.dz1 = off; off += R * LDH;
+  o.a2 = off; if (L == 3) off += R * LDH;
+  o.dz2 = off; if (L == 3) off += R * LDH;
+  o.dzl = off; off += R * 4;
+  o.lossr = off; off += R;
+  o.lab = off; off += R;
+  o.total = off;
+  return o;
+}
+
+__device__ __forceinline__ float drop_apply(float z, uint32_t seed, uint32_t gstep, int LI, int b, int o, float p,
+                                            float scale) {
+  const uint32_t h = mix_hash(seed + (uint32_t)(b >> 6) * 0x9E3779B9u, gstep,
+                              (uint32_t)((LI * 64 + (b & 63)) * 65536 + o));
+  return (u01(h) < p) ? 0.f : z * scale;
+}
+
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+template <int L>
+__global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Lds lo = lds_layout(L);
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int j = lane & 15, q = lane >> 4;
+  const int D0 = tp.D0, H1 = tp.H1, H2 = tp.H2, C = tp.C, K = tp.K;
+  const int B = a.B;
+
+  int cur = 0;
+  if (a.cursor) cur = __hip_atomic_load(a.cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  uint32_t gstep = a.step_base;
+  if (a.step_counter)
+    gstep = (uint32_t)__hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int bs = max(0, min(B, a.n_items - cur * B));
+  const int row0 = blockIdx.x * R;
+  const bool dropping = a.dropout > 0.f;
+  const float dscale = dropping ? a.k_drop_scale : 1.0f;
+
+  float* X0 = lds + lo.x0;
+  float* W0s = lds + lo.w0;
+  float* Wl = lds + lo.wl;
+  float* A1 = lds + lo.a1;
+  float* dZ1 = lds + lo.dz1;
+  float* A2 = lds + lo.a2;
+  float* dZ2 = lds + lo.dz2;
+  float* dZL = lds + lo.dzl;
+  float* lossr = lds + lo.lossr;
+  int* lab = reinterpret_cast<int*>(lds + lo.lab);
+  float* slot = a.tile_ws + (size_t)blockIdx.x * tp.Pp;
+
+  // ---- this wave's W1 fragments of the forward MFMA (column blocks wave, wave + 4): issued first, so
+  // their L2 round trips overlap the gather and layer 0 instead of chaining inside the k loop
+  float4 wf[2][8];
+  if (L == 3) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int cb = wave + 4 * c;
+      const float* wrow = a.p + tp.woff[1] + (size_t)(cb * 16 + j) * H1 + 4 * q;
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        wf[c][i] = (cb * 16 < H2 && i * 16 < H1) ? *reinterpret_cast<const float4*>(wrow + i * 16)
+                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+
+  // ---- gather the tile's rows and labels; stage W0
+  for (int e = tid; e < R * D0; e += NT) {
+    const int r = e / D0, k = e - r * D0;
+    const int gb = row0 + r;
+    float x = 0.f;
+    if (gb < bs) x = a.X[(size_t)a.idx[(size_t)cur * B + gb] * a.ldx + k];
+    X0[r * LDX + k] = x;
+  }
+  if (tid < R) {
+    const int gb = row0 + tid;
+    lab[tid] = (gb < bs) ? a.Y[a.idx[(size_t)cur * B + gb]] : 0;
+  }
+  for (int e = tid; e < H1 * D0; e += NT) {
+    const int o = e / D0, k = e - o * D0;
+    W0s[o * LDX + k] = a.p[tp.woff[0] + e];
+  }
+  for (int e = tid; e < C * K; e += NT) Wl[e] = a.p[tp.woff[L - 1] + e];
+  if (tid < C) Wl[4 * 128 + tid] = a.p[tp.boff[L - 1] + tid];
+  if (tid < H1) W0s[tid * LDX + 32] = a.p[tp.boff[0] + tid];
+  __syncthreads();
+
+  // ---- layer 0 (VALU): A1 = dropout(relu(X0 W0^T + b0))
+  for (int e = tid; e < R * H1; e += NT) {
+    const int r = e / H1, o = e - r * H1;
+    float z = W0s[o * LDX + 32];  // b0, staged in the pad column
+    for (int k = 0; k < D0; ++k) z = fmaf(W0s[o * LDX + k], X0[r * LDX + k], z);
+    z = fmaxf(z, 0.f);
+    if (dropping) z = drop_apply(z, a.seed, gstep, 0, row0 + r, o, a.dropout, dscale);
+    A1[r * LDH + o] = z;
+  }
+  __syncthreads();
+
+  // ---- layer 1 (MFMA): A2 = dropout(relu(A1 W1^T + b1)); a wave owns column blocks wave, wave + 4
+  if (L == 3) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int cb = wave + 4 * c;
+      if (cb * 16 >= H2) break;
+      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+      const float* ar0 = A1 + j * LDH + 4 * q;
+      const float* ar1 = ar0 + 16 * LDH;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (i * 16 >= H1) break;
+        // k of MFMA t, lane group q: 16 i + 4 q + t (the same permutation on both operands)
+        const float4 wv = wf[c][i];
+        const float4 a0 = *reinterpret_cast<const float4*>(ar0 + i * 16);
+        const float4 a1 = *reinterpret_cast<const float4*>(ar1 + i * 16);
+        acc0 = mfma4(a0.x, wv.x, acc0);
+        acc1 = mfma4(a1.x, wv.x, acc1);
+        acc0 = mfma4(a0.y, wv.y, acc0);
+        acc1 = mfma4(a1.y, wv.y, acc1);
+        acc0 = mfma4(a0.z, wv.z, acc0);
+        acc1 = mfma4(a1.z, wv.z, acc1);
+        acc0 = mfma4(a0.w, wv.w, acc0);
+        acc1 = mfma4(a1.w, wv.w, acc1);
+      }
+      const int o = cb * 16 + j;
+      const float bv = a.p[tp.boff[1] + o];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r0 = 4 * q + i, r1 = r0 + 16;
+        float z0 = fmaxf(acc0[i] + bv, 0.f), z1 = fmaxf(acc1[i] + bv, 0.f);
+        if (dropping) {
+          z0 = drop_apply(z0, a.seed, gstep, 1, row0 + r0, o, a.dropout, dscale);
+          z1 = drop_apply(z1, a.seed, gstep, 1, row0 + r1, o, a.dropout, dscale);
+        }
+        A2[r0 * LDH + o] = z0;
+        A2[r1 * LDH + o] = z1;
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- W1 fragments of the dZ1 MFMA (k = the H2 outputs), in flight across the head phases
+  float wb[2][8][4];
+  if (L == 3) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int cb = wave + 4 * c;
+      const float* wcol = a.p + tp.woff[1] + (size_t)(4 * q) * H1 + cb * 16 + j;
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          wb[c][i][t] = (cb * 16 < H1 && i * 16 < H2) ? wcol[(size_t)(i * 16 + t) * H1] : 0.f;
+    }
+  }
+
+  // ---- head (VALU, 8 lanes per row) + loss + dlogits / bs
+  const float* Ah = (L == 3) ? A2 : A1;
+  float* dZh = (L == 3) ? dZ2 : dZ1;
+  {
+    const int r = tid >> 3, part = tid & 7;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int k = part; k < K; k += 8) {
+      const float av = Ah[r * LDH + k];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < C) acc[c] = fmaf(Wl[c * K + k], av, acc[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      acc[c] += __shfl_xor(acc[c], 1);
+      acc[c] += __shfl_xor(acc[c], 2);
+      acc[c] += __shfl_xor(acc[c], 4);
+    }
+    if (part == 0) {
+      float z[4], dz[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) z[c] = (c < C) ? acc[c] + Wl[4 * 128 + c] : 0.f;
+      const bool live = (row0 + r) < bs;
+      const float inv = 1.0f / (float)(bs > 0 ? bs : 1);
+      const LossAcc rl = row_loss4(z, C, lab[r], a.loss_kind, live ? inv : 0.f, dz);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) dZL[r * 4 + c] = (c < C) ? dz[c] : 0.f;
+      lossr[r] = live ? rl.loss : 0.f;
+    }
+  }
+  __syncthreads();
+
+  // ---- head backward (VALU): dZ of the last hidden layer, dW / db of the head
+  for (int e = tid; e < R * K; e += NT) {
+    const int r = e / K, k = e - r * K;
+    float g = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < C) g = fmaf(dZL[r * 4 + c], Wl[c * K + k], g);
+    const float av = Ah[r * LDH + k];
+    dZh[r * LDH + k] = (av > 0.f) ? g * dscale : 0.f;
+  }
+  for (int e = tid; e < C * K; e += NT) {
+    const int c = e / K, k = e - c * K;
+    float g = 0.f;
+    for (int r = 0; r < R; ++r) g = fmaf(dZL[r * 4 + c], Ah[r * LDH + k], g);
+    slot[tp.woff[L - 1] + e] = g;
+  }
+  if (tid < C) {
+    float g = 0.f;
+    for (int r = 0; r < R; ++r) g += dZL[r * 4 + tid];
+    slot[tp.boff[L - 1] + tid] = g;
+  }
+  if (tid == NT - 1) {
+    float s = 0.f;
+    for (int r = 0; r < R; ++r) s += lossr[r];
+    slot[tp.P] = s;
+  }
+  __syncthreads();
+
+  if (L == 3) {
+    // ---- dZ1 = mask(A1) * (dZ2 W1) on the MFMA: k runs over the H2 outputs
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int cb = wave + 4 * c;
+      if (cb * 16 >= H1) break;
+      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+      const float* dr0 = dZ2 + j * LDH + 4 * q;
+      const float* dr1 = dr0 + 16 * LDH;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (i * 16 >= H2) break;
+        const float w0 = wb[c][i][0], w1 = wb[c][i][1], w2 = wb[c][i][2], w3 = wb[c][i][3];
+        const float4 d0 = *reinterpret_cast<const float4*>(dr0 + i * 16);
+        const float4 d1 = *reinterpret_cast<const float4*>(dr1 + i * 16);
+        acc0 = mfma4(d0.x, w0, acc0);
+        acc1 = mfma4(d1.x, w0, acc1);
+        acc0 = mfma4(d0.y, w1, acc0);
+        acc1 = mfma4(d1.y, w1, acc1);
+        acc0 = mfma4(d0.z, w2, acc0);
+        acc1 = mfma4(d1.z, w2, acc1);
+        acc0 = mfma4(d0.w, w3, acc0);
+        acc1 = mfma4(d1.w, w3, acc1);
+      }
+      const int ic = cb * 16 + j;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int r0 = 4 * q + i, r1 = r0 + 16;
+        dZ1[r0 * LDH + ic] = (A1[r0 * LDH + ic] > 0.f) ? acc0[i] * dscale : 0.f;
+        dZ1[r1 * LDH + ic] = (A1[r1 * LDH + ic] > 0.f) ? acc1[i] * dscale : 0.f;
+      }
+    }
+    // ---- dW1 = dZ2^T A1 on the MFMA (M = H2 outputs, N = H1 inputs, k = the tile's 32 rows)
+    const int nib = H1 >> 4;
+    const int ntile = (H2 >> 4) * nib;
+    for (int t = wave; t < ntile; t += 4) {
+      const int ob = t / nib, ib = t - ob * nib;
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const float* dzp = dZ2 + q * LDH + ob * 16 + j;
+      const float* ap = A1 + q * LDH + ib * 16 + j;
+#pragma unroll
+      for (int n = 0; n < R / 4; ++n) acc = mfma4(dzp[4 * n * LDH], ap[4 * n * LDH], acc);
+      float* g = slot + tp.woff[1] + (size_t)(ob * 16 + 4 * q) * H1 + ib * 16 + j;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) g[i * H1] = acc[i];
+    }
+    if (tid < H2) {
+      float g = 0.f;
+      for (int r = 0; r < R; ++r) g += dZ2[r * LDH + tid];
+      slot[tp.boff[1] + tid] = g;
+    }
+    __syncthreads();
+  }
+
+  // ---- dW0 = dZ1^T X0, db0 (VALU)
+  for (int e = tid; e < H1 * D0; e += NT) {
+    const int o = e / D0, k = e - o * D0;
+    float g = 0.f;
+    for (int r = 0; r < R; ++r) g = fmaf(dZ1[r * LDH + o], X0[r * LDX + k], g);
+    slot[tp.woff[0] + e] = g;
+  }
+  if (tid < H1) {
+    float g = 0.f;
+    for (int r = 0; r < R; ++r) g += dZ1[r * LDH + tid];
+    slot[tp.boff[0] + tid] = g;
+  }
+}
+
+// Sum the T slots in ascending tile index; Adam (train mode) or grad_out (grad mode); loss and counters.
+__global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs a, int T, unsigned int* done) {
+  __shared__ int s_cnt[2];
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    s_cnt[0] = a.cursor ? __hip_atomic_load(a.cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    s_cnt[1] = a.step_counter ? __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.t0;
+  }
+  __syncthreads();
+  const int cur = s_cnt[0], tcur = s_cnt[1];
+  const bool adam = (a.mode == 0);
+  const int e = blockIdx.x * FOLD_NT + tid;
+  if (e <= tp.P) {
+    const float* w = a.tile_ws + e;
+    float g = 0.f;
+#pragma unroll 8
+    for (int t = 0; t < T; ++t) g += w[(size_t)t * tp.Pp];
+    if (e < tp.P) {
+      if (adam) {
+        const int t = tcur + 1;
+        const float bc1 = 1.f - pow_t(log2f(a.b1), (float)t);
+        const float bc2 = 1.f - pow_t(log2f(a.b2), (float)t);
+        const float step_size = a.lr / bc1;
+        const float rbc2 = __builtin_amdgcn_rsqf(bc2);
+        float pv = a.p[e], mv = a.m[e], vv = a.v[e];
+        adam_elem(pv, g, mv, vv, a.b1, a.b2, a.wd, step_size, rbc2, a.eps);
+        a.p[e] = pv;
+        a.m[e] = mv;
+        a.v[e] = vv;
+      } else {
+        a.grad_out[e] = g;
+      }
+    } else {
+      const int bs = max(0, min(a.B, a.n_items - cur * a.B));
+      const float bl = bs > 0 ? g / (float)bs : 0.f;
+      if (a.cursor && cur > 0 && a.loss_out) a.loss_out[cur - 1] = a.grad_out[tp.P];
+      if (a.loss_out && !a.cursor) a.loss_out[0] = bl;
+      if (!adam) a.grad_out[tp.P] = bl;
+    }
+  }
+  // the last workgroup to arrive advances the counters: every workgroup has read them by then
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    const unsigned int old = atomicAdd(done, 1u);
+    if (old == gridDim.x - 1) {
+      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.cursor) __hip_atomic_store(a.cursor, cur + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.step_counter) __hip_atomic_store(a.step_counter, tcur + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+template <int L>
+static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* done, hipStream_t st) {
+  const int T = (a0.B + R - 1) / R;
+  const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
+  auto fn = mlp_tile_step_kernel<L>;
+  hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) return e;
+  const int fold_grid = (tp.P + 1 + FOLD_NT - 1) / FOLD_NT;
+  for (int s = 0; s < a0.steps; ++s) {
+    MlpArgs a = a0;
+    a.steps = 1;
+    a.idx = a0.idx + (size_t)s * a0.B;
+    a.n_items = a0.n_items - s * a0.B;
+    a.t0 = a0.t0 + s;
+    a.step_base = a0.step_base + (uint32_t)s;
+    if (a0.loss_out && !a0.cursor) a.loss_out = a0.loss_out + s;
+    hipLaunchKernelGGL(fn, dim3(T), dim3(NT), bytes, st, tp, a);
+    hipLaunchKernelGGL(mlp_tile_fold_kernel, dim3(fold_grid), dim3(FOLD_NT), 0, st, tp, a, T, done);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace tile
+}  // namespace dct
+
+extern "C" {
+
+int dct_mlp_tile_supported(const int* dims, int L) {
+  dct::tile::Plan tp;
+  return dct::tile::make_plan(&tp, dims, L) ? 1 : 0;
+}
+
+// floats of the slot workspace for batches up to B: [ceil(B / R)][Pp] slots + the fold's arrival counter
+long long dct_mlp_tile_ws_floats(const int* dims, int L, int B) {
+  dct::tile::Plan tp;
+  if (!dct::tile::make_plan(&tp, dims, L) || B < 1 || B > dct::tile::BMAX) return 0;
+  const long long T = (B + dct::tile::R - 1) / dct::tile::R;
+  return T * tp.Pp + 4;
+}
+
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream) {
+  dct::tile::Plan tp;
+  if (!dct::tile::make_plan(&tp, dims, L)) return (int)hipErrorInvalidValue;
+  if (a->B < 1 || a->B > dct::tile::BMAX || a->steps < 1 || a->n_items < 1) return (int)hipErrorInvalidValue;
+  if (a->mode == 1 && a->steps != 1) return (int)hipErrorInvalidValue;
+  if (!a->cursor && (long long)(a->steps - 1) * a->B >= a->n_items) return (int)hipErrorInvalidValue;
+  if (a->xg_world > 1 || a->pending) return (int)hipErrorInvalidValue;
+  if (!a->tile_ws || a->tile_ws_floats < dct_mlp_tile_ws_floats(dims, L, a->B)) return (int)hipErrorInvalidValue;
+  unsigned int* done = reinterpret_cast<unsigned int*>(a->tile_ws + (a->tile_ws_floats - 4));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return (int)(L == 2 ? dct::tile::launch_steps<2>(tp, *a, done, st) : dct::tile::launch_steps<3>(tp, *a, done, st));
+}
+
+}  // extern "C"

@@ -25,14 +25,77 @@ def mlp_num_params(dims: Sequence[int]) -> int:
     return sum(dims[i] * dims[i + 1] + dims[i + 1] for i in range(len(dims) - 1))
 
 
+TILE_BMAX = 1024  # largest per-rank batch of the batch-tiled trainer (csrc/mlp_tile.hip)
+
+
+def tile_supported(dims: Sequence[int]) -> bool:
+    """Host-side mirror of the batch-tiled trainer's shape check (csrc/mlp_tile.hip make_plan)."""
+    L = len(dims) - 1
+    if L not in (2, 3):
+        return False
+    if not (1 <= dims[0] <= 32 and 2 <= dims[-1] <= 4):
+        return False
+    return all(16 <= h <= 128 and h % 16 == 0 for h in dims[1:-1])
+
+
+def _mix_hash(a, b, c):
+    """csrc/mlp_fused_impl.h mix_hash on numpy uint32 arrays (wrapping arithmetic)."""
+    import numpy as np
+
+    u = np.uint32
+    with np.errstate(over="ignore"):
+        h = a * u(0x9E3779B1)
+        h = h ^ ((b + u(0x7F4A7C15)) * u(0x85EBCA77))
+        h = h ^ ((c + u(0x165667B1)) * u(0xC2B2AE3D))
+        h = h ^ (h >> u(16))
+        h = h * u(0x7FEB352D)
+        h = h ^ (h >> u(15))
+        h = h * u(0x846CA68B)
+        h = h ^ (h >> u(16))
+    return h
+
+
+def dropout_keep_mask(seed: int, gstep: int, layer: int, n_rows: int, n_units: int, p: float) -> torch.Tensor:
+    """Host mirror of the fused kernels' dropout mask: bool [n_rows, n_units], True = kept.
+
+    Keyed by (seed, global step, hidden layer, row within the batch, unit) with the kernels' own
+    integer arithmetic: ``mix_hash(seed + (b >> 6) * 0x9E3779B9, gstep, (layer * 64 + (b & 63)) * 65536 + o)``
+    and ``u01(h) < p`` means dropped.  Rows < 64 are the key of every fused trainer; the batch-tiled
+    trainer folds ``b >> 6`` into the hash's first argument for the rows above."""
+    import numpy as np
+
+    u = np.uint32
+    b = np.arange(n_rows, dtype=np.uint32)[:, None]
+    o = np.arange(n_units, dtype=np.uint32)[None, :]
+    with np.errstate(over="ignore"):
+        a = u(int(seed) & 0xFFFFFFFF) + (b >> u(6)) * u(0x9E3779B9)
+        key = (u(int(layer)) * u(64) + (b & u(63))) * u(65536) + o
+        h = _mix_hash(a, np.broadcast_to(u(int(gstep) & 0xFFFFFFFF), key.shape), key)
+    u01 = (h >> u(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    return torch.from_numpy(~(u01 < np.float32(p)))
+
+
 class FusedMLPKernel:
     def __init__(self, dims: Sequence[int], bmax: int):
-        if bmax not in (4, 16):
-            raise ValueError("fused MLP kernel is instantiated for batch <= 4 or <= 16")
+        if bmax not in (4, 16, TILE_BMAX):
+            raise ValueError("fused MLP kernel is instantiated for batch <= 4, <= 16 or <= 1024")
         self.dims = [int(d) for d in dims]
+        if bmax == TILE_BMAX and not tile_supported(self.dims):
+            raise ValueError("the batch-tiled trainer (batch 17..1024) does not take this architecture")
         self.bmax = bmax
         self._plan = None
         self._eval_plan = None
+        self._tile_ws = None  # slot workspace of the batch-tiled trainer (csrc/mlp_tile.hip)
+
+    def _tile_args(self, device) -> dict:
+        """The batch-tiled trainer's slot workspace (partial gradients per tile + the fold's arrival
+        counter, zero between launches), allocated once for batches up to ``bmax``."""
+        if not self.plan.use_tile:
+            return {}
+        if self._tile_ws is None or self._tile_ws.device != device:
+            n = int(native().mlp_tile_ws_floats(self.dims, max(self.bmax, 16)))
+            self._tile_ws = torch.zeros(n, dtype=torch.float32, device=device)
+        return dict(tile_ws=ptr(self._tile_ws), tile_ws_floats=self._tile_ws.numel())
 
     @property
     def plan(self):
@@ -42,7 +105,7 @@ class FusedMLPKernel:
 
     def fused_update_supported(self, batch: int) -> bool:
         """True if the update-then-grad DDP step (one kernel per step) is available."""
-        return bool(self.plan.use_wave) and batch <= 8
+        return bool(self.plan.use_wave) and not self.plan.use_tile and batch <= 8
 
     @property
     def eval_plan(self):
@@ -54,7 +117,9 @@ class FusedMLPKernel:
     def supported(dims: Sequence[int], batch: int) -> bool:
         """Host-side mirror of dct::mlp_make_shape's plan (no GPU needed)."""
         L = len(dims) - 1
-        if not (2 <= L <= 4) or batch > 16 or batch < 1:
+        if batch > 16:  # the batch-tiled trainer (csrc/mlp_tile.hip)
+            return batch <= TILE_BMAX and tile_supported(dims)
+        if not (2 <= L <= 4) or batch < 1:
             return False
         bmax = 4 if batch <= 4 else 16
         r4 = lambda x: (x + 3) // 4 * 4  # noqa: E731
@@ -149,7 +214,7 @@ class FusedMLPKernel:
             ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending),
             ptr(stage) if (stage is not None and (self.plan.use_wave or mode == 1)) else 0,
             stream if stream is not None else stream_handle(),
-            **xg_args,
+            **xg_args, **self._tile_args(p.device),
         )
 
     def prepare_train(self, p, m, v, X, Y, idx, n_items: int, batch: int, lr: float, betas=(0.9, 0.999),
@@ -190,8 +255,9 @@ class FusedMLPKernel:
             ptr(p), ptr(m), ptr(v), ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), int(batch), float(lr),
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, ptr(loss_out), 0 if loss_out is None else loss_out.numel(), LOSS_KINDS[loss],
-            ptr(step_counter), **xg_args)
-        return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks), p.device.index or 0)
+            ptr(step_counter), **xg_args, **self._tile_args(p.device))
+        return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws),
+                          p.device.index or 0)
 
     # ------------------------------------------------------------ in-kernel all-reduce
     def xg_slab_granules(self) -> int:
@@ -202,7 +268,9 @@ class FusedMLPKernel:
         """True when training launches can average gradients INSIDE the kernel: the single-wave
         kernel's 2-layer nets (any 2..8 ranks), or the 3x128 block kernel (csrc/mlp_block5.hip:
         reduce-scatter + all-gather with sharded Adam or the one-hop exchange, 2 .. 8 ranks; ``world=None`` asks whether
-        some world size qualifies)."""
+        some world size qualifies).  Never with the batch-tiled trainer (batch > 16)."""
+        if batch > 16 or self.plan.use_tile:
+            return False
         if len(self.dims) == 3 and self.plan.use_wave and self.xg_slab_granules() > 0:
             return 1 <= batch <= min(self.bmax, 8)
         return self._block5_bytes(batch, world if world is not None else 2) > 0

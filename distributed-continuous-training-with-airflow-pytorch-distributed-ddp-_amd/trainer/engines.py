@@ -100,7 +100,7 @@ class FusedMLPEngine(_EngineBase):
         self.dropout = float(spec["dropout"])
         self.loss = spec["loss"]
         self.adam = adam
-        self.kernel = FusedMLPKernel(self.dims, bmax=4 if self.B <= 4 else 16)
+        self.kernel = FusedMLPKernel(self.dims, bmax=4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
         self.P = mlp_num_params(self.dims)
         dev = ctx.device
         self.device = dev

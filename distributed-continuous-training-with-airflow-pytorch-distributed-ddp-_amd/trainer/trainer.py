@@ -225,7 +225,10 @@ class Trainer:
         if choice == "auto":
             choice = os.environ.get("DCT_ENGINE", "auto")
         adam = adam_hparams_from(model.configure_optimizers())
-        if choice in ("auto", "fused") and adam is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size):
+        fused_ok = adam is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size)
+        if choice == "auto" and fused_ok and batch_size > 16 and GraphMLPEngine.applicable(model, ctx.device, batch_size):
+            fused_ok = False  # batch > 16: the graph engine keeps the models it takes; the batch-tiled trainer the rest
+        if choice in ("auto", "fused") and fused_ok:
             return FusedMLPEngine(model, ctx, batch_size, seed, adam, steps_per_launch=self.steps_per_launch)
         if choice == "fused":
             raise RuntimeError("engine='fused' requested but the model/device/batch is not supported by it")
