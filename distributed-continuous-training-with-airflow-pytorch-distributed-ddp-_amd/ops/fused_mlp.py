@@ -75,6 +75,49 @@ def dropout_keep_mask(seed: int, gstep: int, layer: int, n_rows: int, n_units: i
     return torch.from_numpy(~(u01 < np.float32(p)))
 
 
+def _wave_hash(key):
+    """csrc/mlp_wave_impl.h wave_hash on numpy uint32 arrays (wrapping arithmetic)."""
+    import numpy as np
+
+    u = np.uint32
+    with np.errstate(over="ignore"):
+        key = key ^ (key >> u(16))
+        key = key * u(0x7FEB352D)
+        key = key ^ (key >> u(15))
+        key = key * u(0x846CA68B)
+        key = key ^ (key >> u(16))
+    return key
+
+
+def wave_dropout_keep_mask(seed: int, gstep: int, layer: int, n_rows: int, n_units: int, p: float) -> torch.Tensor:
+    """Host mirror of the wave kernels' dropout mask (csrc/mlp_wave_impl.h: the single-wave kernel and
+    the row-parallel kernels): bool [n_rows, n_units], True = kept.
+
+    ``hkey = (seed * 0x9E3779B1) ^ (gstep * 0x85EBCA77)``, unit ``j`` of row ``b`` in hidden layer
+    ``layer`` draws ``wave_hash(hkey ^ ((layer * 4096 + b * 64 + j) * 0xC2B2AE3D))`` and is dropped when
+    the draw is below ``(uint32)(p * 2^32)`` with ``p`` the fp32 dropout rate, all in uint32 arithmetic."""
+    import numpy as np
+
+    u = np.uint32
+    b = np.arange(n_rows, dtype=np.uint32)[:, None]
+    j = np.arange(n_units, dtype=np.uint32)[None, :]
+    with np.errstate(over="ignore"):
+        hkey = (u(int(seed) & 0xFFFFFFFF) * u(0x9E3779B1)) ^ (u(int(gstep) & 0xFFFFFFFF) * u(0x85EBCA77))
+        r = _wave_hash(hkey ^ ((u(int(layer)) * u(4096) + b * u(64) + j) * u(0xC2B2AE3D)))
+    thr = int(float(np.float32(p)) * 4294967296.0)  # < 2^32 for every fp32 p < 1
+    return torch.from_numpy(~(r.astype(np.uint64) < np.uint64(thr)))
+
+
+def wave_supported(dims: Sequence[int], batch: int) -> bool:
+    """Host-side mirror of the wave kernels' shape / batch check (csrc/mlp_wave.hip)."""
+    L = len(dims) - 1
+    if L not in (2, 3):
+        return False
+    if dims[0] > 16 or dims[-1] > 4 or not 1 <= batch <= 8:
+        return False
+    return all(h <= 64 for h in dims[1:-1])
+
+
 class FusedMLPKernel:
     def __init__(self, dims: Sequence[int], bmax: int):
         if bmax not in (4, 16, TILE_BMAX):
@@ -106,6 +149,19 @@ class FusedMLPKernel:
     def fused_update_supported(self, batch: int) -> bool:
         """True if the update-then-grad DDP step (one kernel per step) is available."""
         return bool(self.plan.use_wave) and not self.plan.use_tile and batch <= 8
+
+    def dropout_mask(self, seed: int, gstep: int, layer: int, batch: int, p: float) -> torch.Tensor:
+        """Host mirror of the mask a training launch of this plan draws for hidden layer ``layer`` at
+        global step ``gstep``: bool [batch, dims[layer + 1]], True = kept.  The hash family follows the
+        launcher's own rule (csrc/bindings.cpp launch_train): the wave kernels' when the plan is a wave
+        plan and the wave kernels take this batch, ``dropout_keep_mask`` for every other trainer."""
+        if not 0 <= layer < len(self.dims) - 2:
+            raise ValueError(f"hidden layer {layer} outside 0..{len(self.dims) - 3}")
+        if not 1 <= batch <= self.bmax:
+            raise ValueError(f"batch {batch} outside 1..{self.bmax}")
+        wave = bool(self.plan.use_wave) and not self.plan.use_tile and wave_supported(self.dims, batch)
+        mirror = wave_dropout_keep_mask if wave else dropout_keep_mask
+        return mirror(seed, gstep, layer, batch, self.dims[layer + 1], p)
 
     @property
     def eval_plan(self):
