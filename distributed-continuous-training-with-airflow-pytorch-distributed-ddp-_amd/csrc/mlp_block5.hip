@@ -56,9 +56,9 @@ static void b5_launch_sched(int sched, size_t bytes, hipStream_t st, const MlpSh
 #ifdef B5_SCHED_AB
   if constexpr (!WD && LK == 0 && !PROF) {
     constexpr int D = SCHED_DEFAULT;
-    constexpr int NWT = D & ~(SCH_WT1 | SCH_WT2);  // the default without hoisted transposes
-    constexpr int masks[] = {SCH_DROP, SCH_ADAM_TAB, SCH_WT1, SCH_WT2, SCH_WT1 | SCH_WT2, NWT, NWT | SCH_WT2,
-                             NWT | SCH_WT1 | SCH_WT2, D & ~SCH_DROP, D & ~SCH_ADAM_TAB};
+    constexpr int NWT = SCH_DROP | SCH_ADAM_TAB;  // the default without hoisted transposes
+    constexpr int masks[] = {SCH_DROP, SCH_ADAM_TAB, SCH_WT1, SCH_WTB, NWT, NWT | SCH_WT1, NWT | SCH_WT1 | SCH_WTB,
+                             NWT | SCH_WT2 | SCH_WTB, D & ~SCH_DROP, D & ~SCH_ADAM_TAB};
     bool done = false;
     b5x::static_for<sizeof(masks) / sizeof(masks[0])>([&](auto i) {
       constexpr int M = masks[decltype(i)::value];

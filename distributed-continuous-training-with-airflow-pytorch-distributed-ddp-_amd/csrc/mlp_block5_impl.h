@@ -69,11 +69,17 @@ constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 //               steps, one readlane each per step (instead of 2 exp, 2 rcp, 1 rsq + ~8 VALU per step)
 //   WT1 * n     dZ1's quad transposes of the first n = 0..3 W1 k-blocks (8 MFMAs, 8 registers each): in the
 //               window (SCH_WT2 = 2 blocks, SCH_WT1 | SCH_WT2 = 3)
+//   WTB         the next k-block's transposes (block n) right behind barrier B, under the loss: there every
+//               wave runs one dependent chain (LDS read, cross-lane adds, exp, rcp) and the matrix pipe
+//               is idle.  Faster without a block in the A -> B window than beside one.
 // Measured and not kept (profiles/b5_sched_ab_r7.log): the next input tile read before the dW1 pass
 // (alone +1.2 %), W1 Adam beside the dW1 MFMAs as scalar fmas instead of packed (+10 %), two or three
-// hoisted transpose blocks with the other items (slower than one).
-constexpr int SCH_DROP = 1, SCH_ADAM_TAB = 2, SCH_WT1 = 8, SCH_WT2 = 16;
-constexpr int SCHED_DEFAULT = SCH_DROP | SCH_ADAM_TAB | SCH_WT1;
+// hoisted transpose blocks with the other items (slower than one).  profiles/b5_dw1z_ab_r9.log: dW1's
+// MFMAs and the W1 Adam of k-block q inside dZ1's loop, in the hazard gaps of its dependent MFMA
+// chains (100 -> 41 s_nop per step, +5.5 .. +8.7 %: a padded wave yields its issue slots to its SIMD
+// partner, a filled one does not); two or three blocks behind barrier B (slower than one).
+constexpr int SCH_DROP = 1, SCH_ADAM_TAB = 2, SCH_WT1 = 8, SCH_WT2 = 16, SCH_WTB = 32;
+constexpr int SCHED_DEFAULT = SCH_DROP | SCH_ADAM_TAB | SCH_WTB;
 }  // namespace blk5
 
 // ---- data parallelism inside the persistent launch (XW = 2 / 4 / 8 ranks, one per GPU) ---------
@@ -263,6 +269,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   static_assert(SCH == 0 || (XW == 1 && MB == 1 && ADAM), "step-schedule items: one-rank train mode, one micro-batch");
   constexpr bool S_DROP = (SCH & SCH_DROP) != 0, S_TAB = (SCH & SCH_ADAM_TAB) != 0;
   constexpr int HQ = DXM ? (SCH / SCH_WT1) & 3 : 0;  // hoisted W1 transpose blocks
+  constexpr int HB = DXM ? (SCH / SCH_WTB) & 1 : 0;  // ... and the next one, behind barrier B
+  static_assert(HQ + HB <= KS / 4, "W1 has four k-blocks per wave");
   using LY = Lds<MB>;
   constexpr int RB = LY::RB, XT = LY::XT, LAB = LY::LAB, MSK = LY::MSK, LOGP = LY::LOGP, H1W = LY::H1W;
   constexpr int H1X = LY::H1X, PART = LY::PART, W2L = LY::W2L, B2L = LY::B2L, ABT = LY::ABT, TOTAL = LY::TOTAL;
@@ -546,7 +554,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     float gw0s = 0.f, gw1s = 0.f, gb1s = 0.f, gbs = 0.f, g0s = 0.f, g1s = 0.f, db0s = 0.f;
     float aA = 0.f, aE = 0.f;
     float f1n = 0.f, f2n = 0.f;           // SCH_DROP: next step's dropout factors (from the A -> B window)
-    f32x4_t wth[HQ > 0 ? HQ : 1][2];     // SCH_WT*: transposed W1 quads of k-blocks q < HQ
+    f32x4_t wth[HQ + HB > 0 ? HQ + HB : 1][2];  // SCH_WT*: transposed W1 quads of k-blocks q < HQ + HB
     v2f GO[NO];  // XW > 1 (reduce-scatter): gradients of the W1 pairs this rank owns
 #pragma unroll
     for (int t2 = 0; t2 < NO; ++t2) GO[t2] = (v2f){0.f, 0.f};
@@ -738,9 +746,24 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       // ---- loss: lane (share l / 8, class cb, row r0) -> logit (r0, cb) of the micro-batch
       const uint2 mw0 = *reinterpret_cast<const uint2*>(lds + MSK + mpar * (NW * 2) + 2 * (l >> 4));
       const uint2 mw1 = *reinterpret_cast<const uint2*>(lds + MSK + mpar * (NW * 2) + 2 * ((l >> 4) + 4));
+      float lg0 = 0.f;
+      if constexpr (HB > 0) {
+        // SCH_WTB: the loss below is one dependent chain (LDS read, cross-lane adds, exp, rcp) in every
+        // wave at once; the matrix pipe is idle under it
+        lg0 = lds[LOGP + mpar * (NW * 8) + l];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int qq = HQ; qq < HQ + HB; ++qq)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const float wq[4] = {W[j][2 * qq].x, W[j][2 * qq].y, W[j][2 * qq + 1].x, W[j][2 * qq + 1].y};
+            wth[qq][j] = quad_transpose_mf(wq, eye);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      }
       float lv;
       {
-        float lg = lds[LOGP + mpar * (NW * 8) + l];
+        float lg = HB > 0 ? lg0 : lds[LOGP + mpar * (NW * 8) + l];
         lg += dpp<ROR8>(lg);          // shares w', w' ^ 1 (lane bit 3)
         lg = swap16_sum(lg, lg);      // lane bit 4
         lg = swap32_sum(lg, lg);      // lane bit 5
@@ -883,7 +906,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             const float wq[4] = {W[j][2 * q].x, W[j][2 * q].y, W[j][2 * q + 1].x, W[j][2 * q + 1].y};
-            const f32x4_t wt = q < HQ ? wth[q < HQ ? q : 0][j] : quad_transpose_mf(wq, eye);
+            const f32x4_t wt = q < HQ + HB ? wth[q < HQ + HB ? q : 0][j] : quad_transpose_mf(wq, eye);
             acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[j] = mfma4(wt[i], dzt[j][i], acc[j]);
