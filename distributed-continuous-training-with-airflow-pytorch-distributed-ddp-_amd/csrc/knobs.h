@@ -16,8 +16,9 @@ struct Knobs {
                             // MLP_BLOCK_TILE ("tile") the batch-tiled trainer (mlp_tile.hip) at batch <= 16 too
   int b5_sched = -1;        // DCT_B5_SCHED: mlp_block5's one-rank batch <= 4 train kernels: -1 the default step
                             // schedule (blk5::SCHED_DEFAULT), 0 the previous one (the reference of the bit-for-bit
-                            // test and of same-binary A/Bs), 1 the default one; 256 + mask: one of the item
-                            // masks an A/B build (-DB5_SCHED_AB) carries, the default schedule elsewhere
+                            // test and of same-binary A/Bs), 1 the default one; B5_SCHED_AB_BASE + mask: one of
+                            // the item masks an A/B build (-DB5_SCHED_AB) carries, the default schedule elsewhere
+                            // (round 10's candidate masks outgrew the earlier 256 + mask)
   // wide-MLP step executor (mlp_executor.cpp; copied into each executor at construction)
   int fused_head = 1;       // DCT_FUSED_HEAD=0: the four-kernel head chain
   int dw_into_adam = 1;     // DCT_DW_INTO_ADAM=0: dW through g and the reduce pass
@@ -34,6 +35,7 @@ struct Knobs {
 };
 
 constexpr int MLP_BLOCK_TILE = 32;
+constexpr int B5_SCHED_AB_BASE = 4096;  // DCT_B5_SCHED of an A/B build: B5_SCHED_AB_BASE + item mask (< 4096)
 
 const Knobs& knobs();
 void knobs_reload();

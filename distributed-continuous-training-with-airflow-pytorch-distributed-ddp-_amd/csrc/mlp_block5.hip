@@ -47,8 +47,9 @@ size_t mlp_block5_xg_bytes(int world) {
 }
 
 // one-rank batch <= 4 train launch under the step schedule DCT_B5_SCHED selects (knobs.h): 0 the
-// previous schedule, anything else the default one.  An A/B build (-DB5_SCHED_AB) also carries the
-// single-item and leave-one-out masks of the headline variant (CE, no weight decay): 256 + mask.
+// previous schedule, anything else the default one.  An A/B build (-DB5_SCHED_AB) also carries, for the
+// headline variant (CE, no weight decay), the default without the phase priorities (round 9's) and the
+// priorities alone: B5_SCHED_AB_BASE + mask.  A round's candidate items go into this list.
 template <bool WD, int LK, bool PROF = false>
 static void b5_launch_sched(int sched, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
   using namespace blk5;
@@ -56,13 +57,11 @@ static void b5_launch_sched(int sched, size_t bytes, hipStream_t st, const MlpSh
 #ifdef B5_SCHED_AB
   if constexpr (!WD && LK == 0 && !PROF) {
     constexpr int D = SCHED_DEFAULT;
-    constexpr int NWT = SCH_DROP | SCH_ADAM_TAB;  // the default without hoisted transposes
-    constexpr int masks[] = {SCH_DROP, SCH_ADAM_TAB, SCH_WT1, SCH_WTB, NWT, NWT | SCH_WT1, NWT | SCH_WT1 | SCH_WTB,
-                             NWT | SCH_WT2 | SCH_WTB, D & ~SCH_DROP, D & ~SCH_ADAM_TAB};
+    constexpr int masks[] = {D & ~SCH_PRIO_LAT, SCH_PRIO_LAT};
     bool done = false;
     b5x::static_for<sizeof(masks) / sizeof(masks[0])>([&](auto i) {
       constexpr int M = masks[decltype(i)::value];
-      if (!done && sched == 256 + M && M != D) {
+      if (!done && sched == B5_SCHED_AB_BASE + M && M != D) {
         b5_launch<WD, LK, false, true, true, 1, -1, 1, M>(bytes, st, sh, a);
         done = true;
       }

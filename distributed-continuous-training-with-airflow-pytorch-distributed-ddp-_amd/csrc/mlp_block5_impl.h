@@ -72,14 +72,25 @@ constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 //   WTB         the next k-block's transposes (block n) right behind barrier B, under the loss: there every
 //               wave runs one dependent chain (LDS read, cross-lane adds, exp, rcp) and the matrix pipe
 //               is idle.  Faster without a block in the A -> B window than beside one.
+//   PRIO_LAT    wave priority per phase: s_setprio 1 over the short dependency-bound phases (h2 + logit
+//               share, the loss, dZ2 + the W2 / b1 / b2 owners up to dZ1's first k-block, the dW0 / db0
+//               tail), 0 over F1 / F2, the rest of dZ1's MFMA chains + its reduce-scatter and dW1 + Adam.
+//               With both waves of a SIMD at priority 0 the younger one queues in those few dozen
+//               instructions (v_sqrt / v_rcp / DPP / readlane chains) behind its partner's dense dZ1 /
+//               dW1 + Adam stream, and the partner then waits for it at barrier A.
 // Measured and not kept (profiles/b5_sched_ab_r7.log): the next input tile read before the dW1 pass
 // (alone +1.2 %), W1 Adam beside the dW1 MFMAs as scalar fmas instead of packed (+10 %), two or three
 // hoisted transpose blocks with the other items (slower than one).  profiles/b5_dw1z_ab_r9.log: dW1's
 // MFMAs and the W1 Adam of k-block q inside dZ1's loop, in the hazard gaps of its dependent MFMA
 // chains (100 -> 41 s_nop per step, +5.5 .. +8.7 %: a padded wave yields its issue slots to its SIMD
 // partner, a filled one does not); two or three blocks behind barrier B (slower than one).
+// profiles/b5_prio_defer_ab_r10.log: the backward one level above F1 / F2 (alone
+// -1.7 %, nothing on top of PRIO_LAT), the owners' Adam deferred into the next step in front of barrier A
+// (+4.2 %), PRIO_LAT over dZ1's reduce-scatter too, without the A -> B window, without the dW0 / db0 tail,
+// without the owners, or one level higher in waves 4..7 (all slower than PRIO_LAT as it is).
 constexpr int SCH_DROP = 1, SCH_ADAM_TAB = 2, SCH_WT1 = 8, SCH_WT2 = 16, SCH_WTB = 32;
-constexpr int SCHED_DEFAULT = SCH_DROP | SCH_ADAM_TAB | SCH_WTB;
+constexpr int SCH_PRIO_LAT = 64;
+constexpr int SCHED_DEFAULT = SCH_DROP | SCH_ADAM_TAB | SCH_WTB | SCH_PRIO_LAT;
 }  // namespace blk5
 
 // ---- data parallelism inside the persistent launch (XW = 2 / 4 / 8 ranks, one per GPU) ---------
@@ -166,6 +177,15 @@ __device__ __host__ __forceinline__ void static_for(F&& f) {
     const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
     pacc[(k)] += t_ - t_last;                                   \
     t_last = t_;                                                \
+  }
+
+// SCH_PRIO_LAT: the wave's priority from here on; pinned, or the scheduler moves the neighbouring phases'
+// instructions across it
+#define B5PRIO(p)                      \
+  if constexpr (S_PLAT) {              \
+    __builtin_amdgcn_sched_barrier(0); \
+    __builtin_amdgcn_s_setprio(p);     \
+    __builtin_amdgcn_sched_barrier(0); \
   }
 
 // dropout factor of element (layer li, row r, unit u) at global step gstep: 0 or 1 / (1 - p).  Same
@@ -271,6 +291,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   constexpr int HQ = DXM ? (SCH / SCH_WT1) & 3 : 0;  // hoisted W1 transpose blocks
   constexpr int HB = DXM ? (SCH / SCH_WTB) & 1 : 0;  // ... and the next one, behind barrier B
   static_assert(HQ + HB <= KS / 4, "W1 has four k-blocks per wave");
+  constexpr bool S_PLAT = (SCH & SCH_PRIO_LAT) != 0;
   using LY = Lds<MB>;
   constexpr int RB = LY::RB, XT = LY::XT, LAB = LY::LAB, MSK = LY::MSK, LOGP = LY::LOGP, H1W = LY::H1W;
   constexpr int H1X = LY::H1X, PART = LY::PART, W2L = LY::W2L, B2L = LY::B2L, ABT = LY::ABT, TOTAL = LY::TOTAL;
@@ -672,6 +693,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       B5STAMP(1)
       lds_barrier();  // A: all partials of this step are in (and W2 / b2 of the previous publish)
       B5STAMP(2)
+      B5PRIO(1)  // h2 + logit share, the loss, dZ2 + owners, dZ1's first k-block
       if constexpr (XW > 1) {
         // a wave's exchange of the previous step timed out (flag written before this barrier):
         // the whole workgroup leaves together, the epilogue writes nothing back
@@ -902,6 +924,9 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         float P[16];
 #pragma unroll
         for (int q = 0; q < KS / 4; ++q) {
+          // (behind the block whose W1 transposes were hoisted: dropped between the owners and dZ1, the
+          // headline kernel needs 12 registers more and spills 7)
+          if (q == 1) B5PRIO(0)
           f32x4_t acc[2];  // one chain per j (4 dependent MFMAs each)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
@@ -929,6 +954,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         }
       }
       dz1 = h1 > 0.f ? dz1 * scale : 0.f;
+      B5PRIO(1)
       // ---- dW0 / db0 (the quad holds unit u's four rows; inputs from the F1 tile in registers)
       {
         const float dq0 = dpp<QB0>(dz1), dq1 = dpp<QB1>(dz1), dq2 = dpp<QB2>(dz1), dq3 = dpp<QB3>(dz1);
@@ -968,6 +994,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     if constexpr (XW > 1) {
       if (abort_step) break;
     }
+    B5PRIO(0)
     // next step's dropout factors (independent work for the Adam stream below)
     if constexpr (S_DROP) {
       f1[0] = f1n;
@@ -1272,6 +1299,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   }
 }
 #undef B5STAMP
+#undef B5PRIO
 
 // one launch of an instantiation; its dynamic-LDS limit (two 64-KB staging tiles) is raised once
 template <bool WD, int LK, bool PROF = false, bool DXM = true, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1,
