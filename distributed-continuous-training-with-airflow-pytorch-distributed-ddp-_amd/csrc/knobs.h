@@ -18,7 +18,8 @@ struct Knobs {
                             // schedule (blk5::SCHED_DEFAULT), 0 the previous one (the reference of the bit-for-bit
                             // test and of same-binary A/Bs), 1 the default one; B5_SCHED_AB_BASE + mask: one of
                             // the item masks an A/B build (-DB5_SCHED_AB) carries, the default schedule elsewhere
-                            // (round 10's candidate masks outgrew the earlier 256 + mask)
+                            // (round 10's candidate masks outgrew the earlier 256 + mask; round 11's items are the
+                            // bits 128 .. 2048, so the default mask is 4067 and every mask stays below 4096)
   // wide-MLP step executor (mlp_executor.cpp; copied into each executor at construction)
   int fused_head = 1;       // DCT_FUSED_HEAD=0: the four-kernel head chain
   int dw_into_adam = 1;     // DCT_DW_INTO_ADAM=0: dW through g and the reduce pass

@@ -49,6 +49,11 @@ struct Lds {
   static constexpr int B2L = W2L + 2 * H * C;              // [2][4] b2
   static constexpr int ABT = B2L + 8;                      // [4] data-parallel launches: a wave's exchange timed out
   static constexpr int TOTAL = ABT + 4;
+  // SCH_DZ2F: [2][H][4] h2 > 0 ? scale : 0 of (output o, row).  Behind TOTAL: the layout and the zeroing
+  // loop of the other kernels stay as they are (every word is written before barrier B, read behind it)
+  static constexpr int DZF = TOTAL;
+  static constexpr int TOTAL_DZF = DZF + 2 * H * 4;
+  static_assert((DZF % 4) == 0, "16-B aligned");
   static_assert((H1W % 4) == 0 && (PART % 4) == 0 && (MSK % 4) == 0 && (LAB % 4) == 0 && (W2L % 4) == 0 &&
                     (B2L % 4) == 0 && (H1X % 4) == 0 && (LOGP % 4) == 0,
                 "16-B aligned tiles");
@@ -56,6 +61,7 @@ struct Lds {
 static_assert(Lds<1>::TOTAL == 11036, "the batch <= 4 layout is round 5's");
 constexpr int STG = H * H;
 constexpr int LDS_FLOATS = Lds<MBMAX>::TOTAL > 2 * STG ? Lds<MBMAX>::TOTAL : 2 * STG;  // two staging tiles (prologue/epilogue)
+static_assert(Lds<1>::TOTAL_DZF <= LDS_FLOATS, "SCH_DZ2F's region inside the launch's LDS");
 static_assert(LDS_FLOATS * 4 <= 160 * 1024, "fits the CU");
 using Stg = bku::Stage<H, NT>;
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
@@ -90,7 +96,28 @@ constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 // without the owners, or one level higher in waves 4..7 (all slower than PRIO_LAT as it is).
 constexpr int SCH_DROP = 1, SCH_ADAM_TAB = 2, SCH_WT1 = 8, SCH_WT2 = 16, SCH_WTB = 32;
 constexpr int SCH_PRIO_LAT = 64;
-constexpr int SCHED_DEFAULT = SCH_DROP | SCH_ADAM_TAB | SCH_WTB | SCH_PRIO_LAT;
+// Round 11: vector instructions the result does not need, out of the loop (both waves of a SIMD pay for
+// each other's issue).  Same operations in the same order on every value, so still bit for bit SCH = 0.
+//   PF_W0       the next batch's gather (index, x / label word and their address arithmetic) only in wave 0,
+//               behind a scalar branch: at one micro-batch only threads 0 .. B * D0 + B - 1 <= 35 have a
+//               prefetch role, yet all eight waves issued the loads and waited for them behind barrier A;
+//               the row offset as one 32 x 32 -> 64-bit multiply-add (indices and strides are not negative)
+//   ADAM_SM     the two small Adam pairs (W2-own + b1, the two W0 slices) held as 64-bit pairs and updated
+//               in place by adam_v2 like W1 (as scalar fmacs their moments landed in the gradient's register
+//               and went back through v_mov at the loop's back edge); the step's E in one VGPR for the
+//               small updates instead of a v_mov from its SGPR in front of each v_fma
+//   DZ2F        dZ2's ReLU / dropout factor (h2 > 0 ? scale : 0) published as floats [o][row] by the owning
+//               wave instead of a ballot whose nibbles every consumer takes apart: one float4 read per
+//               output and one multiply per value.  A masked value is g * 0 = +-0 instead of +0; dZ2 is only
+//               an MFMA operand into accumulators that start at +0, where x * +-0 + (+0) = +0 either way
+//   DROP_INT    dropout keep test on integers: u01(h) < p <=> (h >> 8) < ceil(p * 2^24), the threshold
+//               once per launch (h >> 8 < 2^24 converts exactly and 2^-24 scales exactly)
+//   DB2         db2 of class l & 1 as quad_sum(dz) - (d0 + d1) + (d2 + d3) of class cb in every lane, the
+//               same association - and one row rotation, instead of two exec-masked blocks of readlane sums
+constexpr int SCH_PF_W0 = 128, SCH_ADAM_SM = 256, SCH_DZ2F = 512, SCH_DROP_INT = 1024, SCH_DB2 = 2048;
+constexpr int SCHED_R10 = SCH_DROP | SCH_ADAM_TAB | SCH_WTB | SCH_PRIO_LAT;  // round 10's default
+constexpr int SCHED_DEFAULT = SCHED_R10 | SCH_PF_W0 | SCH_ADAM_SM | SCH_DZ2F | SCH_DROP_INT | SCH_DB2;
+static_assert(SCHED_DEFAULT < 4096, "item masks stay below B5_SCHED_AB_BASE (knobs.h)");
 }  // namespace blk5
 
 // ---- data parallelism inside the persistent launch (XW = 2 / 4 / 8 ranks, one per GPU) ---------
@@ -205,6 +232,19 @@ __device__ __forceinline__ float b5_drop(uint32_t seed, uint32_t gstep, uint32_t
   h ^= h >> 16;
   return u01(h) < p ? 0.f : scale;
 }
+// SCH_DROP_INT: the same keep test on integers.  u01(h) = (h >> 8) * 2^-24 is exact (24 bits, a power-of-
+// two scale), so u01(h) < p <=> (h >> 8) < p * 2^24 <=> (h >> 8) < ceil(p * 2^24) for the integer h >> 8
+__device__ __forceinline__ uint32_t b5_drop_thr(float p) { return (uint32_t)ceilf(p * 16777216.0f); }
+__device__ __forceinline__ float b5_drop_int(uint32_t seed, uint32_t gstep, uint32_t elem, uint32_t thr, float scale) {
+  uint32_t h = (seed * 0x9E3779B1u) ^ ((gstep + 0x7F4A7C15u) * 0x85EBCA77u);
+  h ^= elem;
+  h ^= h >> 16;
+  h *= 0x7feb352du;
+  h ^= h >> 15;
+  h *= 0x846ca68bu;
+  h ^= h >> 16;
+  return (h >> 8) < thr ? 0.f : scale;
+}
 
 // Adam (scaled moments, bku::adam_scaled) of two parameters sharing one reciprocal
 template <bool WD>
@@ -292,6 +332,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   constexpr int HB = DXM ? (SCH / SCH_WTB) & 1 : 0;  // ... and the next one, behind barrier B
   static_assert(HQ + HB <= KS / 4, "W1 has four k-blocks per wave");
   constexpr bool S_PLAT = (SCH & SCH_PRIO_LAT) != 0;
+  constexpr bool S_PF = (SCH & SCH_PF_W0) != 0, S_SM = (SCH & SCH_ADAM_SM) != 0, S_DZF = (SCH & SCH_DZ2F) != 0;
+  constexpr bool S_DINT = (SCH & SCH_DROP_INT) != 0, S_DB2 = (SCH & SCH_DB2) != 0;
   using LY = Lds<MB>;
   constexpr int RB = LY::RB, XT = LY::XT, LAB = LY::LAB, MSK = LY::MSK, LOGP = LY::LOGP, H1W = LY::H1W;
   constexpr int H1X = LY::H1X, PART = LY::PART, W2L = LY::W2L, B2L = LY::B2L, ABT = LY::ABT, TOTAL = LY::TOTAL;
@@ -460,6 +502,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   // re-materialised work with the MFMA chains), so XW = 1 keeps deriving them
   const float p_drop = a.dropout;
   const bool drop = p_drop > 0.f;
+  const uint32_t drop_thr = S_DINT ? b5_drop_thr(p_drop) : 0u;  // SCH_DROP_INT
   const float scale = XW > 1 ? a.k_drop_scale : (drop ? 1.0f / (1.0f - p_drop) : 1.0f);
   const float l2b1 = XW > 1 ? a.k_l2b1 : log2f(a.b1), l2b2 = XW > 1 ? a.k_l2b2 : log2f(a.b2);
   const float c1 = 1.f - a.b1, c2 = 1.f - a.b2;
@@ -485,6 +528,11 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       Mo[j][h] = (v2f){m1[j][2 * h], m1[j][2 * h + 1]};
       Vo[j][h] = (v2f){v1[j][2 * h], v1[j][2 * h + 1]};
     }
+  // SCH_ADAM_SM: the small Adam pairs in the same form (unpacked behind the loop): {W2[r0 & 1][u], b1[u]}
+  // - its .x is taken from pw2 every step - and the two W0 slices
+  const v2f z2 = (v2f){0.f, 0.f};
+  v2f PSm = S_SM ? (v2f){0.f, pb1} : z2, MSm = S_SM ? (v2f){mw2, mb1} : z2, VSm = S_SM ? (v2f){vw2, vb1} : z2;
+  v2f PW0 = S_SM ? (v2f){w0[0], w0[1]} : z2, MW0 = S_SM ? (v2f){m0[0], m0[1]} : z2, VW0 = S_SM ? (v2f){v0[0], v0[1]} : z2;
   // ---- XW > 1: the moments of the owned W1 pairs only (slot t = pair rank + XW t), the exchange's
   // buffer descriptors, this rank's small-pair ownership
   const int xrank = XW > 1 ? (RK >= 0 ? RK : a.xg_rank) : 0;
@@ -539,6 +587,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     f1[hf] = b5_drop(a.seed, step_base, el0[hf], p_drop, scale);
     f2[hf] = b5_drop(a.seed, step_base, el1[hf], p_drop, scale);
   }
+  // SCH_PF_W0: every prefetch role sits in wave 0 (B * D0 + B <= 36 threads); a scalar condition
+  const bool pf_wave = !S_PF || __builtin_amdgcn_readfirstlane(w) == 0;
   float* h1x = lds + H1X + w * (KS * 4);
   float eye[4];  // one-hot of lane % 4 (B operands of the MFMA quad transposes)
 #pragma unroll
@@ -561,9 +611,19 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     const float* xT = lds + XT + xb * DMAX * RB;
     const bool have_next = (s + 1 < a.steps);
     const int bs_next = have_next ? min(Bsz, a.n_items - (sb + 1) * Bsz) : 0;
-    const uint32_t raw_next = pf_base[(size_t)ridx_next * pf_stride];
-    const int nx2 = min((sb + 2) * Bsz + pb, a.n_items - 1);
-    const int ridx_next2 = a.idx[nx2 < 0 ? 0 : nx2];
+    uint32_t raw_next = 0u;
+    int ridx_next2 = 0;
+    if constexpr (S_PF) {
+      if (pf_wave) {  // wave-uniform: the other waves issue neither the loads nor their addresses
+        raw_next = pf_base[(size_t)(uint32_t)ridx_next * (uint32_t)pf_stride];
+        const int nx2 = min((sb + 2) * Bsz + pb, a.n_items - 1);
+        ridx_next2 = a.idx[nx2 < 0 ? 0 : nx2];
+      }
+    } else {
+      raw_next = pf_base[(size_t)ridx_next * pf_stride];
+      const int nx2 = min((sb + 2) * Bsz + pb, a.n_items - 1);
+      ridx_next2 = a.idx[nx2 < 0 ? 0 : nx2];
+    }
     const uint32_t xtag = gstep + 1u;  // XW > 1: this step's exchange tag and parity slab
     const int xpar = (int)(gstep & 1u);
     const int t = t0 + s + 1;
@@ -573,7 +633,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     float dz = 0.f, xbl = 0.f, tls = 0.f;  // last micro-batch's dlogit; XW > 1: batch loss; loss sum
     float h2 = 0.f, h1 = 0.f;
     float gw0s = 0.f, gw1s = 0.f, gb1s = 0.f, gbs = 0.f, g0s = 0.f, g1s = 0.f, db0s = 0.f;
-    float aA = 0.f, aE = 0.f;
+    float aA = 0.f, aE = 0.f, aEv = 0.f;
     float f1n = 0.f, f2n = 0.f;           // SCH_DROP: next step's dropout factors (from the A -> B window)
     f32x4_t wth[HQ + HB > 0 ? HQ + HB : 1][2];  // SCH_WT*: transposed W1 quads of k-blocks q < HQ + HB
     v2f GO[NO];  // XW > 1 (reduce-scatter): gradients of the W1 pairs this rank owns
@@ -638,8 +698,9 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       const float4 xa = *reinterpret_cast<const float4*>(xT + r0 * RB + B * hf);
       const float4 xc = *reinterpret_cast<const float4*>(xT + (r0 + 4) * RB + B * hf);
       {
-        const float acc0 = w0[0] * xa.x + w0[1] * xc.x, acc1 = w0[0] * xa.y + w0[1] * xc.y;
-        const float acc2 = w0[0] * xa.z + w0[1] * xc.z, acc3 = w0[0] * xa.w + w0[1] * xc.w;
+        const float wa = S_SM ? PW0.x : w0[0], wc = S_SM ? PW0.y : w0[1];
+        const float acc0 = wa * xa.x + wc * xc.x, acc1 = wa * xa.y + wc * xc.y;
+        const float acc2 = wa * xa.z + wc * xc.z, acc3 = wa * xa.w + wc * xc.w;
         const bool qb1 = (r0 >> 1) & 1, qb0 = r0 & 1;
         const float k0 = qb1 ? acc2 : acc0, k1 = qb1 ? acc3 : acc1;
         const float s0 = qb1 ? acc0 : acc2, s1 = qb1 ? acc1 : acc3;
@@ -682,13 +743,15 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
           if (tid == 0) a.stage[0] = bs_st > 0 ? (uint32_t)(sb + 2) : 0u;
         }
         // next batch into the next input buffer (its last readers finished before the previous barrier B)
-        if (role) {
-          const uint32_t v = (have_next && pb < bs_next) ? raw_next : 0u;
-          uint32_t* dst = (role == 1) ? reinterpret_cast<uint32_t*>(lds + XT + xbn * DMAX * RB) + pk * RB + pb
-                                      : reinterpret_cast<uint32_t*>(lds + LAB) + xbn * RB + pb;
-          *dst = v;
+        if (pf_wave) {  // (SCH_PF_W0: wave 0; otherwise constant true)
+          if (role) {
+            const uint32_t v = (have_next && pb < bs_next) ? raw_next : 0u;
+            uint32_t* dst = (role == 1) ? reinterpret_cast<uint32_t*>(lds + XT + xbn * DMAX * RB) + pk * RB + pb
+                                        : reinterpret_cast<uint32_t*>(lds + LAB) + xbn * RB + pb;
+            *dst = v;
+          }
+          ridx_next = role ? ridx_next2 : 0;
         }
-        ridx_next = role ? ridx_next2 : 0;
       }
       B5STAMP(1)
       lds_barrier();  // A: all partials of this step are in (and W2 / b2 of the previous publish)
@@ -733,8 +796,13 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             // front of barrier A, and code sinking moves values only used next step back to the loop end)
             uint32_t gnext = gstep + 1u;
             asm volatile("" : "+s"(gnext));
-            f1n = b5_drop(a.seed, gnext, el0[0], p_drop, scale);  // p_drop = 0: always 1
-            f2n = b5_drop(a.seed, gnext, el1[0], p_drop, scale);
+            if constexpr (S_DINT) {  // the integer form of the same test
+              f1n = b5_drop_int(a.seed, gnext, el0[0], drop_thr, scale);
+              f2n = b5_drop_int(a.seed, gnext, el1[0], drop_thr, scale);
+            } else {
+              f1n = b5_drop(a.seed, gnext, el0[0], p_drop, scale);  // p_drop = 0: always 1
+              f2n = b5_drop(a.seed, gnext, el1[0], p_drop, scale);
+            }
             asm volatile("" : "+v"(f1n), "+v"(f2n));
           }
           if constexpr (S_TAB) {
@@ -750,24 +818,40 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             }
             aA = rl(tabA, ti);
             aE = rl(tabE, ti);
+            if constexpr (S_SM) {  // one VGPR copy for the step's small updates (a v_fma takes one SGPR)
+              aEv = aE;
+              asm volatile("" : "+v"(aEv));
+            }
           }
           __builtin_amdgcn_sched_barrier(0);
         }
         const float z = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
-        h2 = fmaxf(z + pb1, 0.f) * f2[hf];
+        h2 = fmaxf(z + (S_SM ? PSm.y : pb1), 0.f) * f2[hf];
         const float t0s = sum_bits2to5(pw2[0] * h2), t1s = sum_bits2to5(pw2[1] * h2);  // row r0's shares
-        const unsigned long long msk = __ballot(h2 > 0.f);
-        if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = cb ? t1s : t0s;  // [wave][class][row]
-        if (l == 0)
-          *reinterpret_cast<uint2*>(lds + MSK + mpar * (NW * 2) + w * 2) = make_uint2((uint32_t)msk, (uint32_t)(msk >> 32));
+        if constexpr (S_DZF) {  // [o = u][row r0]: word 64 w + l, one linear store per wave
+          lds[LY::DZF + mpar * (H * 4) + u * 4 + r0] = h2 > 0.f ? scale : 0.f;
+          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = cb ? t1s : t0s;  // [wave][class][row]
+        } else {
+          const unsigned long long msk = __ballot(h2 > 0.f);
+          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = cb ? t1s : t0s;  // [wave][class][row]
+          if (l == 0)
+            *reinterpret_cast<uint2*>(lds + MSK + mpar * (NW * 2) + w * 2) = make_uint2((uint32_t)msk, (uint32_t)(msk >> 32));
+        }
       }
       B5STAMP(3)
       lds_barrier();  // B: logit shares and masks of every wave are in
       B5STAMP(4)
 
       // ---- loss: lane (share l / 8, class cb, row r0) -> logit (r0, cb) of the micro-batch
-      const uint2 mw0 = *reinterpret_cast<const uint2*>(lds + MSK + mpar * (NW * 2) + 2 * (l >> 4));
-      const uint2 mw1 = *reinterpret_cast<const uint2*>(lds + MSK + mpar * (NW * 2) + 2 * ((l >> 4) + 4));
+      uint2 mw0 = make_uint2(0u, 0u), mw1 = mw0;
+      float4 zf0 = make_float4(0.f, 0.f, 0.f, 0.f), zf1 = zf0;  // SCH_DZ2F: factors of outputs l, l + 64
+      if constexpr (S_DZF) {
+        zf0 = *reinterpret_cast<const float4*>(lds + LY::DZF + mpar * (H * 4) + l * 4);
+        zf1 = *reinterpret_cast<const float4*>(lds + LY::DZF + mpar * (H * 4) + (l + 64) * 4);
+      } else {
+        mw0 = *reinterpret_cast<const uint2*>(lds + MSK + mpar * (NW * 2) + 2 * (l >> 4));
+        mw1 = *reinterpret_cast<const uint2*>(lds + MSK + mpar * (NW * 2) + 2 * ((l >> 4) + 4));
+      }
       float lg0 = 0.f;
       if constexpr (HB > 0) {
         // SCH_WTB: the loss below is one dependent chain (LDS read, cross-lane adds, exp, rcp) in every
@@ -846,9 +930,22 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         const float rss = __builtin_amdgcn_rcpf(step_size);
         aA = sqc2 * rbc2 * rss * rc1;
         aE = a.eps * rss * rc1;
+        if constexpr (S_SM) aEv = aE;
       }
       // ---- dZ2 of outputs o = l + 64 j, the micro-batch's rows (old W2, mask bits of the owning wave)
-      {
+      if constexpr (S_DZF) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const float2 wv = j ? wv1 : wv0;
+          const float4 zf = j ? zf1 : zf0;
+          const float fr[4] = {zf.x, zf.y, zf.z, zf.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float g = wv.x * dz3[r][0] + wv.y * dz3[r][1];
+            dz2m[hf][j][r] = g * fr[r];  // fr = scale: the same product; fr = 0: +-0 for +0
+          }
+        }
+      } else {
         const int sh4 = 4 * (l & 15);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -876,8 +973,18 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         float gdz = pw2[0] * dr0 + pw2[1] * dr1;
         gdz = h2 > 0.f ? gdz * scale : 0.f;
         const float gb1 = quad_sum(gdz);
-        const float gbh = (l & 1) ? (dz3[0][1] + dz3[1][1]) + (dz3[2][1] + dz3[3][1])
-                                  : (dz3[0][0] + dz3[1][0]) + (dz3[2][0] + dz3[3][0]);
+        float gbh;
+        if constexpr (S_DB2) {
+          // dz of lane 4 c + r is dlogit (r, c): the quad sum is (d0 + d1) + (d2 + d3) of class cb up to
+          // the order inside a commutative add; lane 1 takes class 1 from lane 5 (row_ror:12 reads lane
+          // i + 4).  Only wave 0's lanes 0 / 1 keep the value
+          const float qs = quad_sum(dz);
+          const float qo = dpp<0x12C>(qs);
+          gbh = (l & 1) ? qo : qs;
+        } else {
+          gbh = (l & 1) ? (dz3[0][1] + dz3[1][1]) + (dz3[2][1] + dz3[3][1])
+                        : (dz3[0][0] + dz3[1][0]) + (dz3[2][0] + dz3[3][0]);
+        }
         gw0s = hf == 0 ? gw0 : gw0s + gw0;
         gw1s = hf == 0 ? gw1 : gw1s + gw1;
         gb1s = hf == 0 ? gb1 : gb1s + gb1;
@@ -893,11 +1000,17 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             xg_own = gown;
             xg_bx = r0 == 1 ? gb1s : gb;  // (r0 0: db0, known after dZ1)
           } else if constexpr (ADAM) {
-            adam_pair<WD>(pown, gown, mw2, vw2, pb1, gb1s, mb1, vb1, a.b1, a.b2, a.wd, aA, aE);
+            if constexpr (S_SM) {
+              PSm.x = pown;
+              adam_v2<WD>(PSm, (v2f){gown, gb1s}, MSm, VSm, a.b1, a.b2, a.wd, aA, aEv);
+              pown = PSm.x;
+            } else {
+              adam_pair<WD>(pown, gown, mw2, vw2, pb1, gb1s, mb1, vb1, a.b1, a.b2, a.wd, aA, aE);
+            }
             pw2[0] = dpp<QB0>(pown);
             pw2[1] = dpp<QB1>(pown);
             if (own_w2) lds[W2L + nbuf * (H * C) + u * C + r0] = pown;
-            adam_scaled<WD>(pb2, gb, mb2, vb2, a.b1, a.b2, a.wd, aA, aE);
+            adam_scaled<WD>(pb2, gb, mb2, vb2, a.b1, a.b2, a.wd, aA, S_SM ? aEv : aE);
             if (own_b2) lds[B2L + nbuf * 4 + l] = pb2;
           } else {  // grad mode (one step): dW2[r0][u], db1[u], db2 to the flat gradient
             if (own_w2) a.grad_out[fw2] = gown;
@@ -981,8 +1094,11 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
                 }
             }
           } else if constexpr (ADAM) {
-            adam_pair<WD>(w0[0], g0, m0[0], v0[0], w0[1], g1, m0[1], v0[1], a.b1, a.b2, a.wd, aA, aE);  // d >= D0: stays 0
-            adam_scaled<WD>(pb0, db0s, mb0, vb0, a.b1, a.b2, a.wd, aA, aE);
+            if constexpr (S_SM)
+              adam_v2<WD>(PW0, (v2f){g0, g1}, MW0, VW0, a.b1, a.b2, a.wd, aA, aEv);
+            else
+              adam_pair<WD>(w0[0], g0, m0[0], v0[0], w0[1], g1, m0[1], v0[1], a.b1, a.b2, a.wd, aA, aE);  // d >= D0: stays 0
+            adam_scaled<WD>(pb0, db0s, mb0, vb0, a.b1, a.b2, a.wd, aA, S_SM ? aEv : aE);
           } else {
             if (r0 < D0) a.grad_out[wo0 + u * D0 + r0] = g0;
             if (r0 + 4 < D0) a.grad_out[wo0 + u * D0 + r0 + 4] = g1;
@@ -1150,6 +1266,10 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     __builtin_amdgcn_wave_barrier();  // the next step rewrites this wave's h1 tiles
     B5STAMP(8)
     xb = xbn;
+  }
+  if constexpr (S_SM) {  // the small pairs back to their scalars (the write-back below)
+    pb1 = PSm.y; mw2 = MSm.x; mb1 = MSm.y; vw2 = VSm.x; vb1 = VSm.y;
+    w0[0] = PW0.x; w0[1] = PW0.y; m0[0] = MW0.x; m0[1] = MW0.y; v0[0] = VW0.x; v0[1] = VW0.y;
   }
 
   if constexpr (XW > 1) {
