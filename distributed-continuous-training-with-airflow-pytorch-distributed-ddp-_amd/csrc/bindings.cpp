@@ -16,6 +16,7 @@
 
 #include "kernels.h"
 #include "mlp_fused.h"
+#include "mlp_select.h"
 #include "runtime.h"
 #include "mlp_executor.h"
 
@@ -63,8 +64,27 @@ struct MlpPlan {
   }
   int use_tile = 0;  // mlp_tile.hip runs this plan's training launches
   const dct::MlpShape* sh() const { return reinterpret_cast<const dct::MlpShape*>(shape.data()); }
+  // the trainer of a launch (mlp_select.h): launch_train and the Python query `trainer` both ask here
+  dct::MlpChoice select(const dct::MlpLaunchKey& k) const {
+    return dct::mlp_select_trainer(*sh(), use_wave != 0, use_tile != 0, k);
+  }
 };
 
+
+// The key of a described launch (MlpPlan.trainer): what mlp_launch_key would derive from its arguments,
+// with every buffer the description implies bound.
+static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, int rank, int loss_kind, bool prof,
+                                   bool cursor, bool stage, bool pending, bool aligned) {
+  dct::MlpLaunchKey k{};
+  k.B = batch; k.mode = mode; k.steps = steps; k.loss_kind = loss_kind;
+  k.xg_world = world; k.xg_rank = rank;
+  k.cursor = cursor; k.stage = stage; k.pending = pending; k.prof = prof;
+  k.grad_out = mode == 1;
+  k.moments = mode == 0 || pending;
+  k.xg_bufs = world > 1;
+  k.p_aligned = k.mv_aligned = aligned;
+  return k;
+}
 
 // Validated MlpArgs of a training launch (the kernels trust their arguments).
 static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t grad_out,
@@ -116,36 +136,46 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
   a.xg_status = P<unsigned int>(xg_status);
   a.xg_timeout = xg_timeout;
   a.xg_poll = xg_poll;
-  if (xg_world > 1) {
-    const dct::MlpShape* sh = plan.sh();
-    const bool wave = plan.use_wave && dct_mlp_wave_supported(sh->dims, sh->L, B);
-    const bool blk5 = !plan.use_wave && mode == 0 && dct::mlp_block5_shape_ok(sh->dims, sh->L, B) &&
-                      dct::mlp_block5_xg_bytes(xg_world) > 0;
-    if (!wave && !blk5)
-      throw std::invalid_argument("in-kernel all-reduce needs the single-wave kernel or the 3x128 block kernel "
-                                  "(train mode, 2 / 4 / 8 ranks)");
-    if (!xg_recv || !xg_peers || !xg_status || xg_rank < 0 || xg_rank >= xg_world)
-      throw std::invalid_argument("in-kernel all-reduce: exchange buffers / rank missing");
-  }
-  if (plan.use_tile && (xg_world > 1 || pending))
-    throw std::invalid_argument("the batch-tiled trainer has no in-kernel all-reduce and no update-then-grad step");
-  if (pending && (mode != 1 || !plan.use_wave || !mo || !vo))
-    throw std::invalid_argument("update-then-grad needs grad mode, m/v and the single-wave kernel");
+  // a request no trainer of this plan serves is an invalid argument; a chosen trainer's own refusal of
+  // the arguments surfaces in launch_train
+  const dct::MlpChoice c = plan.select(dct::mlp_launch_key(a));
+  if (c.trainer == dct::MLP_NONE && c.plan_level) throw std::invalid_argument(c.why_none);
+  if (xg_world > 1 && (!xg_recv || !xg_peers || !xg_status || xg_rank < 0 || xg_rank >= xg_world))
+    throw std::invalid_argument("in-kernel all-reduce: exchange buffers / rank missing");
+  if (pending && (mode != 1 || !mo || !vo)) throw std::invalid_argument("update-then-grad needs grad mode and m/v");
   if (cursor && mode != 1) throw std::invalid_argument("cursor is only valid in grad mode");
   if (mode == 1 && !grad_out) throw std::invalid_argument("grad mode needs grad_out");
   if (mode == 1 && steps != 1) throw std::invalid_argument("grad mode runs exactly one step");
   return a;
 }
 
-static void launch_train(const MlpPlan& plan, const dct::MlpArgs& a, uintptr_t stream) {
+static void launch_train(const MlpPlan& plan, dct::MlpArgs& a, uintptr_t stream) {
   const dct::MlpShape* sh = plan.sh();
-  if (plan.use_tile) {
-    if (!a.tile_ws) throw std::invalid_argument("the batch-tiled trainer needs its slot workspace");
-    check(dct_mlp_tile_train(sh->dims, sh->L, &a, reinterpret_cast<void*>(stream)), "mlp_tile_train");
-  } else if (plan.use_wave && dct_mlp_wave_supported(sh->dims, sh->L, a.B))
-    check(dct_mlp_wave_train(sh->dims, sh->L, &a, reinterpret_cast<void*>(stream)), "mlp_wave_train");
-  else
-    check(dct_mlp_train(plan.shape.data(), &a, reinterpret_cast<void*>(stream)), "mlp_train");
+  void* st = reinterpret_cast<void*>(stream);
+  const dct::MlpChoice c = plan.select(dct::mlp_launch_key(a));
+  if (!c.use_stage) a.stage = nullptr;
+  switch (c.trainer) {
+    case dct::MLP_TILE:
+      if (!a.tile_ws) throw std::invalid_argument("the batch-tiled trainer needs its slot workspace");
+      check(dct_mlp_tile_train(sh->dims, sh->L, &a, st), "mlp_tile_train");
+      break;
+    case dct::MLP_WAVE_SINGLE:
+    case dct::MLP_WAVE_ROWS:
+      check(dct_mlp_wave_train(sh->dims, sh->L, &a, c.trainer == dct::MLP_WAVE_ROWS, st), "mlp_wave_train");
+      break;
+    case dct::MLP_BLOCK5:
+    case dct::MLP_BLOCK5_B8:
+      check((int)dct::mlp_launch_block5(*sh, a, reinterpret_cast<hipStream_t>(st)), "mlp_train");
+      break;
+    case dct::MLP_BLOCK3:
+      check((int)dct::mlp_launch_block3(*sh, a, reinterpret_cast<hipStream_t>(st)), "mlp_train");
+      break;
+    case dct::MLP_LDS:
+      check(dct_mlp_lds_train(plan.shape.data(), &a, st), "mlp_train");
+      break;
+    case dct::MLP_NONE:
+      throw std::runtime_error(std::string("no fused MLP trainer takes this launch: ") + c.why_none);
+  }
 }
 
 // A training launch with every operand bound once (FusedMLPKernel.prepare_train validates
@@ -236,6 +266,25 @@ PYBIND11_MODULE(_dct_native, m) {
       .def_property_readonly("lds_bytes", [](const MlpPlan& p) { return p.sh()->lds_floats * 4; })
       .def_property_readonly("bmax", [](const MlpPlan& p) { return p.sh()->bmax; })
       .def_property_readonly("mlp_block", [](const MlpPlan& p) { return p.sh()->mlp_block; })
+      // the trainer a launch of this description reaches: "wave_single", "wave_rows", "block5", "block5_b8",
+      // "block3", "lds", "tile" or "none".  `aligned`: the flat buffers lie on 16-byte boundaries.  No device needed.
+#define MLP_QUERY_ARGS                                                                                              \
+  py::arg("batch"), py::arg("mode") = 0, py::arg("steps") = 1, py::arg("world") = 1, py::arg("rank") = 0,           \
+      py::arg("loss_kind") = 0, py::arg("prof") = false, py::arg("cursor") = false, py::arg("stage") = false,       \
+      py::arg("pending") = false, py::arg("aligned") = true
+      .def("trainer", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
+                         bool prof, bool cursor, bool stage, bool pending, bool aligned) {
+        return std::string(dct::mlp_trainer_name(
+            plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned))
+                .trainer));
+      }, MLP_QUERY_ARGS)
+      // whether that launch reads its staged-batch buffer (the wave kernels and mlp_block5's grad mode do)
+      .def("uses_stage", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
+                            bool prof, bool cursor, bool stage, bool pending, bool aligned) {
+        return plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned))
+            .use_stage;
+      }, MLP_QUERY_ARGS)
+#undef MLP_QUERY_ARGS
       .def(
           "train",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t grad_out, uintptr_t X, int ldx,
@@ -699,6 +748,16 @@ PYBIND11_MODULE(_dct_native, m) {
     if (dims.size() != 4 || !dct::mlp_block5_shape_ok(dims.data(), 3, B)) return 0;
     return (int64_t)dct::mlp_block5_xg_bytes(world);
   }, py::arg("dims"), py::arg("batch"), py::arg("world"));
+  // shape checks of the small-MLP trainers, each the kernel's own (no device needed)
+  m.def("mlp_supported", [](const std::vector<int>& dims, int batch) {
+    return dct_mlp_supported(dims.data(), (int)dims.size() - 1, batch) != 0;
+  }, py::arg("dims"), py::arg("batch"));
+  m.def("mlp_wave_supported", [](const std::vector<int>& dims, int batch) {
+    return dims.size() >= 2 && dct_mlp_wave_supported(dims.data(), (int)dims.size() - 1, batch) != 0;
+  }, py::arg("dims"), py::arg("batch"));
+  m.def("mlp_tile_supported", [](const std::vector<int>& dims) {
+    return dims.size() >= 2 && dct_mlp_tile_supported(dims.data(), (int)dims.size() - 1) != 0;
+  }, py::arg("dims"));
   m.def("mlp_tile_ws_floats", [](const std::vector<int>& dims, int B) {
     return (int64_t)dct_mlp_tile_ws_floats(dims.data(), (int)dims.size() - 1, B);
   });

@@ -9,7 +9,7 @@
 namespace dct {
 
 struct Knobs {
-  // fused MLP trainers (mlp_fused.hip dispatch, bindings.cpp plan)
+  // fused MLP trainers (bindings.cpp plan -> mlp_select.cpp)
   int mlp_force_lds = 0;    // DCT_MLP_KERNEL=lds: the LDS/block kernels even where the wave kernel fits
   int mlp_block = -1;       // DCT_MLP_BLOCK: -1 auto, 0 generic LDS trainer, 3 force mlp_block3, 8 mlp_block5's
                             // two-micro-batch kernels at every batch (tests: == the one-micro-batch kernels at B <= 4),

@@ -3,7 +3,7 @@
 // the reference's WeatherClassifier with a second 128-wide hidden layer,
 // jobs/train_lightning_ddp.py:57-62,69,88,122).  Same contract as mlp_train_kernel: one workgroup
 // runs every step of a launch with the same dropout hash, loss and Adam, so it is a drop-in
-// replacement selected by dct_mlp_train (mlp_block2.hip, its one-barrier predecessor, stays
+// replacement selected by mlp_select_trainer (mlp_block2.hip, its one-barrier predecessor, stays
 // selectable with DCT_MLP_BLOCK=2 for A/B).
 //
 // Per step, 8 waves (2 per SIMD):
@@ -22,6 +22,7 @@
 //   * dZ1 = W1^T dZ2 over the wave's k-slice (permlane / DPP reduce-scatter, no LDS), dW0 / db0
 //     via quad DPP broadcasts, dW1 on the 4x4x1 MFMA (D0 <= 8, C <= 2) or the VALU, Adam in VGPRs.
 #include "mlp_block_util.h"
+#include "mlp_select.h"
 
 namespace dct {
 
@@ -564,16 +565,14 @@ __global__ __launch_bounds__(blk3::NT, 1) void mlp_block3_kernel(MlpShape sh, Ml
 }
 #undef B3STAMP
 
-bool mlp_block3_ok(const MlpShape& sh, const MlpArgs& a) {
-  if (sh.mlp_block == 0) return false;  // DCT_MLP_BLOCK=0 (plan-time copy): the generic LDS trainer
+bool mlp_block3_takes(const MlpShape& sh, const MlpLaunchKey& k) {
   // a profiling launch is served for the weather shape (D0 <= 8, C <= 2, train mode) only
-  const bool prof_ok = a.prof == nullptr || (sh.dims[0] <= 8 && sh.dims[3] <= 2 && a.mode == 0);
+  const bool prof_ok = !k.prof || (sh.dims[0] <= 8 && sh.dims[3] <= 2 && k.mode == 0);
   // 16-byte W1 row loads / stores
-  const bool aligned = (sh.woff[1] % 4) == 0 && ((uintptr_t)a.p & 15) == 0 &&
-                       (a.mode != 0 || (((uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0);
+  const bool aligned = (sh.woff[1] % 4) == 0 && k.p_aligned && (k.mode != 0 || k.mv_aligned);
   return prof_ok && aligned && sh.L == 3 && sh.dims[1] == blk3::H && sh.dims[2] == blk3::H && sh.dims[0] >= 1 &&
-         sh.dims[0] <= blk3::DMAX && sh.dims[3] >= 1 && sh.dims[3] <= 4 && a.B >= 1 && a.B <= blk3::B &&
-         a.pending == nullptr && a.stage == nullptr && a.xg_world <= 1 && (a.mode == 0 || a.mode == 1);
+         sh.dims[0] <= blk3::DMAX && sh.dims[3] >= 1 && sh.dims[3] <= 4 && k.B >= 1 && k.B <= blk3::B &&
+         !k.pending && !k.stage && k.xg_world <= 1 && (k.mode == 0 || k.mode == 1);
 }
 
 // one launch of an instantiation; its dynamic-LDS limit (two 64-KB staging tiles) is raised once
@@ -586,6 +585,7 @@ static void b3_launch(size_t bytes, hipStream_t st, const MlpShape& sh, const Ml
 }
 
 hipError_t mlp_launch_block3(const MlpShape& sh, const MlpArgs& a, hipStream_t st) {
+  if (!mlp_block3_takes(sh, mlp_launch_key(a))) return hipErrorInvalidValue;
   const int d0 = sh.dims[0], C = sh.dims[3];
   const bool tr = a.mode == 0;
   const size_t bytes = (size_t)blk3::LDS_FLOATS * sizeof(float);

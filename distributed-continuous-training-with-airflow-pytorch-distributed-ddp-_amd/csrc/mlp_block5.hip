@@ -4,6 +4,7 @@
 // (profiles/b5_sched_strategy_ab_r4.log).
 #include "knobs.h"
 #include "mlp_block5_impl.h"
+#include "mlp_select.h"
 
 namespace dct {
 
@@ -14,18 +15,23 @@ void mlp_launch_block5_b8(size_t bytes, hipStream_t st, const MlpShape& sh, cons
 // instantiations exist for 2 / 4 / 8
 static bool b5_xg_world_ok(int w) { return w >= 2 && w <= 8; }
 
-bool mlp_block5_ok(const MlpShape& sh, const MlpArgs& a) {
-  const bool aligned = (sh.woff[1] % 4) == 0 && ((uintptr_t)a.p & 15) == 0 && (((uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0;
-  const bool xg_ok = a.xg_world <= 1 ||
-                     (a.mode == 0 && b5_xg_world_ok(a.xg_world) && a.xg_rank >= 0 && a.xg_rank < a.xg_world &&
-                      a.xg_recv != nullptr && a.xg_peers != nullptr && a.xg_status != nullptr &&
-                      (a.prof == nullptr || a.xg_world == 2 || a.xg_world == 4 || a.xg_world == 8));
-  // per-rank batch 5..8 (two micro-batches per step, mlp_block5_b8.hip): no profiling instantiation
-  const bool b8_ok = (a.B <= blk5::B && sh.mlp_block != 8) || a.prof == nullptr;
-  return aligned && b8_ok && mlp_block5_shape_ok(sh.dims, sh.L, a.B) &&
+// per-rank batch 5..8, or every batch under DCT_MLP_BLOCK=8: two micro-batches per step (mlp_block5_b8.hip)
+bool mlp_block5_two_micro(const MlpShape& sh, int B) { return B > blk5::B || sh.mlp_block == 8; }
+
+bool mlp_block5_takes(const MlpShape& sh, const MlpLaunchKey& k) {
+  const bool aligned = (sh.woff[1] % 4) == 0 && k.p_aligned && k.mv_aligned;
+  const bool xg_ok = k.xg_world <= 1 ||
+                     (k.mode == 0 && b5_xg_world_ok(k.xg_world) && k.xg_rank >= 0 && k.xg_rank < k.xg_world &&
+                      k.xg_bufs && (!k.prof || k.xg_world == 2 || k.xg_world == 4 || k.xg_world == 8));
+  const bool b8_ok = !mlp_block5_two_micro(sh, k.B) || !k.prof;  // no profiling instantiation of the b8 kernels
+  return aligned && b8_ok && mlp_block5_shape_ok(sh.dims, sh.L, k.B) &&
          // train mode, or grad mode for ONE step (the DDP step path: grads + loss to grad_out, device cursor)
-         ((a.mode == 0 && a.cursor == nullptr) || (a.mode == 1 && a.steps == 1 && a.grad_out != nullptr)) &&
-         (a.loss_kind == 0 || a.loss_kind == 1) && a.pending == nullptr && (a.stage == nullptr || a.mode == 1) && xg_ok;
+         ((k.mode == 0 && !k.cursor) || (k.mode == 1 && k.steps == 1 && k.grad_out)) &&
+         (k.loss_kind == 0 || k.loss_kind == 1) && !k.pending && (!k.stage || k.mode == 1) && xg_ok;
+}
+
+bool mlp_block5_xg_shape_ok(const MlpShape& sh, const MlpLaunchKey& k) {
+  return k.mode == 0 && mlp_block5_shape_ok(sh.dims, sh.L, k.B) && mlp_block5_xg_bytes(k.xg_world) > 0;
 }
 
 bool mlp_block5_shape_ok(const int* dims, int L, int B) {
@@ -79,7 +85,8 @@ hipError_t mlp_launch_block5(const MlpShape& sh, const MlpArgs& a, hipStream_t s
   const size_t bytes = (size_t)blk5::LDS_FLOATS * sizeof(float);
   const bool wd = a.wd != 0.f;
   const int sched = knobs().b5_sched;
-  if (a.B > blk5::B || sh.mlp_block == 8) {
+  if (!mlp_block5_takes(sh, mlp_launch_key(a))) return hipErrorInvalidValue;
+  if (mlp_block5_two_micro(sh, a.B)) {
     mlp_launch_block5_b8(bytes, st, sh, a);  // two micro-batches per step, every world size
   } else if (a.xg_world > 1) {
     mlp_launch_block5_xg(a.xg_world, bytes, st, sh, a);  // mlp_block5_xg.hip

@@ -22,7 +22,7 @@ static void b5_launch_xg_prof(size_t bytes, hipStream_t st, const MlpShape& sh, 
 void mlp_launch_block5_xg_prof(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
   if (world == 2) b5_launch_xg_prof<2>(bytes, st, sh, a);
   else if (world == 4) b5_launch_xg_prof<4>(bytes, st, sh, a);
-  else if (world == 8) b5_launch_xg_prof<8>(bytes, st, sh, a);  // (3 / 5 / 6 / 7 ranks: no profiling instantiation; mlp_block5_ok refuses prof there)
+  else if (world == 8) b5_launch_xg_prof<8>(bytes, st, sh, a);  // (3 / 5 / 6 / 7 ranks: no profiling instantiation; mlp_block5_takes refuses prof there)
 }
 
 }  // namespace dct

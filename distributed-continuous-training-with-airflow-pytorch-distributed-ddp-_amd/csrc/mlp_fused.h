@@ -127,17 +127,17 @@ constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
 hipError_t mlp_launch_train_L2(const MlpShape& sh, const MlpArgs& a, hipStream_t st);
 hipError_t mlp_launch_train_L3(const MlpShape& sh, const MlpArgs& a, hipStream_t st);
 hipError_t mlp_launch_train_L4(const MlpShape& sh, const MlpArgs& a, hipStream_t st);
+// Which trainer runs a launch is mlp_select.h's decision; the launchers below refuse what their
+// kernel does not take (hipErrorInvalidValue) and choose only among their own instantiations.
 // register-resident 8-wave two-barrier trainer for D0 <= 32 -> 128 -> 128 -> C <= 4, train and
 // grad mode (mlp_block3.hip): every 3x128 shape mlp_block5 does not take
-bool mlp_block3_ok(const MlpShape& sh, const MlpArgs& a);
 hipError_t mlp_launch_block3(const MlpShape& sh, const MlpArgs& a, hipStream_t st);
 // lean two-barrier trainer for the exact weather shape D0<=8 -> 128 -> 128 -> 2, train mode, the
 // one-step grad mode and the in-kernel data-parallel launches (mlp_block5.hip, the default there);
 // DCT_MLP_BLOCK=3 selects mlp_block3, DCT_MLP_BLOCK=0 the generic LDS trainer
-bool mlp_block5_ok(const MlpShape& sh, const MlpArgs& a);
 hipError_t mlp_launch_block5(const MlpShape& sh, const MlpArgs& a, hipStream_t st);
-// its shape (D0 <= 8 -> 128 -> 128 -> 2, batch <= 4) and the exchange buffer of its in-kernel
-// data-parallel launches at `world` = 2 / 4 / 8 ranks (0: not supported)
+// its shape (D0 <= 8 -> 128 -> 128 -> 2, batch <= 8) and the exchange buffer of its in-kernel
+// data-parallel launches at `world` = 2 .. 8 ranks (0: not supported)
 bool mlp_block5_shape_ok(const int* dims, int L, int B);
 size_t mlp_block5_xg_bytes(int world);
 hipError_t mlp_launch_eval_L2(const MlpShape& sh, const MlpArgs& a, int grid, hipStream_t st);
@@ -150,10 +150,11 @@ extern "C" {
 int dct_mlp_shape_size();
 int dct_mlp_make_shape(void* out, const int* dims, int L, int bmax);
 int dct_mlp_select(const dct::MlpShape* sh, int* nt, int* maxblk);
-int dct_mlp_train(const void* shape, const dct::MlpArgs* a, void* stream);
+int dct_mlp_lds_train(const void* shape, const dct::MlpArgs* a, void* stream);  // the generic LDS trainer
 int dct_mlp_eval(const void* shape, const dct::MlpArgs* a, int grid, void* stream);
 int dct_mlp_wave_supported(const int* dims, int L, int B);
-int dct_mlp_wave_train(const int* dims, int L, const dct::MlpArgs* a, void* stream);
+// rows != 0: the row-parallel kernels (mlp_select.h MLP_WAVE_ROWS), else the single-wave kernel
+int dct_mlp_wave_train(const int* dims, int L, const dct::MlpArgs* a, int rows, void* stream);
 size_t dct_mlp_xg_slab_granules(const int* dims, int L);
 // batch-tiled trainer for per-rank batch 17..1024 (mlp_tile.hip; DCT_MLP_BLOCK=tile forces it at smaller batches)
 int dct_mlp_tile_supported(const int* dims, int L);

@@ -137,23 +137,12 @@ int dct_mlp_select(const MlpShape* sh, int* nt, int* maxblk) {
   return sh->supported;
 }
 
-int dct_mlp_train(const void* shape, const MlpArgs* a, void* stream) {
+// the generic LDS trainer: no exchange, no staged batches (mlp_select.h sends those elsewhere)
+int dct_mlp_lds_train(const void* shape, const MlpArgs* a, void* stream) {
   const MlpShape& sh = *reinterpret_cast<const MlpShape*>(shape);
   if (!sh.supported) return (int)hipErrorInvalidValue;
-  if (a->B < 1 || a->B > sh.bmax) return (int)hipErrorInvalidValue;
+  if (a->B < 1 || a->B > sh.bmax || a->xg_world > 1 || a->stage) return (int)hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a->stage && !dct::mlp_block5_ok(sh, *a)) {  // only mlp_block5's grad mode stages batches here
-    MlpArgs b = *a;
-    b.stage = nullptr;
-    return dct_mlp_train(shape, &b, stream);
-  }
-  if (a->xg_world > 1) {  // in-kernel data parallelism: only the 3x128 block kernel has it here
-    if (!dct::mlp_block5_ok(sh, *a)) return (int)hipErrorInvalidValue;
-    return (int)dct::mlp_launch_block5(sh, *a, st);
-  }
-  const int blk = sh.mlp_block;  // plan-time DCT_MLP_BLOCK: -1 auto, 3 mlp_block3, 0 the generic LDS trainer
-  if ((blk < 0 || blk == 8) && dct::mlp_block5_ok(sh, *a)) return (int)dct::mlp_launch_block5(sh, *a, st);
-  if (blk != 0 && dct::mlp_block3_ok(sh, *a)) return (int)dct::mlp_launch_block3(sh, *a, st);
   switch (sh.L) {
     case 2: return (int)dct::mlp_launch_train_L2(sh, *a, st);
     case 3: return (int)dct::mlp_launch_train_L3(sh, *a, st);

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "mlp_fused_impl.h"
+#include "mlp_select.h"
 
 namespace dct {
 namespace tile {
@@ -446,6 +447,9 @@ static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* 
 }
 
 }  // namespace tile
+
+bool mlp_tile_batch_ok(int B) { return B >= 1 && B <= tile::BMAX; }
+
 }  // namespace dct
 
 extern "C" {

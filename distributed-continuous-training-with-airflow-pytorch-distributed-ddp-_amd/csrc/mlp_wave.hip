@@ -1,6 +1,7 @@
 // Entry points of the narrow-MLP trainers (kernels: mlp_wave_impl.h; the template instantiations
 // live in mlp_wave_rows_x*.hip / mlp_wave_single*.hip so they compile in parallel).
 #include "mlp_wave_impl.h"
+#include "mlp_select.h"
 
 extern "C" {
 
@@ -23,8 +24,11 @@ size_t dct_mlp_xg_slab_granules(const int* dims, int L) {
   return wave_kernel > (size_t)dct::XG_ROWS_GRANULES ? wave_kernel : (size_t)dct::XG_ROWS_GRANULES;
 }
 
-int dct_mlp_wave_train(const int* dims, int L, const dct::MlpArgs* a, void* stream) {
-  if (!dct_mlp_wave_supported(dims, L, a->B)) return (int)hipErrorInvalidValue;
+int dct_mlp_wave_train(const int* dims, int L, const dct::MlpArgs* a, int rows, void* stream) {
+  const dct::MlpLaunchKey k = dct::mlp_launch_key(*a);
+  if (!dct_mlp_wave_supported(dims, L, a->B) || (a->xg_world > 1 && !dct::mlp_wave_xg_takes(L, k)) ||
+      (rows && !dct::mlp_wave_rows_takes(L, k)))
+    return (int)hipErrorInvalidValue;
   WaveShape sh{};
   sh.L = L;
   sh.d0 = dims[0];
@@ -40,20 +44,34 @@ int dct_mlp_wave_train(const int* dims, int L, const dct::MlpArgs* a, void* stre
   }
   sh.P = flat;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool xg = a->xg_world > 1;
-  if (xg) {
-    if (L != 2 || a->mode != 0 || !a->xg_recv || !a->xg_peers || !a->xg_status || a->xg_world > dct::XG_MAXW ||
-        a->xg_rank < 0 || a->xg_rank >= a->xg_world || a->cursor || a->pending)
-      return (int)hipErrorInvalidValue;
-    if (rows_eligible(L, *a)) {
-      if (a->xg_world <= 2) return (int)dct::wave_rows_launch_x2(sh, *a, st);
-      if (a->xg_world <= 4) return (int)dct::wave_rows_launch_x4(sh, *a, st);
-      return (int)dct::wave_rows_launch_x8(sh, *a, st);
-    }
-    return (int)dct::wave_single_launch_xg(sh, *a, st);
+  if (a->xg_world > 1) {
+    if (!rows) return (int)dct::wave_single_launch_xg(sh, *a, st);
+    if (a->xg_world <= 2) return (int)dct::wave_rows_launch_x2(sh, *a, st);
+    if (a->xg_world <= 4) return (int)dct::wave_rows_launch_x4(sh, *a, st);
+    return (int)dct::wave_rows_launch_x8(sh, *a, st);
   }
-  if (rows_eligible(L, *a)) return (int)dct::wave_rows_launch_x0(sh, *a, st);
+  if (rows) return (int)dct::wave_rows_launch_x0(sh, *a, st);
   return (int)dct::wave_single_launch(sh, *a, st);
 }
 
 }  // extern "C"
+
+namespace dct {
+
+// the row-parallel kernel takes plain train-mode launches of 2-layer nets
+bool mlp_wave_rows_takes(int L, const MlpLaunchKey& k) {
+#ifdef WAVE_PROF_BUILD
+  const bool prof_ok = true;  // profiling build: the rows kernel stamps its phases into MlpArgs::prof
+#else
+  const bool prof_ok = !k.prof;
+#endif
+  return L == 2 && k.mode == 0 && !k.cursor && !k.pending && !k.stage && prof_ok && k.B >= 1 && k.B <= 8 && k.moments;
+}
+
+// in-kernel data-parallel launches of the wave kernels: 2-layer nets, train mode, up to XG_MAXW ranks
+bool mlp_wave_xg_takes(int L, const MlpLaunchKey& k) {
+  return L == 2 && k.mode == 0 && k.xg_bufs && k.xg_world <= XG_MAXW && k.xg_rank >= 0 && k.xg_rank < k.xg_world &&
+         !k.cursor && !k.pending;
+}
+
+}  // namespace dct

@@ -1351,17 +1351,6 @@ hipError_t launch_rows_d0(const WaveShape& sh, const MlpArgs& a, hipStream_t st)
   return hipErrorInvalidValue;
 }
 
-// the row-parallel kernel takes plain train-mode launches of 2-layer nets
-bool rows_eligible(int L, const MlpArgs& a) {
-#ifdef WAVE_PROF_BUILD
-  const bool prof_ok = true;  // profiling build: the rows kernel stamps its phases into a.prof
-#else
-  const bool prof_ok = !a.prof;
-#endif
-  return L == 2 && a.mode == 0 && !a.cursor && !a.pending && !a.stage && prof_ok && a.B >= 1 &&
-         a.B <= 8 && a.m && a.v;
-}
-
 template <int BMAX>
 hipError_t launch_wave_xg(const WaveShape& sh, const MlpArgs& a, hipStream_t st) {
   if (a.xg_world <= 2) return launch_wave_d0<2, BMAX, 2>(sh, a, st);

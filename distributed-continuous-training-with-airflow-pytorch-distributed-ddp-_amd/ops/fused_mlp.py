@@ -28,14 +28,13 @@ def mlp_num_params(dims: Sequence[int]) -> int:
 TILE_BMAX = 1024  # largest per-rank batch of the batch-tiled trainer (csrc/mlp_tile.hip)
 
 
+WAVE_TRAINERS = ("wave_single", "wave_rows")  # MlpPlan.trainer's names (csrc/mlp_select.h)
+BLOCK5_TRAINERS = ("block5", "block5_b8")
+
+
 def tile_supported(dims: Sequence[int]) -> bool:
-    """Host-side mirror of the batch-tiled trainer's shape check (csrc/mlp_tile.hip make_plan)."""
-    L = len(dims) - 1
-    if L not in (2, 3):
-        return False
-    if not (1 <= dims[0] <= 32 and 2 <= dims[-1] <= 4):
-        return False
-    return all(16 <= h <= 128 and h % 16 == 0 for h in dims[1:-1])
+    """The batch-tiled trainer's own shape check (csrc/mlp_tile.hip make_plan); no GPU needed."""
+    return bool(native().mlp_tile_supported([int(d) for d in dims]))
 
 
 def _mix_hash(a, b, c):
@@ -109,13 +108,8 @@ def wave_dropout_keep_mask(seed: int, gstep: int, layer: int, n_rows: int, n_uni
 
 
 def wave_supported(dims: Sequence[int], batch: int) -> bool:
-    """Host-side mirror of the wave kernels' shape / batch check (csrc/mlp_wave.hip)."""
-    L = len(dims) - 1
-    if L not in (2, 3):
-        return False
-    if dims[0] > 16 or dims[-1] > 4 or not 1 <= batch <= 8:
-        return False
-    return all(h <= 64 for h in dims[1:-1])
+    """The wave kernels' own shape / batch check (csrc/mlp_wave.hip); no GPU needed."""
+    return bool(native().mlp_wave_supported([int(d) for d in dims], int(batch)))
 
 
 class FusedMLPKernel:
@@ -148,19 +142,18 @@ class FusedMLPKernel:
 
     def fused_update_supported(self, batch: int) -> bool:
         """True if the update-then-grad DDP step (one kernel per step) is available."""
-        return bool(self.plan.use_wave) and not self.plan.use_tile and batch <= 8
+        return self.plan.trainer(int(batch), mode=1, pending=True) == "wave_single"
 
     def dropout_mask(self, seed: int, gstep: int, layer: int, batch: int, p: float) -> torch.Tensor:
         """Host mirror of the mask a training launch of this plan draws for hidden layer ``layer`` at
-        global step ``gstep``: bool [batch, dims[layer + 1]], True = kept.  The hash family follows the
-        launcher's own rule (csrc/bindings.cpp launch_train): the wave kernels' when the plan is a wave
-        plan and the wave kernels take this batch, ``dropout_keep_mask`` for every other trainer."""
+        global step ``gstep``: bool [batch, dims[layer + 1]], True = kept.  The hash family is that of the
+        trainer the plan names for this batch (``MlpPlan.trainer``): the wave kernels' for the two wave
+        trainers, ``dropout_keep_mask`` for every other one."""
         if not 0 <= layer < len(self.dims) - 2:
             raise ValueError(f"hidden layer {layer} outside 0..{len(self.dims) - 3}")
         if not 1 <= batch <= self.bmax:
             raise ValueError(f"batch {batch} outside 1..{self.bmax}")
-        wave = bool(self.plan.use_wave) and not self.plan.use_tile and wave_supported(self.dims, batch)
-        mirror = wave_dropout_keep_mask if wave else dropout_keep_mask
+        mirror = wave_dropout_keep_mask if self.plan.trainer(int(batch)) in WAVE_TRAINERS else dropout_keep_mask
         return mirror(seed, gstep, layer, batch, self.dims[layer + 1], p)
 
     @property
@@ -171,31 +164,9 @@ class FusedMLPKernel:
 
     @staticmethod
     def supported(dims: Sequence[int], batch: int) -> bool:
-        """Host-side mirror of dct::mlp_make_shape's plan (no GPU needed)."""
-        L = len(dims) - 1
-        if batch > 16:  # the batch-tiled trainer (csrc/mlp_tile.hip)
-            return batch <= TILE_BMAX and tile_supported(dims)
-        if not (2 <= L <= 4) or batch < 1:
-            return False
-        bmax = 4 if batch <= 4 else 16
-        r4 = lambda x: (x + 3) // 4 * 4  # noqa: E731
-        nblk4 = sum((r4(dims[i + 1]) // 4) * (r4(dims[i]) // 4) for i in range(L))
-        nblk1 = sum(dims[i + 1] * (r4(dims[i]) // 4) for i in range(L))
-        if nblk1 <= 512 or nblk4 <= 1024:
-            nt = 256
-        elif nblk4 <= 2048:
-            nt = 512
-        else:
-            return False
-        if sum(dims[1:]) > 2 * nt:
-            return False
-        lds = 0
-        for i in range(L):
-            ldw = r4(dims[i]) + (4 if r4(dims[i]) % 8 == 0 else 0)
-            lds += r4(dims[i + 1]) * ldw + r4(dims[i + 1])
-        lds += 2 * bmax * r4(dims[0]) + sum(bmax * r4(d) for d in dims[1:])
-        lds += sum(bmax * r4(d) for d in dims[1:]) + 2 * r4(bmax) + r4(2 * bmax)
-        return lds * 4 <= 160 * 1024
+        """Some fused trainer takes this architecture at this per-rank batch: the plan's own budget
+        (csrc/mlp_fused.hip mlp_make_shape) up to batch 16, the batch-tiled trainer's above.  No GPU needed."""
+        return bool(native().mlp_supported([int(d) for d in dims], int(batch)))
 
     # ------------------------------------------------------------------ checks
     def _check_params(self, *ts):
@@ -267,8 +238,7 @@ class FusedMLPKernel:
             ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), int(batch), int(steps), int(t0),
             float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, int(step_base) & 0xFFFFFFFF, ptr(loss_out), mode, LOSS_KINDS[loss],
-            ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending),
-            ptr(stage) if (stage is not None and (self.plan.use_wave or mode == 1)) else 0,
+            ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending), ptr(stage),
             stream if stream is not None else stream_handle(),
             **xg_args, **self._tile_args(p.device),
         )
@@ -325,19 +295,21 @@ class FusedMLPKernel:
         kernel's 2-layer nets (any 2..8 ranks), or the 3x128 block kernel (csrc/mlp_block5.hip:
         reduce-scatter + all-gather with sharded Adam or the one-hop exchange, 2 .. 8 ranks; ``world=None`` asks whether
         some world size qualifies).  Never with the batch-tiled trainer (batch > 16)."""
-        if batch > 16 or self.plan.use_tile:
-            return False
-        if len(self.dims) == 3 and self.plan.use_wave and self.xg_slab_granules() > 0:
-            return 1 <= batch <= min(self.bmax, 8)
-        return self._block5_bytes(batch, world if world is not None else 2) > 0
+        return self._xg_trainer(batch, world if world is not None else 2) != "none"
+
+    def _xg_trainer(self, batch: int, world: int) -> str:
+        """The trainer of this plan's train-mode exchange launches at ``world`` ranks ("none": refused)."""
+        if not 1 <= batch <= self.bmax or world < 2:
+            return "none"
+        return self.plan.trainer(int(batch), world=int(world))
 
     def _block5_bytes(self, batch: int, world: int) -> int:
-        if self.plan.use_wave or len(self.dims) != 4 or batch > self.bmax:
+        if self._xg_trainer(batch, world) not in BLOCK5_TRAINERS:
             return 0
         return int(native().mlp_block5_xg_bytes(list(self.dims), int(batch), int(world)))
 
     def xg_buffer_bytes(self, world: int, batch: int = 4) -> int:
-        if self.plan.use_wave:
+        if self._xg_trainer(batch, world) in WAVE_TRAINERS:
             return 2 * world * self.xg_slab_granules() * 8
         return self._block5_bytes(batch, world)
 

@@ -65,6 +65,7 @@ def _train(monkeypatch, env, shape, dropout, loss, wd):
     p, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
     losses = torch.zeros(STEPS, device=p0.device)
     k = FusedMLPKernel(dims, bmax=4)  # (re-reads the knobs)
+    assert k.plan.trainer(B) == ("lds" if env.get("DCT_MLP_BLOCK") == "0" else "block5")  # the kernel under test
     for first, n in ((0, FIRST), (FIRST, STEPS - FIRST)):
         k.train(p, m, v, X, Y, idx[first * B:], n_items=n_items - first * B, batch=B, steps=n, t0=first, lr=0.01,
                 weight_decay=wd, dropout=dropout, seed=3, step_base=first, loss=loss, loss_out=losses[first:])

@@ -80,6 +80,7 @@ def _train(monkeypatch, env, shape, split, dropout, loss, wd):
     p, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
     losses = torch.zeros(steps, device=p0.device)
     k = FusedMLPKernel(dims, bmax=4)  # (re-reads the knobs)
+    assert k.plan.trainer(B) == ("lds" if env.get("DCT_MLP_BLOCK") == "0" else "block5")  # the kernel under test
     first = 0
     for n in launches:
         k.train(p, m, v, X, Y, idx[first * B:n_items], n_items=n_items - first * B, batch=B, steps=n, t0=first, lr=0.01,

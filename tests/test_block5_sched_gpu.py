@@ -49,6 +49,7 @@ def _train(monkeypatch, env, data, dims, B, n_items, launches, dropout, loss, wd
     p, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
     losses = torch.zeros(steps, device=p0.device)
     k = FusedMLPKernel(dims, bmax=4)  # (re-reads the knobs)
+    assert k.plan.trainer(B) == ("lds" if env.get("DCT_MLP_BLOCK") == "0" else "block5")  # the kernel under test
     for first, n, t0, sbase in launches:
         k.train(p, m, v, X, Y, idx[first * B:], n_items=n_items - first * B, batch=B, steps=n, t0=t0, lr=0.01,
                 weight_decay=wd, dropout=dropout, seed=3, step_base=sbase, loss=loss, loss_out=losses[first:])

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 import dct_amd  # noqa: F401
 from dct_amd.ops._native import native
-from dct_amd.ops.fused_mlp import FusedMLPKernel, mlp_num_params, wave_supported
+from dct_amd.ops.fused_mlp import FusedMLPKernel, mlp_num_params
 from test_mlp_tile_gpu import _check_against_torch  # the project's trajectory bounds, shared
 
 pytestmark = pytest.mark.gpu
@@ -152,31 +152,32 @@ WAVE_GRAD = [([5, 64, 2], 4, NO_ENV), ([5, 64, 2], 3, NO_ENV), ([7, 20, 2], 8, N
 LDS_GRAD = [([5, 64, 2], 16, NO_ENV), ([7, 20, 2], 9, NO_ENV), ([12, 40, 4], 6, LDS), ([16, 32, 48, 32, 3], 16, NO_ENV),
             ([5, 128, 128, 2], 4, BLOCK0)]
 BLOCK3_GRAD = [([7, 128, 128, 2], 4, BLOCK3), ([30, 128, 128, 3], 3, BLOCK3)]
-BLOCK5_GRAD = [([5, 128, 128, 2], 4, NO_ENV), ([5, 128, 128, 2], 3, NO_ENV), ([8, 128, 128, 2], 1, NO_ENV),
-               ([1, 128, 128, 2], 2, NO_ENV), ([5, 128, 128, 2], 8, NO_ENV), ([3, 128, 128, 2], 7, NO_ENV)]
+BLOCK5_GRAD = [([5, 128, 128, 2], 4, NO_ENV, "block5"), ([5, 128, 128, 2], 3, NO_ENV, "block5"),
+               ([8, 128, 128, 2], 1, NO_ENV, "block5"), ([1, 128, 128, 2], 2, NO_ENV, "block5"),
+               ([5, 128, 128, 2], 8, NO_ENV, "block5_b8"), ([3, 128, 128, 2], 7, NO_ENV, "block5_b8")]
 TILE_GRAD = [([5, 64, 2], 17, NO_ENV), ([5, 128, 128, 2], 33, NO_ENV), ([5, 128, 128, 2], 100, NO_ENV),
              ([7, 48, 32, 3], 65, NO_ENV), ([7, 32, 48, 3], 40, NO_ENV), ([32, 128, 128, 4], 17, NO_ENV)]
 
 
-def _check_plan(k, B, family):
-    """The launcher's rule (csrc/bindings.cpp launch_train): tile plan, else the wave kernels where the
-    plan is a wave plan and they take this batch, else the LDS trainer and its 3x128 block kernels.
-
-    The plan does not say which of the LDS trainer, mlp_block3, mlp_block5 and mlp_block5_b8 a launch
-    reaches: "lds" and "block" assert the same here.  That the BLOCK3 / BLOCK5 cases run the kernel they
-    are labelled with rests on dct_mlp_train's dispatch (csrc/mlp_fused.hip) and on mlp_block5_ok /
-    mlp_block3_ok accepting these shapes (H = 128 twice, woff[1] % 4 == 0, dims[0] <= 8 and 2 classes for
-    block5, dims[0] <= 32 and <= 4 classes for block3, batch <= 8 / <= 4, DCT_MLP_BLOCK as set per case).
-    A change to those checks that refused one of these shapes would quietly turn its case into a test of
-    the generic LDS trainer: revisit the case lists with such a change."""
-    wave = bool(k.plan.use_wave) and not k.plan.use_tile and wave_supported(k.dims, B)
-    assert wave == (family == "wave"), family
-    assert bool(k.plan.use_tile) == (family == "tile"), family
+def _check_plan(k, B, trainer, mode):
+    """The plan names the trainer this case's launch reaches (csrc/mlp_select.h): the kernel under test."""
+    assert k.plan.trainer(B, mode=mode) == trainer
 
 
-def _grad_case(dims, B, n_items, env, loss, family, cuda, monkeypatch):
+FAMILY = {"wave_single": "wave", "wave_rows": "wave", "block5": "block", "block5_b8": "block", "block3": "block",
+          "lds": "lds", "tile": "tile"}
+
+
+def _ids(params, family=False):
+    """Ids of (dims, B, [n_items,] env, trainer) cases: those they had before they named their trainer (with
+    ``family``, when they named a kernel family), so a case's history stays under one id."""
+    return ["-".join(["dims%d" % i] + [str(x) for x in p[1:-2]] + ["env%d" % i] + ([FAMILY[p[-1]]] if family else []))
+            for i, p in enumerate(params)]
+
+
+def _grad_case(dims, B, n_items, env, loss, trainer, cuda, monkeypatch):
     k = _kernel(dims, B, env, monkeypatch)
-    _check_plan(k, B, family)
+    _check_plan(k, B, trainer, mode=1)
     X, Y, idx, net, _, (want, want_loss) = _build(dims, B, n_items, k, _one_step_reference(n_items, loss))
     P = mlp_num_params(dims)
     p = _flat(net).to(cuda)
@@ -192,10 +193,13 @@ def _grad_case(dims, B, n_items, env, loss, family, cuda, monkeypatch):
     assert lerr < LOSS_TOL, lerr
 
 
+BLOCK5_GRAD_CASES = [c + (t,) for d, b, e, t in BLOCK5_GRAD for c in _with_siblings([(d, b, e)])]
+
+
 @pytest.mark.parametrize("loss", ["ce", "mse"])
 @pytest.mark.parametrize("dims,B,n_items,env", _with_siblings(WAVE_GRAD))
 def test_wave_grad_mode_matches_fp64_under_host_mask(dims, B, n_items, env, loss, cuda, monkeypatch):
-    _grad_case(dims, B, n_items, env, loss, "wave", cuda, monkeypatch)
+    _grad_case(dims, B, n_items, env, loss, "wave_single", cuda, monkeypatch)
 
 
 @pytest.mark.parametrize("loss", ["ce", "mse"])
@@ -207,13 +211,13 @@ def test_lds_grad_mode_matches_fp64_under_host_mask(dims, B, n_items, env, loss,
 @pytest.mark.parametrize("loss", ["ce", "mse"])
 @pytest.mark.parametrize("dims,B,n_items,env", _with_siblings(BLOCK3_GRAD))
 def test_block3_grad_mode_matches_fp64_under_host_mask(dims, B, n_items, env, loss, cuda, monkeypatch):
-    _grad_case(dims, B, n_items, env, loss, "block", cuda, monkeypatch)
+    _grad_case(dims, B, n_items, env, loss, "block3", cuda, monkeypatch)
 
 
 @pytest.mark.parametrize("loss", ["ce", "mse"])
-@pytest.mark.parametrize("dims,B,n_items,env", _with_siblings(BLOCK5_GRAD))
-def test_block5_grad_mode_matches_fp64_under_host_mask(dims, B, n_items, env, loss, cuda, monkeypatch):
-    _grad_case(dims, B, n_items, env, loss, "block", cuda, monkeypatch)
+@pytest.mark.parametrize("dims,B,n_items,env,trainer", BLOCK5_GRAD_CASES, ids=_ids(BLOCK5_GRAD_CASES))
+def test_block5_grad_mode_matches_fp64_under_host_mask(dims, B, n_items, env, trainer, loss, cuda, monkeypatch):
+    _grad_case(dims, B, n_items, env, loss, trainer, cuda, monkeypatch)
 
 
 @pytest.mark.parametrize("loss", ["ce", "mse"])
@@ -225,16 +229,17 @@ def test_tile_grad_mode_matches_fp64_under_host_mask(dims, B, n_items, env, loss
 # ------------------------------------------------------------------ b. train mode, one step from zero moments
 ROWS_TRAIN = [([5, 64, 2], 4, NO_ENV), ([5, 64, 2], 8, NO_ENV), ([5, 64, 2], 3, NO_ENV), ([8, 48, 3], 5, NO_ENV),
               ([16, 64, 4], 2, NO_ENV)]
-OTHER_TRAIN = [([5, 128, 128, 2], 4, NO_ENV, "block"), ([5, 128, 128, 2], 8, NO_ENV, "block"),
-               ([5, 128, 128, 2], 4, BLOCK3, "block"), ([5, 64, 2], 16, NO_ENV, "lds"),
+OTHER_TRAIN = [([5, 128, 128, 2], 4, NO_ENV, "block5"), ([5, 128, 128, 2], 8, NO_ENV, "block5_b8"),
+               ([5, 128, 128, 2], 4, BLOCK3, "block3"), ([5, 64, 2], 16, NO_ENV, "lds"),
                ([5, 128, 128, 2], 33, NO_ENV, "tile")]
+OTHER_TRAIN_CASES = [c + (t,) for d, b, e, t in OTHER_TRAIN for c in _with_siblings([(d, b, e)])]
 
 
-def _train_step_case(dims, B, n_items, env, loss, family, cuda, monkeypatch):
+def _train_step_case(dims, B, n_items, env, loss, trainer, cuda, monkeypatch):
     """After one Adam step from m = v = 0 without weight decay, m / (1 - beta1) is the gradient and
     sqrt(v / (1 - beta2)) its magnitude."""
     k = _kernel(dims, B, env, monkeypatch)
-    _check_plan(k, B, family)
+    _check_plan(k, B, trainer, mode=0)
     X, Y, idx, net, _, (want, want_loss) = _build(dims, B, n_items, k, _one_step_reference(n_items, loss))
     p = _flat(net).to(cuda)
     m, v = torch.zeros_like(p), torch.zeros_like(p)
@@ -261,15 +266,14 @@ def _train_step_case(dims, B, n_items, env, loss, family, cuda, monkeypatch):
 @pytest.mark.parametrize("loss", ["ce", "mse"])
 @pytest.mark.parametrize("dims,B,n_items,env", _with_siblings(ROWS_TRAIN))
 def test_rows_kernel_train_step_matches_fp64_under_host_mask(dims, B, n_items, env, loss, cuda, monkeypatch):
-    assert len(dims) == 3 and B <= 8  # wave_rows_x0's launches (csrc/mlp_wave_impl.h rows_eligible)
-    _train_step_case(dims, B, n_items, env, loss, "wave", cuda, monkeypatch)
+    assert len(dims) == 3 and B <= 8  # wave_rows_x0's launches (csrc/mlp_wave.hip mlp_wave_rows_takes)
+    _train_step_case(dims, B, n_items, env, loss, "wave_rows", cuda, monkeypatch)
 
 
 @pytest.mark.parametrize("loss", ["ce", "mse"])
-@pytest.mark.parametrize("dims,B,n_items,env,family",
-                         [c + (f,) for d, b, e, f in OTHER_TRAIN for c in _with_siblings([(d, b, e)])])
-def test_train_step_matches_fp64_under_host_mask(dims, B, n_items, env, family, loss, cuda, monkeypatch):
-    _train_step_case(dims, B, n_items, env, loss, family, cuda, monkeypatch)
+@pytest.mark.parametrize("dims,B,n_items,env,trainer", OTHER_TRAIN_CASES, ids=_ids(OTHER_TRAIN_CASES, family=True))
+def test_train_step_matches_fp64_under_host_mask(dims, B, n_items, env, trainer, loss, cuda, monkeypatch):
+    _train_step_case(dims, B, n_items, env, loss, trainer, cuda, monkeypatch)
 
 
 # ------------------------------------------------------------------ c. trajectories
@@ -310,17 +314,19 @@ def _check_trajectory(p, m, v, losses, ref, ref_losses, ref_m, ref_v):
     _check_against_torch(p, m, v, losses, ref.net, ref_losses.float(), ref_m.float(), ref_v.float())
 
 
+TRAJECTORIES = [([5, 64, 2], 4, NO_ENV, "wave_rows"), ([9, 48, 64, 3], 4, NO_ENV, "wave_single"),
+                ([5, 128, 128, 2], 4, NO_ENV, "block5"), ([5, 128, 128, 2], 8, NO_ENV, "block5_b8"),
+                ([5, 128, 128, 2], 4, BLOCK3, "block3")]
+
+
 @pytest.mark.parametrize("loss", ["ce", "mse"])
-@pytest.mark.parametrize("dims,B,env,family", [([5, 64, 2], 4, NO_ENV, "wave"), ([9, 48, 64, 3], 4, NO_ENV, "wave"),
-                                               ([5, 128, 128, 2], 4, NO_ENV, "block"),
-                                               ([5, 128, 128, 2], 8, NO_ENV, "block"),
-                                               ([5, 128, 128, 2], 4, BLOCK3, "block")])
-def test_trajectory_matches_fp64_adam_under_host_mask(dims, B, env, family, loss, cuda, monkeypatch):
+@pytest.mark.parametrize("dims,B,env,trainer", TRAJECTORIES, ids=_ids(TRAJECTORIES, family=True))
+def test_trajectory_matches_fp64_adam_under_host_mask(dims, B, env, trainer, loss, cuda, monkeypatch):
     """7 steps in two launches (3, then 4 at t0 = step_base = 3), the last batch partial: [5,64,2] runs
     wave_rows_x0, [9,48,64,3] the single-wave kernel, 3x128 mlp_block5 (B = 8: mlp_block5_b8) or mlp_block3."""
     n_items = (STEPS - 1) * B + B - 1
     k = _kernel(dims, B, env, monkeypatch)
-    _check_plan(k, B, family)
+    _check_plan(k, B, trainer, mode=0)
     X, Y, idx, net, ref, want = _build(dims, B, n_items, k, _adam_reference(B, n_items, 0, loss))
     p = _flat(net).to(cuda)
     m, v = torch.zeros_like(p), torch.zeros_like(p)
@@ -339,7 +345,7 @@ def test_bound_train_mask_step_follows_the_device_counter(cuda, monkeypatch):
     dims, B, first_gstep = [5, 64, 2], 4, 9
     n_items = (STEPS - 1) * B + B - 1
     k = _kernel(dims, B, NO_ENV, monkeypatch)
-    _check_plan(k, B, "wave")
+    _check_plan(k, B, "wave_rows", mode=0)
     X, Y, idx, net, ref, want = _build(dims, B, n_items, k, _adam_reference(B, n_items, first_gstep, "ce"))
     p = _flat(net).to(cuda)
     m, v = torch.zeros_like(p), torch.zeros_like(p)

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 import dct_amd  # noqa: F401
 from dct_amd.ops._native import native
 from dct_amd.ops.fused_mlp import FusedMLPKernel, mlp_num_params, reference_mlp_forward
+from test_mlp_select_cpu import KERNELS_GRAD, KERNELS_TRAIN  # (dims, B, the trainer under each of KERNELS)
 
 pytestmark = pytest.mark.gpu
 
@@ -69,6 +70,11 @@ def test_native_loaded_and_arch():
 KERNELS = ["auto", "lds", "lds-noblock", "lds-b3"]
 
 
+def _promised_trainer(table, dims, B, kernel):
+    """The trainer the selector's table (tests/test_mlp_select_cpu.py) derives for this shape and variant."""
+    return {(tuple(d), b): w for d, b, w in table}[(tuple(dims), B)][KERNELS.index(kernel)]
+
+
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("loss", ["ce", "mse"])
 @pytest.mark.parametrize("dims,B", [([5, 64, 2], 4), ([5, 128, 128, 2], 4), ([5, 64, 2], 3), ([9, 48, 64, 3], 4),
@@ -93,6 +99,7 @@ def test_fused_train_matches_torch_adam(dims, B, loss, kernel, cuda, monkeypatch
     steps = math.ceil(n_items / B)
     losses = torch.zeros(steps, device=cuda)
     k = FusedMLPKernel(dims, bmax=4 if B <= 4 else 16)
+    assert k.plan.trainer(B, mode=0, steps=steps) == _promised_trainer(KERNELS_TRAIN, dims, B, kernel)
     k.train(p, m, v, X.to(cuda), Y.to(cuda, torch.int32), idx.to(cuda, torch.int32), n_items=n_items, batch=B,
             steps=steps, t0=0, lr=0.01, loss=loss, loss_out=losses)
     opt = torch.optim.Adam(net.parameters(), lr=0.01)
@@ -163,6 +170,7 @@ def test_fused_grad_mode_matches_autograd(dims, B, kernel, cuda, monkeypatch):
     P = mlp_num_params(dims)
     g = torch.zeros(P + 1, device=cuda)
     k = FusedMLPKernel(dims, bmax=4 if B <= 4 else 16)
+    assert k.plan.trainer(B, mode=1) == _promised_trainer(KERNELS_GRAD, dims, B, kernel)
     k.train(p, None, None, X.to(cuda), Y.to(cuda, torch.int32), idx.to(cuda), n_items=B, batch=B, steps=1, t0=0,
             lr=0.01, grad_out=g)
     l = F.cross_entropy(net(X[:B]), Y[:B]) if dims[-1] > 1 else F.cross_entropy(net(X[:B]), Y[:B] * 0)
@@ -228,6 +236,7 @@ def test_block5_two_micro_batch_kernel_equals_one_at_batch4(dropout, loss, cuda,
         p, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
         losses = torch.zeros(steps, device=cuda)
         k = FusedMLPKernel(dims, bmax=4)
+        assert k.plan.trainer(B) == {"-1": "block5", "8": "block5_b8"}[blk]
         for first, n in ((0, 17), (17, steps - 17)):  # two launches: the epilogue / prologue round trip too
             k.train(p, m, v, X, Y, idx[first * B:], n_items=n_items - first * B, batch=B, steps=n, t0=first, lr=0.01,
                     dropout=dropout, seed=3, step_base=first, loss=loss, loss_out=losses[first:])

@@ -64,7 +64,7 @@ def test_mlp_plan_reloads_knobs(nat, monkeypatch):
 
 
 def test_block_choice_is_a_plan_time_copy(nat, monkeypatch):
-    """the 3x128 launch path (dct_mlp_train, mlp_block3_ok) reads DCT_MLP_BLOCK from the
+    """the 3x128 launch path (mlp_select_trainer) reads DCT_MLP_BLOCK from the
     plan's own copy, stamped when the MlpPlan is built - a later reload of the process-wide knobs does not
     change an existing plan's launches."""
     monkeypatch.setenv("DCT_MLP_BLOCK", "3")
