@@ -19,7 +19,8 @@ struct Knobs {
                             // test and of same-binary A/Bs), 1 the default one; B5_SCHED_AB_BASE + mask: one of
                             // the item masks an A/B build (-DB5_SCHED_AB) carries, the default schedule elsewhere
                             // (round 10's candidate masks outgrew the earlier 256 + mask; round 11's items are the
-                            // bits 128 .. 2048, so the default mask is 4067 and every mask stays below 4096)
+                            // bits 128 .. 2048 and round 12's 4096 .. 16384, so the default mask is 32739 and
+                            // every mask stays below 32768)
   // wide-MLP step executor (mlp_executor.cpp; copied into each executor at construction)
   int fused_head = 1;       // DCT_FUSED_HEAD=0: the four-kernel head chain
   int dw_into_adam = 1;     // DCT_DW_INTO_ADAM=0: dW through g and the reduce pass
@@ -36,7 +37,7 @@ struct Knobs {
 };
 
 constexpr int MLP_BLOCK_TILE = 32;
-constexpr int B5_SCHED_AB_BASE = 4096;  // DCT_B5_SCHED of an A/B build: B5_SCHED_AB_BASE + item mask (< 4096)
+constexpr int B5_SCHED_AB_BASE = 32768;  // DCT_B5_SCHED of an A/B build: B5_SCHED_AB_BASE + item mask (< 32768)
 
 const Knobs& knobs();
 void knobs_reload();

@@ -55,7 +55,9 @@ size_t mlp_block5_xg_bytes(int world) {
 // one-rank batch <= 4 train launch under the step schedule DCT_B5_SCHED selects (knobs.h): 0 the
 // previous schedule, anything else the default one.  An A/B build (-DB5_SCHED_AB) also carries, for the
 // headline variant (CE, no weight decay), round 10's default, that default plus each of round 11's
-// items alone, and the default without the prefetch item (which passes only beside the others):
+// items alone, round 11's default without the prefetch item (which passes only beside the others),
+// round 11's default, that default plus each of round 12's items alone, and the default without SCH_INV_BS
+// (which passes only beside the other two):
 // B5_SCHED_AB_BASE + mask.  A round's candidate items go into this list.
 template <bool WD, int LK, bool PROF = false>
 static void b5_launch_sched(int sched, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
@@ -64,9 +66,10 @@ static void b5_launch_sched(int sched, size_t bytes, hipStream_t st, const MlpSh
 #ifdef B5_SCHED_AB
   if constexpr (!WD && LK == 0 && !PROF) {
     constexpr int D = SCHED_DEFAULT;
-    constexpr int R = SCHED_R10;
+    constexpr int R = SCHED_R10, E = SCHED_R11;
     constexpr int masks[] = {R, R | SCH_PF_W0, R | SCH_ADAM_SM, R | SCH_DZ2F, R | SCH_DROP_INT, R | SCH_DB2,
-                             D & ~SCH_PF_W0};
+                             E & ~SCH_PF_W0,
+                             E, E | SCH_LOGIT_RS, E | SCH_INV_BS, E | SCH_ADAM_B02, D & ~SCH_INV_BS};
     bool done = false;
     b5x::static_for<sizeof(masks) / sizeof(masks[0])>([&](auto i) {
       constexpr int M = masks[decltype(i)::value];

@@ -116,8 +116,29 @@ constexpr int SCH_PRIO_LAT = 64;
 //               same association - and one row rotation, instead of two exec-masked blocks of readlane sums
 constexpr int SCH_PF_W0 = 128, SCH_ADAM_SM = 256, SCH_DZ2F = 512, SCH_DROP_INT = 1024, SCH_DB2 = 2048;
 constexpr int SCHED_R10 = SCH_DROP | SCH_ADAM_TAB | SCH_WTB | SCH_PRIO_LAT;  // round 10's default
-constexpr int SCHED_DEFAULT = SCHED_R10 | SCH_PF_W0 | SCH_ADAM_SM | SCH_DZ2F | SCH_DROP_INT | SCH_DB2;
-static_assert(SCHED_DEFAULT < 4096, "item masks stay below B5_SCHED_AB_BASE (knobs.h)");
+constexpr int SCHED_R11 = SCHED_R10 | SCH_PF_W0 | SCH_ADAM_SM | SCH_DZ2F | SCH_DROP_INT | SCH_DB2;  // round 11's
+// Round 12: the same lever on what round 11 left (same operations in the same order on every value).
+//   LOGIT_RS    the two logit shares as a reduce-scatter over lane bits 2..5 instead of two all-reduces of which
+//               only class cb = lane bit 2 is stored: lane i - 4 has the opposite bit 2, so row_ror:4 delivers
+//               exactly the class lane i keeps, every later partner agrees on bit 2, and each level adds the
+//               two operands it added before (the first level as the compiler fuses it in sum_bits2to5: the lane's
+//               own product inside an fma, the neighbour's rounded)
+//   INV_BS      1 / bs once per launch for bs = B (the same v_cvt + v_rcp on the same value, held in an SGPR);
+//               the per-step form only behind a scalar bs != B branch (a dataset's last batch), and wave 0's
+//               batch loss takes the same value instead of evaluating it again
+//   ADAM_B02    b0[u] and b2 (the two remaining adam_scaled calls) as one 64-bit triple updated in place by
+//               adam_v2r at the dW0 / db0 tail: packed moment / denominator / parameter updates, two square roots
+//               and two reciprocals (adam_v2's shared reciprocal is not the bits of rcp(d)); b2 is published
+//               there, still in front of the next barrier A
+// Measured and not kept (profiles/b5_lean2_ab_r12.log): packed fp32 where the operands
+// already sit in aligned pairs - F1's four row products over the two 16-byte input tiles (-2 after the copies
+// of W0's odd half it needs), dZ2's two-class products and factor multiply over row pairs (-12) - each fails
+// alone and makes the kept items slower (dZ2: 3.16 -> 3.21 us/step); dZ1's acc[0] + acc[1] as packed adds (-8;
+// the results must sit in aligned pairs, 251 -> 256 VGPRs, the weight-decay instantiations spill); W1 Adam's
+// addend E from ADAM_SM's VGPR (the splat is marshalled into a pair again, no instruction fewer).
+constexpr int SCH_LOGIT_RS = 4096, SCH_INV_BS = 8192, SCH_ADAM_B02 = 16384;
+constexpr int SCHED_DEFAULT = SCHED_R11 | SCH_LOGIT_RS | SCH_INV_BS | SCH_ADAM_B02;
+static_assert(SCHED_DEFAULT < 32768, "item masks stay below B5_SCHED_AB_BASE (knobs.h)");
 }  // namespace blk5
 
 // ---- data parallelism inside the persistent launch (XW = 2 / 4 / 8 ranks, one per GPU) ---------
@@ -308,6 +329,17 @@ __device__ __forceinline__ void adam_v2(v2f& p, v2f g, v2f& m, v2f& v, float b1,
   const float R = __builtin_amdgcn_rcpf(d.x * d.y);
   p = p - m * ((v2f){d.y, d.x} * R);
 }
+// SCH_ADAM_B02: two bku::adam_scaled updates held as one pair - component-wise adam_scaled's sequence,
+// each parameter with its own reciprocal
+template <bool WD>
+__device__ __forceinline__ void adam_v2r(v2f& p, v2f g, v2f& m, v2f& v, float b1, float b2, float wd, float A, float E) {
+  if constexpr (WD) g = (v2f)(wd) * p + g;
+  m = (v2f)(b1) * m + g;
+  v = (v2f)(b2) * v + g * g;
+  const v2f sq = (v2f){__builtin_amdgcn_sqrtf(v.x), __builtin_amdgcn_sqrtf(v.y)};
+  const v2f d = sq * (v2f)(A) + (v2f)(E);
+  p = p - m * (v2f){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+}
 
 // MB: micro-batches of B = 4 rows per step (MB = 2: per-rank batch 5..8): every micro-batch runs the
 // forward and backward of its four rows on the same lanes (rows r0 + 4 mb), its gradients accumulate
@@ -334,6 +366,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   constexpr bool S_PLAT = (SCH & SCH_PRIO_LAT) != 0;
   constexpr bool S_PF = (SCH & SCH_PF_W0) != 0, S_SM = (SCH & SCH_ADAM_SM) != 0, S_DZF = (SCH & SCH_DZ2F) != 0;
   constexpr bool S_DINT = (SCH & SCH_DROP_INT) != 0, S_DB2 = (SCH & SCH_DB2) != 0;
+  constexpr bool S_LRS = (SCH & SCH_LOGIT_RS) != 0, S_INVB = (SCH & SCH_INV_BS) != 0, S_B02 = (SCH & SCH_ADAM_B02) != 0;
+  constexpr bool S_EV = S_SM || S_B02;  // the step's E in a VGPR
   using LY = Lds<MB>;
   constexpr int RB = LY::RB, XT = LY::XT, LAB = LY::LAB, MSK = LY::MSK, LOGP = LY::LOGP, H1W = LY::H1W;
   constexpr int H1X = LY::H1X, PART = LY::PART, W2L = LY::W2L, B2L = LY::B2L, ABT = LY::ABT, TOTAL = LY::TOTAL;
@@ -533,6 +567,12 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   const v2f z2 = (v2f){0.f, 0.f};
   v2f PSm = S_SM ? (v2f){0.f, pb1} : z2, MSm = S_SM ? (v2f){mw2, mb1} : z2, VSm = S_SM ? (v2f){vw2, vb1} : z2;
   v2f PW0 = S_SM ? (v2f){w0[0], w0[1]} : z2, MW0 = S_SM ? (v2f){m0[0], m0[1]} : z2, VW0 = S_SM ? (v2f){v0[0], v0[1]} : z2;
+  // SCH_ADAM_B02: {b0[u], b2} the same way
+  v2f PB02 = S_B02 ? (v2f){pb0, pb2} : z2, MB02 = S_B02 ? (v2f){mb0, mb2} : z2, VB02 = S_B02 ? (v2f){vb0, vb2} : z2;
+  // SCH_INV_BS: 1 / B as every full batch's step evaluates it, wave-uniform in a scalar register
+  const uint32_t inv_bsz = S_INVB ? __builtin_amdgcn_readfirstlane(
+                                        __float_as_uint(__builtin_amdgcn_rcpf((float)(Bsz > 0 ? Bsz : 1))))
+                                  : 0u;
   // ---- XW > 1: the moments of the owned W1 pairs only (slot t = pair rank + XW t), the exchange's
   // buffer descriptors, this rank's small-pair ownership
   const int xrank = XW > 1 ? (RK >= 0 ? RK : a.xg_rank) : 0;
@@ -706,7 +746,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         const float s0 = qb1 ? acc0 : acc2, s1 = qb1 ? acc1 : acc3;
         const float e0 = k0 + dpp<QP_X2>(s0), e1 = k1 + dpp<QP_X2>(s1);
         const float kq = qb0 ? e1 : e0, sq = qb0 ? e0 : e1;
-        h1 = fmaxf(kq + dpp<QP_X1>(sq) + pb0, 0.f) * f1[hf];
+        h1 = fmaxf(kq + dpp<QP_X1>(sq) + (S_B02 ? PB02.x : pb0), 0.f) * f1[hf];
         h1w[l] = h1;                    // [k = l / 4][row = l % 4]
         h1x[r0 * KS + (l >> 2)] = h1;   // [row][k]
       }
@@ -818,7 +858,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             }
             aA = rl(tabA, ti);
             aE = rl(tabE, ti);
-            if constexpr (S_SM) {  // one VGPR copy for the step's small updates (a v_fma takes one SGPR)
+            if constexpr (S_EV) {  // one VGPR copy for the step's small updates (a v_fma takes one SGPR)
               aEv = aE;
               asm volatile("" : "+v"(aEv));
             }
@@ -827,13 +867,25 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         }
         const float z = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
         h2 = fmaxf(z + (S_SM ? PSm.y : pb1), 0.f) * f2[hf];
-        const float t0s = sum_bits2to5(pw2[0] * h2), t1s = sum_bits2to5(pw2[1] * h2);  // row r0's shares
+        float t0s = 0.f, t1s = 0.f, tcs = 0.f;  // row r0's shares; SCH_LOGIT_RS: only the one of class cb
+        if constexpr (S_LRS) {
+          // sum_bits2to5's first level compiles to fma(w, h2, ror4(w * h2)) - the lane's own product is fused
+          // into the add, the neighbour's is rounded -, so the same here, spelled out
+          const float wk = cb ? pw2[1] : pw2[0], ws = cb ? pw2[0] : pw2[1];
+          const float send = ws * h2;
+          tcs = fmaf(wk, h2, dpp<ROR4>(send));  // lane i - 4: bit 2 flipped, its send is this lane's class
+          tcs += dpp<ROR8>(tcs);
+          tcs = swap16_sum(tcs, tcs);
+          tcs = swap32_sum(tcs, tcs);
+        } else {
+          t0s = sum_bits2to5(pw2[0] * h2), t1s = sum_bits2to5(pw2[1] * h2);
+        }
         if constexpr (S_DZF) {  // [o = u][row r0]: word 64 w + l, one linear store per wave
           lds[LY::DZF + mpar * (H * 4) + u * 4 + r0] = h2 > 0.f ? scale : 0.f;
-          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = cb ? t1s : t0s;  // [wave][class][row]
+          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = S_LRS ? tcs : (cb ? t1s : t0s);  // [wave][class][row]
         } else {
           const unsigned long long msk = __ballot(h2 > 0.f);
-          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = cb ? t1s : t0s;  // [wave][class][row]
+          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = S_LRS ? tcs : (cb ? t1s : t0s);  // [wave][class][row]
           if (l == 0)
             *reinterpret_cast<uint2*>(lds + MSK + mpar * (NW * 2) + w * 2) = make_uint2((uint32_t)msk, (uint32_t)(msk >> 32));
         }
@@ -868,6 +920,13 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         __builtin_amdgcn_sched_barrier(0);
       }
       float lv;
+      uint32_t inv_bs = inv_bsz;  // SCH_INV_BS: 1 / bs of this step
+      if constexpr (S_INVB) {
+        if (bs != Bsz) {  // wave-uniform: a dataset's last batch
+          asm volatile("");  // a real branch: if-converted, the conversion and the reciprocal run every step
+          inv_bs = __builtin_amdgcn_readfirstlane(__float_as_uint(__builtin_amdgcn_rcpf((float)(bs > 0 ? bs : 1))));
+        }
+      }
       {
         float lg = HB > 0 ? lg0 : lds[LOGP + mpar * (NW * 8) + l];
         lg += dpp<ROR8>(lg);          // shares w', w' ^ 1 (lane bit 3)
@@ -877,7 +936,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         const float zo = dpp<ROR4>(z);  // the other class of the same row (lane bit 2 flipped in the
                                         // row-replicated copies)
         const bool live = r0 + B * hf < bs;
-        const float invb = __builtin_amdgcn_rcpf((float)(bs > 0 ? bs : 1));
+        const float invb = S_INVB ? __uint_as_float(inv_bs) : __builtin_amdgcn_rcpf((float)(bs > 0 ? bs : 1));
         const float inv = live ? invb : 0.f;
         const float y = (cb == lab) ? 1.f : 0.f;
         if constexpr (LK == 0) {
@@ -906,7 +965,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         tl += dpp<ROR4>(tl);
         tls = hf == 0 ? tl : tls + tl;
         if (last) {
-          const float bl = bs > 0 ? tls * __builtin_amdgcn_rcpf((float)bs) : 0.f;
+          // (SCH_INV_BS: bs > 0 makes the loss block's operand (float)bs too)
+          const float bl = bs > 0 ? tls * (S_INVB ? __uint_as_float(inv_bs) : __builtin_amdgcn_rcpf((float)bs)) : 0.f;
           if constexpr (ADAM && XW > 1) {
             // sync_dist: one granule to every peer now, the rank-ordered mean after the all-gather
             xbl = rl(bl, 0);
@@ -930,7 +990,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         const float rss = __builtin_amdgcn_rcpf(step_size);
         aA = sqc2 * rbc2 * rss * rc1;
         aE = a.eps * rss * rc1;
-        if constexpr (S_SM) aEv = aE;
+        if constexpr (S_EV) aEv = aE;
       }
       // ---- dZ2 of outputs o = l + 64 j, the micro-batch's rows (old W2, mask bits of the owning wave)
       if constexpr (S_DZF) {
@@ -1010,8 +1070,10 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             pw2[0] = dpp<QB0>(pown);
             pw2[1] = dpp<QB1>(pown);
             if (own_w2) lds[W2L + nbuf * (H * C) + u * C + r0] = pown;
-            adam_scaled<WD>(pb2, gb, mb2, vb2, a.b1, a.b2, a.wd, aA, S_SM ? aEv : aE);
-            if (own_b2) lds[B2L + nbuf * 4 + l] = pb2;
+            if constexpr (!S_B02) {  // (SCH_ADAM_B02: with b0 at the dW0 / db0 tail)
+              adam_scaled<WD>(pb2, gb, mb2, vb2, a.b1, a.b2, a.wd, aA, S_SM ? aEv : aE);
+              if (own_b2) lds[B2L + nbuf * 4 + l] = pb2;
+            }
           } else {  // grad mode (one step): dW2[r0][u], db1[u], db2 to the flat gradient
             if (own_w2) a.grad_out[fw2] = gown;
             if (r0 == 0) a.grad_out[bo1 + u] = gb1s;
@@ -1098,7 +1160,12 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
               adam_v2<WD>(PW0, (v2f){g0, g1}, MW0, VW0, a.b1, a.b2, a.wd, aA, aEv);
             else
               adam_pair<WD>(w0[0], g0, m0[0], v0[0], w0[1], g1, m0[1], v0[1], a.b1, a.b2, a.wd, aA, aE);  // d >= D0: stays 0
-            adam_scaled<WD>(pb0, db0s, mb0, vb0, a.b1, a.b2, a.wd, aA, S_SM ? aEv : aE);
+            if constexpr (S_B02) {  // {b0[u], b2}; b2 published for the next step's barrier A
+              adam_v2r<WD>(PB02, (v2f){db0s, gbs}, MB02, VB02, a.b1, a.b2, a.wd, aA, aEv);
+              if (own_b2) lds[B2L + nbuf * 4 + l] = PB02.y;
+            } else {
+              adam_scaled<WD>(pb0, db0s, mb0, vb0, a.b1, a.b2, a.wd, aA, S_SM ? aEv : aE);
+            }
           } else {
             if (r0 < D0) a.grad_out[wo0 + u * D0 + r0] = g0;
             if (r0 + 4 < D0) a.grad_out[wo0 + u * D0 + r0 + 4] = g1;
@@ -1270,6 +1337,9 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   if constexpr (S_SM) {  // the small pairs back to their scalars (the write-back below)
     pb1 = PSm.y; mw2 = MSm.x; mb1 = MSm.y; vw2 = VSm.x; vb1 = VSm.y;
     w0[0] = PW0.x; w0[1] = PW0.y; m0[0] = MW0.x; m0[1] = MW0.y; v0[0] = VW0.x; v0[1] = VW0.y;
+  }
+  if constexpr (S_B02) {
+    pb0 = PB02.x; pb2 = PB02.y; mb0 = MB02.x; mb2 = MB02.y; vb0 = VB02.x; vb2 = VB02.y;
   }
 
   if constexpr (XW > 1) {
