@@ -260,11 +260,16 @@ PYBIND11_MODULE(_dct_native, m) {
       .def_readonly("supported", &MlpPlan::supported)
       .def_readonly("threads", &MlpPlan::nt)
       .def_readonly("max_blocks_per_thread", &MlpPlan::maxblk)
+      .def_property_readonly("block_rows", [](const MlpPlan& p) { return p.sh()->br; })
       .def_readonly("use_wave", &MlpPlan::use_wave)
       .def_readonly("use_tile", &MlpPlan::use_tile)
       .def_property_readonly("num_params", [](const MlpPlan& p) { return p.sh()->P; })
       .def_property_readonly("lds_bytes", [](const MlpPlan& p) { return p.sh()->lds_floats * 4; })
       .def_property_readonly("bmax", [](const MlpPlan& p) { return p.sh()->bmax; })
+      // the evaluation kernel takes this plan's layout (dct_mlp_eval: its LDS budget, 4- or 16-row chunks)
+      .def_property_readonly("eval_fits", [](const MlpPlan& p) {
+        return (size_t)p.sh()->lds_floats * 4 <= dct::MLP_LDS_BUDGET && (p.sh()->bmax == 4 || p.sh()->bmax == 16);
+      })
       .def_property_readonly("mlp_block", [](const MlpPlan& p) { return p.sh()->mlp_block; })
       // the trainer a launch of this description reaches: "wave_single", "wave_rows", "block5", "block5_b8",
       // "block3", "lds", "tile" or "none".  `aligned`: the flat buffers lie on 16-byte boundaries.  No device needed.

@@ -8,6 +8,7 @@
 namespace dct {
 
 constexpr int MLP_MAXL = 4;
+constexpr size_t MLP_LDS_BUDGET = 160 * 1024;  // bytes of LDS one workgroup of the LDS trainer / evaluator may lay out
 
 // Everything a launch needs about one MLP architecture, computed once on the host
 // (dct_mlp_make_shape): LDS layout, per-layer work split of the forward / dX phases and

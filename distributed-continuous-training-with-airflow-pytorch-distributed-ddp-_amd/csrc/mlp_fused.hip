@@ -113,7 +113,7 @@ int mlp_make_shape(MlpShape* sh, const int* dims, int L, int bmax) {
   sh->red_lds = off;
   off += r4(2 * bmax);
   sh->lds_floats = off;
-  sh->supported = (nt > 0) && (nbias <= 2 * nt) && ((size_t)off * 4 <= 160 * 1024) ? 1 : 0;
+  sh->supported = (nt > 0) && (nbias <= 2 * nt) && ((size_t)off * 4 <= MLP_LDS_BUDGET) ? 1 : 0;
   sh->mlp_block = -1;  // auto until the plan stamps its knob copy
   return 0;
 }
@@ -153,7 +153,7 @@ int dct_mlp_lds_train(const void* shape, const MlpArgs* a, void* stream) {
 
 int dct_mlp_eval(const void* shape, const MlpArgs* a, int grid, void* stream) {
   const MlpShape& sh = *reinterpret_cast<const MlpShape*>(shape);
-  if ((size_t)sh.lds_floats * 4 > 160 * 1024) return (int)hipErrorInvalidValue;
+  if ((size_t)sh.lds_floats * 4 > dct::MLP_LDS_BUDGET) return (int)hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   switch (sh.L) {
     case 2: return (int)dct::mlp_launch_eval_L2(sh, *a, grid, st);

@@ -780,15 +780,23 @@ hipError_t launch_train_L(const MlpShape& sh, const MlpArgs& a, hipStream_t st) 
   return hipErrorInvalidValue;
 }
 
-template <int L>
-hipError_t launch_eval_L(const MlpShape& sh, const MlpArgs& a, int grid, hipStream_t st) {
-  if (sh.bmax != 16) return hipErrorInvalidValue;
+template <int L, int BMAX>
+hipError_t launch_eval_inst(const MlpShape& sh, const MlpArgs& a, int grid, hipStream_t st) {
   const size_t bytes = (size_t)sh.lds_floats * sizeof(float);
-  auto fn = mlp_eval_kernel<L, 256, 16>;
+  auto fn = mlp_eval_kernel<L, 256, BMAX>;
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(256), bytes, st, sh, a);
   return hipGetLastError();
+}
+
+// 16-row chunks; 4-row chunks for the shapes whose 16-row layout overflows the LDS budget while
+// their 4-row training plan fits (FusedMLPKernel.eval_plan)
+template <int L>
+hipError_t launch_eval_L(const MlpShape& sh, const MlpArgs& a, int grid, hipStream_t st) {
+  if (sh.bmax == 16) return launch_eval_inst<L, 16>(sh, a, grid, st);
+  if (sh.bmax == 4) return launch_eval_inst<L, 4>(sh, a, grid, st);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace dct

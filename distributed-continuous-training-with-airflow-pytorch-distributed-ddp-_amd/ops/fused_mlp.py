@@ -158,8 +158,15 @@ class FusedMLPKernel:
 
     @property
     def eval_plan(self):
+        """The evaluation kernel's layout: 16-row chunks, or 4-row chunks for the shapes whose 16-row
+        layout overflows the LDS budget (``supported`` accepts those at batch <= 4 on their 4-row plan)."""
         if self._eval_plan is None:
-            self._eval_plan = native().MlpPlan(self.dims, 16)
+            plan = native().MlpPlan(self.dims, 16)
+            if not plan.eval_fits:
+                small = native().MlpPlan(self.dims, 4)
+                if small.eval_fits:
+                    plan = small
+            self._eval_plan = plan
         return self._eval_plan
 
     @staticmethod
@@ -323,11 +330,11 @@ class FusedMLPKernel:
             raise ValueError("acc_out must be cuda fp32 [2]")
         if logits_out is not None and logits_out.numel() < n_items * self.dims[-1]:
             raise ValueError("logits_out too small")
-        chunks = (n_items + 15) // 16
+        plan = self.eval_plan
+        chunks = (n_items + plan.bmax - 1) // plan.bmax
         g = grid or max(1, min(chunks, 256))
-        self.eval_plan.eval(ptr(p), ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), LOSS_KINDS[loss],
-                            ptr(acc_out), ptr(logits_out), int(g),
-                            stream if stream is not None else stream_handle())
+        plan.eval(ptr(p), ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), LOSS_KINDS[loss],
+                  ptr(acc_out), ptr(logits_out), int(g), stream if stream is not None else stream_handle())
 
 
 # the current stream's raw handle without building a torch.cuda.Stream object (one C call); the
