@@ -22,8 +22,8 @@ void knobs_reload() {
   k.mlp_force_lds = (mk && std::strcmp(mk, "lds") == 0) ? 1 : 0;
   if (const char* b = std::getenv("DCT_MLP_BLOCK"))
     k.mlp_block = (std::strcmp(b, "tile") == 0) ? MLP_BLOCK_TILE : (b[0] == '0') ? 0 : (b[0] == '3' ? 3 : (b[0] == '8' ? 8 : -1));
-  k.b5_sched = env_int("DCT_B5_SCHED", -1);
-  if (k.b5_sched < 0 || k.b5_sched >= 2 * B5_SCHED_AB_BASE) k.b5_sched = -1;
+  const char* bs = std::getenv("DCT_B5_SCHED");
+  k.b5_sched = (bs && std::strcmp(bs, "0") == 0) ? 0 : 1;  // exactly "0"; unset or anything else: the default
   k.fused_head = env_int("DCT_FUSED_HEAD", 1) != 0;
   k.dw_into_adam = env_int("DCT_DW_INTO_ADAM", 1) != 0;
   k.reducer_inline = env_int("DCT_REDUCER_INLINE", -2);

@@ -14,13 +14,9 @@ struct Knobs {
   int mlp_block = -1;       // DCT_MLP_BLOCK: -1 auto, 0 generic LDS trainer, 3 force mlp_block3, 8 mlp_block5's
                             // two-micro-batch kernels at every batch (tests: == the one-micro-batch kernels at B <= 4),
                             // MLP_BLOCK_TILE ("tile") the batch-tiled trainer (mlp_tile.hip) at batch <= 16 too
-  int b5_sched = -1;        // DCT_B5_SCHED: mlp_block5's one-rank batch <= 4 train kernels: -1 the default step
-                            // schedule (blk5::SCHED_DEFAULT), 0 the previous one (the reference of the bit-for-bit
-                            // test and of same-binary A/Bs), 1 the default one; B5_SCHED_AB_BASE + mask: one of
-                            // the item masks an A/B build (-DB5_SCHED_AB) carries, the default schedule elsewhere
-                            // (round 10's candidate masks outgrew the earlier 256 + mask; round 11's items are the
-                            // bits 128 .. 2048 and round 12's 4096 .. 16384, so the default mask is 32739 and
-                            // every mask stays below 32768)
+  int b5_sched = 1;         // DCT_B5_SCHED=0: mlp_block5's one-rank batch <= 4 train kernels without the step
+                            // schedule (blk5::SCHED_DEFAULT, csrc/mlp_block5_impl.h): the reference of the
+                            // bit-for-bit test and of same-binary A/Bs.  Unset or anything else: with it
   // wide-MLP step executor (mlp_executor.cpp; copied into each executor at construction)
   int fused_head = 1;       // DCT_FUSED_HEAD=0: the four-kernel head chain
   int dw_into_adam = 1;     // DCT_DW_INTO_ADAM=0: dW through g and the reduce pass
@@ -37,7 +33,6 @@ struct Knobs {
 };
 
 constexpr int MLP_BLOCK_TILE = 32;
-constexpr int B5_SCHED_AB_BASE = 32768;  // DCT_B5_SCHED of an A/B build: B5_SCHED_AB_BASE + item mask (< 32768)
 
 const Knobs& knobs();
 void knobs_reload();

@@ -52,36 +52,12 @@ size_t mlp_block5_xg_bytes(int world) {
   }
 }
 
-// one-rank batch <= 4 train launch under the step schedule DCT_B5_SCHED selects (knobs.h): 0 the
-// previous schedule, anything else the default one.  An A/B build (-DB5_SCHED_AB) also carries, for the
-// headline variant (CE, no weight decay), round 10's default, that default plus each of round 11's
-// items alone, round 11's default without the prefetch item (which passes only beside the others),
-// round 11's default, that default plus each of round 12's items alone, and the default without SCH_INV_BS
-// (which passes only beside the other two):
-// B5_SCHED_AB_BASE + mask.  A round's candidate items go into this list.
+// one-rank batch <= 4 train launch: DCT_B5_SCHED=0 (knobs.h) selects the kernel without the step schedule
+// (the reference of the bit-for-bit test and of same-binary A/Bs), anything else the default
 template <bool WD, int LK, bool PROF = false>
 static void b5_launch_sched(int sched, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
-  using namespace blk5;
-  if (sched == 0) return b5_launch<WD, LK, PROF>(bytes, st, sh, a);
-#ifdef B5_SCHED_AB
-  if constexpr (!WD && LK == 0 && !PROF) {
-    constexpr int D = SCHED_DEFAULT;
-    constexpr int R = SCHED_R10, E = SCHED_R11;
-    constexpr int masks[] = {R, R | SCH_PF_W0, R | SCH_ADAM_SM, R | SCH_DZ2F, R | SCH_DROP_INT, R | SCH_DB2,
-                             E & ~SCH_PF_W0,
-                             E, E | SCH_LOGIT_RS, E | SCH_INV_BS, E | SCH_ADAM_B02, D & ~SCH_INV_BS};
-    bool done = false;
-    b5x::static_for<sizeof(masks) / sizeof(masks[0])>([&](auto i) {
-      constexpr int M = masks[decltype(i)::value];
-      if (!done && sched == B5_SCHED_AB_BASE + M && M != D) {
-        b5_launch<WD, LK, false, true, true, 1, -1, 1, M>(bytes, st, sh, a);
-        done = true;
-      }
-    });
-    if (done) return;
-  }
-#endif
-  b5_launch<WD, LK, PROF, true, true, 1, -1, 1, SCHED_DEFAULT>(bytes, st, sh, a);
+  if (sched == 0) b5_launch<WD, LK, PROF>(bytes, st, sh, a);
+  else b5_launch<WD, LK, PROF, true, 1, -1, 1, blk5::SCHED_DEFAULT>(bytes, st, sh, a);
 }
 
 hipError_t mlp_launch_block5(const MlpShape& sh, const MlpArgs& a, hipStream_t st) {
@@ -94,8 +70,8 @@ hipError_t mlp_launch_block5(const MlpShape& sh, const MlpArgs& a, hipStream_t s
   } else if (a.xg_world > 1) {
     mlp_launch_block5_xg(a.xg_world, bytes, st, sh, a);  // mlp_block5_xg.hip
   } else if (a.mode == 1) {  // grad mode: no Adam, no moments
-    if (a.loss_kind == 0) b5_launch<false, 0, false, true, false>(bytes, st, sh, a);
-    else b5_launch<false, 1, false, true, false>(bytes, st, sh, a);
+    if (a.loss_kind == 0) b5_launch<false, 0, false, false>(bytes, st, sh, a);
+    else b5_launch<false, 1, false, false>(bytes, st, sh, a);
   } else if (a.prof) {  // per-phase cycle stamps (tools/prof_block.py)
     if (a.loss_kind == 0) b5_launch_sched<true, 0, true>(sched, bytes, st, sh, a);
     else b5_launch_sched<true, 1, true>(sched, bytes, st, sh, a);

@@ -10,8 +10,8 @@ namespace dct {
 
 template <int XW>
 static void b8_xg(size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
-  if (a.loss_kind == 0) b5_launch<true, 0, false, true, true, XW, -1, 2>(bytes, st, sh, a);
-  else b5_launch<true, 1, false, true, true, XW, -1, 2>(bytes, st, sh, a);
+  if (a.loss_kind == 0) b5_launch<true, 0, false, true, XW, -1, 2>(bytes, st, sh, a);
+  else b5_launch<true, 1, false, true, XW, -1, 2>(bytes, st, sh, a);
 }
 
 void mlp_launch_block5_b8(size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
@@ -27,14 +27,14 @@ void mlp_launch_block5_b8(size_t bytes, hipStream_t st, const MlpShape& sh, cons
     default: break;
   }
   if (a.mode == 1) {  // grad mode (the DDP step path): no Adam, no moments
-    if (a.loss_kind == 0) b5_launch<false, 0, false, true, false, 1, -1, 2>(bytes, st, sh, a);
-    else b5_launch<false, 1, false, true, false, 1, -1, 2>(bytes, st, sh, a);
+    if (a.loss_kind == 0) b5_launch<false, 0, false, false, 1, -1, 2>(bytes, st, sh, a);
+    else b5_launch<false, 1, false, false, 1, -1, 2>(bytes, st, sh, a);
   } else if (a.loss_kind == 0) {
-    if (wd) b5_launch<true, 0, false, true, true, 1, -1, 2>(bytes, st, sh, a);
-    else b5_launch<false, 0, false, true, true, 1, -1, 2>(bytes, st, sh, a);
+    if (wd) b5_launch<true, 0, false, true, 1, -1, 2>(bytes, st, sh, a);
+    else b5_launch<false, 0, false, true, 1, -1, 2>(bytes, st, sh, a);
   } else {
-    if (wd) b5_launch<true, 1, false, true, true, 1, -1, 2>(bytes, st, sh, a);
-    else b5_launch<false, 1, false, true, true, 1, -1, 2>(bytes, st, sh, a);
+    if (wd) b5_launch<true, 1, false, true, 1, -1, 2>(bytes, st, sh, a);
+    else b5_launch<false, 1, false, true, 1, -1, 2>(bytes, st, sh, a);
   }
 }
 

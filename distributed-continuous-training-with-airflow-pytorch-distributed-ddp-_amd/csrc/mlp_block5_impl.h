@@ -49,8 +49,9 @@ struct Lds {
   static constexpr int B2L = W2L + 2 * H * C;              // [2][4] b2
   static constexpr int ABT = B2L + 8;                      // [4] data-parallel launches: a wave's exchange timed out
   static constexpr int TOTAL = ABT + 4;
-  // SCH_DZ2F: [2][H][4] h2 > 0 ? scale : 0 of (output o, row).  Behind TOTAL: the layout and the zeroing
-  // loop of the other kernels stay as they are (every word is written before barrier B, read behind it)
+  // the step schedule's dZ2 factors: [2][H][4] h2 > 0 ? scale : 0 of (output o, row).  Behind TOTAL: the layout
+  // and the zeroing loop of the other kernels stay as they are (every word is written before barrier B, read
+  // behind it)
   static constexpr int DZF = TOTAL;
   static constexpr int TOTAL_DZF = DZF + 2 * H * 4;
   static_assert((DZF % 4) == 0, "16-B aligned");
@@ -61,84 +62,50 @@ struct Lds {
 static_assert(Lds<1>::TOTAL == 11036, "the batch <= 4 layout is round 5's");
 constexpr int STG = H * H;
 constexpr int LDS_FLOATS = Lds<MBMAX>::TOTAL > 2 * STG ? Lds<MBMAX>::TOTAL : 2 * STG;  // two staging tiles (prologue/epilogue)
-static_assert(Lds<1>::TOTAL_DZF <= LDS_FLOATS, "SCH_DZ2F's region inside the launch's LDS");
+static_assert(Lds<1>::TOTAL_DZF <= LDS_FLOATS, "the dZ2 factors inside the launch's LDS");
 static_assert(LDS_FLOATS * 4 <= 160 * 1024, "fits the CU");
 using Stg = bku::Stage<H, NT>;
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-// Step-schedule items of the one-rank batch <= 4 train kernels (template parameter SCH, a mask):
-// work that does not depend on this step's gradients leaves the contended backward (where every
-// instruction of either SIMD partner is on the younger wave's path) for the barrier A -> B window,
-// in which both waves of a SIMD mostly wait on LDS and on each other.  Every item keeps each value's
-// instruction sequence, so the results are bit for bit those of SCH = 0.
-//   DROP        next step's dropout factors: hashed behind the A -> B window's LDS reads
-//   ADAM_TAB    Adam's per-step scalars A / E: lane i evaluates them for step t + i once every 64
-//               steps, one readlane each per step (instead of 2 exp, 2 rcp, 1 rsq + ~8 VALU per step)
-//   WT1 * n     dZ1's quad transposes of the first n = 0..3 W1 k-blocks (8 MFMAs, 8 registers each): in the
-//               window (SCH_WT2 = 2 blocks, SCH_WT1 | SCH_WT2 = 3)
-//   WTB         the next k-block's transposes (block n) right behind barrier B, under the loss: there every
-//               wave runs one dependent chain (LDS read, cross-lane adds, exp, rcp) and the matrix pipe
-//               is idle.  Faster without a block in the A -> B window than beside one.
-//   PRIO_LAT    wave priority per phase: s_setprio 1 over the short dependency-bound phases (h2 + logit
-//               share, the loss, dZ2 + the W2 / b1 / b2 owners up to dZ1's first k-block, the dW0 / db0
-//               tail), 0 over F1 / F2, the rest of dZ1's MFMA chains + its reduce-scatter and dW1 + Adam.
-//               With both waves of a SIMD at priority 0 the younger one queues in those few dozen
-//               instructions (v_sqrt / v_rcp / DPP / readlane chains) behind its partner's dense dZ1 /
-//               dW1 + Adam stream, and the partner then waits for it at barrier A.
-// Measured and not kept (profiles/b5_sched_ab_r7.log): the next input tile read before the dW1 pass
-// (alone +1.2 %), W1 Adam beside the dW1 MFMAs as scalar fmas instead of packed (+10 %), two or three
-// hoisted transpose blocks with the other items (slower than one).  profiles/b5_dw1z_ab_r9.log: dW1's
-// MFMAs and the W1 Adam of k-block q inside dZ1's loop, in the hazard gaps of its dependent MFMA
-// chains (100 -> 41 s_nop per step, +5.5 .. +8.7 %: a padded wave yields its issue slots to its SIMD
-// partner, a filled one does not); two or three blocks behind barrier B (slower than one).
-// profiles/b5_prio_defer_ab_r10.log: the backward one level above F1 / F2 (alone
-// -1.7 %, nothing on top of PRIO_LAT), the owners' Adam deferred into the next step in front of barrier A
-// (+4.2 %), PRIO_LAT over dZ1's reduce-scatter too, without the A -> B window, without the dW0 / db0 tail,
-// without the owners, or one level higher in waves 4..7 (all slower than PRIO_LAT as it is).
-constexpr int SCH_DROP = 1, SCH_ADAM_TAB = 2, SCH_WT1 = 8, SCH_WT2 = 16, SCH_WTB = 32;
-constexpr int SCH_PRIO_LAT = 64;
-// Round 11: vector instructions the result does not need, out of the loop (both waves of a SIMD pay for
-// each other's issue).  Same operations in the same order on every value, so still bit for bit SCH = 0.
-//   PF_W0       the next batch's gather (index, x / label word and their address arithmetic) only in wave 0,
-//               behind a scalar branch: at one micro-batch only threads 0 .. B * D0 + B - 1 <= 35 have a
-//               prefetch role, yet all eight waves issued the loads and waited for them behind barrier A;
-//               the row offset as one 32 x 32 -> 64-bit multiply-add (indices and strides are not negative)
-//   ADAM_SM     the two small Adam pairs (W2-own + b1, the two W0 slices) held as 64-bit pairs and updated
-//               in place by adam_v2 like W1 (as scalar fmacs their moments landed in the gradient's register
-//               and went back through v_mov at the loop's back edge); the step's E in one VGPR for the
-//               small updates instead of a v_mov from its SGPR in front of each v_fma
-//   DZ2F        dZ2's ReLU / dropout factor (h2 > 0 ? scale : 0) published as floats [o][row] by the owning
-//               wave instead of a ballot whose nibbles every consumer takes apart: one float4 read per
-//               output and one multiply per value.  A masked value is g * 0 = +-0 instead of +0; dZ2 is only
-//               an MFMA operand into accumulators that start at +0, where x * +-0 + (+0) = +0 either way
-//   DROP_INT    dropout keep test on integers: u01(h) < p <=> (h >> 8) < ceil(p * 2^24), the threshold
-//               once per launch (h >> 8 < 2^24 converts exactly and 2^-24 scales exactly)
-//   DB2         db2 of class l & 1 as quad_sum(dz) - (d0 + d1) + (d2 + d3) of class cb in every lane, the
-//               same association - and one row rotation, instead of two exec-masked blocks of readlane sums
-constexpr int SCH_PF_W0 = 128, SCH_ADAM_SM = 256, SCH_DZ2F = 512, SCH_DROP_INT = 1024, SCH_DB2 = 2048;
-constexpr int SCHED_R10 = SCH_DROP | SCH_ADAM_TAB | SCH_WTB | SCH_PRIO_LAT;  // round 10's default
-constexpr int SCHED_R11 = SCHED_R10 | SCH_PF_W0 | SCH_ADAM_SM | SCH_DZ2F | SCH_DROP_INT | SCH_DB2;  // round 11's
-// Round 12: the same lever on what round 11 left (same operations in the same order on every value).
-//   LOGIT_RS    the two logit shares as a reduce-scatter over lane bits 2..5 instead of two all-reduces of which
-//               only class cb = lane bit 2 is stored: lane i - 4 has the opposite bit 2, so row_ror:4 delivers
-//               exactly the class lane i keeps, every later partner agrees on bit 2, and each level adds the
-//               two operands it added before (the first level as the compiler fuses it in sum_bits2to5: the lane's
-//               own product inside an fma, the neighbour's rounded)
-//   INV_BS      1 / bs once per launch for bs = B (the same v_cvt + v_rcp on the same value, held in an SGPR);
-//               the per-step form only behind a scalar bs != B branch (a dataset's last batch), and wave 0's
-//               batch loss takes the same value instead of evaluating it again
-//   ADAM_B02    b0[u] and b2 (the two remaining adam_scaled calls) as one 64-bit triple updated in place by
-//               adam_v2r at the dW0 / db0 tail: packed moment / denominator / parameter updates, two square roots
-//               and two reciprocals (adam_v2's shared reciprocal is not the bits of rcp(d)); b2 is published
-//               there, still in front of the next barrier A
-// Measured and not kept (profiles/b5_lean2_ab_r12.log): packed fp32 where the operands
-// already sit in aligned pairs - F1's four row products over the two 16-byte input tiles (-2 after the copies
-// of W0's odd half it needs), dZ2's two-class products and factor multiply over row pairs (-12) - each fails
-// alone and makes the kept items slower (dZ2: 3.16 -> 3.21 us/step); dZ1's acc[0] + acc[1] as packed adds (-8;
-// the results must sit in aligned pairs, 251 -> 256 VGPRs, the weight-decay instantiations spill); W1 Adam's
-// addend E from ADAM_SM's VGPR (the splat is marshalled into a pair again, no instruction fewer).
-constexpr int SCH_LOGIT_RS = 4096, SCH_INV_BS = 8192, SCH_ADAM_B02 = 16384;
-constexpr int SCHED_DEFAULT = SCHED_R11 | SCH_LOGIT_RS | SCH_INV_BS | SCH_ADAM_B02;
-static_assert(SCHED_DEFAULT < 32768, "item masks stay below B5_SCHED_AB_BASE (knobs.h)");
+// The step schedule of the one-rank batch <= 4 train kernels (template parameter SCH: 0 = without it, the
+// path of every data-parallel, two-micro-batch and grad-mode kernel and of DCT_B5_SCHED=0; SCHED_DEFAULT =
+// with it).  Two levers, each described at the code it governs in mlp_block5_kernel:
+//   * work that does not depend on this step's gradients leaves the contended backward (where every
+//     instruction of either SIMD partner is on the younger wave's path) for the barrier A -> B window, in
+//     which both waves of a SIMD mostly wait on LDS and on each other, and for the loss behind barrier B;
+//     the short dependency-bound phases run at a raised wave priority;
+//   * vector instructions the result does not need leave the loop (both waves of a SIMD pay for each
+//     other's issue).
+// In step order ("step schedule" in the comments there): the next batch's gather in wave 0 only; in the A -> B
+// window the next step's dropout factors (integer keep test) and Adam's scalars from a 64-step lane table;
+// the logit share as a reduce-scatter and dZ2's ReLU / dropout factors published as floats; behind barrier B
+// the first W1 k-block's transposes for dZ1 under the loss, 1 / bs from a launch constant, db2 from a quad
+// sum; the small Adam pairs packed and updated in place ({W2, b1}, the W0 slices, {b0, b2} at the dW0 / db0
+// tail); B5PRIO around the phases.
+// Every value keeps its operations in their order, so parameters, moments and losses are bit for bit those
+// of SCH = 0 (tests/test_block5_sched_gpu.py).  The A/Bs of the single items: profiles/b5_sched_ab_r7.log,
+// b5_dw1z_ab_r9.log, b5_prio_defer_ab_r10.log, b5_lean_ab_r11.log, b5_lean2_ab_r12.log and BASELINE.md.
+// A future candidate is A/B'd as the next bit of SCH with one extra launch line under its own -D in
+// mlp_block5.hip, and is deleted or folded into SCHED_DEFAULT once measured.
+// Measured and not kept:
+//   * profiles/b5_sched_ab_r7.log: the next input tile read before the dW1 pass (alone +1.2 %), W1 Adam
+//     beside the dW1 MFMAs as scalar fmas instead of packed (+10 %), two or three k-blocks of dZ1's W1
+//     transposes hoisted into the A -> B window (slower than one).
+//   * profiles/b5_dw1z_ab_r9.log: dW1's MFMAs and the W1 Adam of k-block q inside dZ1's loop, in the hazard
+//     gaps of its dependent MFMA chains (100 -> 41 s_nop per step, +5.5 .. +8.7 %: a padded wave yields its
+//     issue slots to its SIMD partner, a filled one does not); one transpose block in the A -> B window, alone
+//     or beside the block behind barrier B (slower than that block alone); two or three blocks behind barrier
+//     B (slower than one).
+//   * profiles/b5_prio_defer_ab_r10.log: the backward one priority level above F1 / F2 (alone -1.7 %, nothing
+//     on top of the per-phase priorities), the owners' Adam deferred into the next step in front of barrier A
+//     (+4.2 %), the raised priority over dZ1's reduce-scatter too, without the A -> B window, without the
+//     dW0 / db0 tail, without the owners, or one level higher in waves 4..7 (all slower than B5PRIO as placed).
+//   * profiles/b5_lean2_ab_r12.log: packed fp32 where the operands already sit in aligned pairs - F1's four
+//     row products over the two 16-byte input tiles (-2 after the copies of W0's odd half it needs), dZ2's
+//     two-class products and factor multiply over row pairs (-12) - each fails alone and makes the kept items
+//     slower (dZ2: 3.16 -> 3.21 us/step); dZ1's acc[0] + acc[1] as packed adds (-8; the results must sit in
+//     aligned pairs, 251 -> 256 VGPRs, the weight-decay instantiations spill); W1 Adam's addend E from the
+//     small updates' VGPR (the splat is marshalled into a pair again, no instruction fewer).
+constexpr int SCHED_DEFAULT = 1;
 }  // namespace blk5
 
 // ---- data parallelism inside the persistent launch (XW = 2 / 4 / 8 ranks, one per GPU) ---------
@@ -227,10 +194,14 @@ __device__ __host__ __forceinline__ void static_for(F&& f) {
     t_last = t_;                                                \
   }
 
-// SCH_PRIO_LAT: the wave's priority from here on; pinned, or the scheduler moves the neighbouring phases'
-// instructions across it
+// Step schedule: the wave's priority from here on (pinned, or the scheduler moves the neighbouring phases'
+// instructions across it).  s_setprio 1 over the short dependency-bound phases (h2 + logit share, the loss,
+// dZ2 + the W2 / b1 owners up to dZ1's first k-block, the dW0 / db0 tail), 0 over F1 / F2, the rest of dZ1's
+// MFMA chains + its reduce-scatter and dW1 + Adam.  With both waves of a SIMD at priority 0 the younger one
+// queues in those few dozen instructions (v_sqrt / v_rcp / DPP / readlane chains) behind its partner's dense
+// dZ1 / dW1 + Adam stream, and the partner then waits for it at barrier A.
 #define B5PRIO(p)                      \
-  if constexpr (S_PLAT) {              \
+  if constexpr (S) {                   \
     __builtin_amdgcn_sched_barrier(0); \
     __builtin_amdgcn_s_setprio(p);     \
     __builtin_amdgcn_sched_barrier(0); \
@@ -253,8 +224,9 @@ __device__ __forceinline__ float b5_drop(uint32_t seed, uint32_t gstep, uint32_t
   h ^= h >> 16;
   return u01(h) < p ? 0.f : scale;
 }
-// SCH_DROP_INT: the same keep test on integers.  u01(h) = (h >> 8) * 2^-24 is exact (24 bits, a power-of-
-// two scale), so u01(h) < p <=> (h >> 8) < p * 2^24 <=> (h >> 8) < ceil(p * 2^24) for the integer h >> 8
+// Step schedule: the same keep test on integers, the threshold once per launch.  u01(h) = (h >> 8) * 2^-24 is
+// exact (24 bits, a power-of-two scale: h >> 8 < 2^24 converts exactly and 2^-24 scales exactly), so
+// u01(h) < p <=> (h >> 8) < p * 2^24 <=> (h >> 8) < ceil(p * 2^24) for the integer h >> 8
 __device__ __forceinline__ uint32_t b5_drop_thr(float p) { return (uint32_t)ceilf(p * 16777216.0f); }
 __device__ __forceinline__ float b5_drop_int(uint32_t seed, uint32_t gstep, uint32_t elem, uint32_t thr, float scale) {
   uint32_t h = (seed * 0x9E3779B1u) ^ ((gstep + 0x7F4A7C15u) * 0x85EBCA77u);
@@ -329,8 +301,8 @@ __device__ __forceinline__ void adam_v2(v2f& p, v2f g, v2f& m, v2f& v, float b1,
   const float R = __builtin_amdgcn_rcpf(d.x * d.y);
   p = p - m * ((v2f){d.y, d.x} * R);
 }
-// SCH_ADAM_B02: two bku::adam_scaled updates held as one pair - component-wise adam_scaled's sequence,
-// each parameter with its own reciprocal
+// two bku::adam_scaled updates held as one pair - component-wise adam_scaled's sequence, each parameter with
+// its own reciprocal (adam_v2's shared reciprocal is not the bits of rcp(d))
 template <bool WD>
 __device__ __forceinline__ void adam_v2r(v2f& p, v2f g, v2f& m, v2f& v, float b1, float b2, float wd, float A, float E) {
   if constexpr (WD) g = (v2f)(wd) * p + g;
@@ -350,24 +322,15 @@ __device__ __forceinline__ void adam_v2r(v2f& p, v2f g, v2f& m, v2f& v, float b1
 // XW > 1: train mode of one rank of XW data-parallel ranks (b5x above); RK >= 0: that rank as a
 // compile-time constant (every ownership test folds, the all-gather loads land straight in the W1
 // registers; fewer live registers and spills than the runtime-rank kernel, RK = -1);
-// SCH: step-schedule items (blk5::SCH_*; one-rank train mode at MB = 1 only, 0 = the previous schedule)
-template <bool WD, int LK, bool PROF = false, bool DXM = true, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1,
-          int SCH = 0>
+// SCH: the step schedule (blk5::SCHED_DEFAULT; one-rank train mode at MB = 1 only), 0 = without it
+template <bool WD, int LK, bool PROF = false, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1, int SCH = 0>
 __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, MlpArgs a) {
   using namespace blk5;
   using namespace bku;
   static_assert(XW == 1 || (ADAM && XW >= 2 && XW <= 8), "exchange: train mode, 2..8 ranks");
   static_assert(MB >= 1 && MB <= MBMAX, "micro-batches per step");
-  static_assert(SCH == 0 || (XW == 1 && MB == 1 && ADAM), "step-schedule items: one-rank train mode, one micro-batch");
-  constexpr bool S_DROP = (SCH & SCH_DROP) != 0, S_TAB = (SCH & SCH_ADAM_TAB) != 0;
-  constexpr int HQ = DXM ? (SCH / SCH_WT1) & 3 : 0;  // hoisted W1 transpose blocks
-  constexpr int HB = DXM ? (SCH / SCH_WTB) & 1 : 0;  // ... and the next one, behind barrier B
-  static_assert(HQ + HB <= KS / 4, "W1 has four k-blocks per wave");
-  constexpr bool S_PLAT = (SCH & SCH_PRIO_LAT) != 0;
-  constexpr bool S_PF = (SCH & SCH_PF_W0) != 0, S_SM = (SCH & SCH_ADAM_SM) != 0, S_DZF = (SCH & SCH_DZ2F) != 0;
-  constexpr bool S_DINT = (SCH & SCH_DROP_INT) != 0, S_DB2 = (SCH & SCH_DB2) != 0;
-  constexpr bool S_LRS = (SCH & SCH_LOGIT_RS) != 0, S_INVB = (SCH & SCH_INV_BS) != 0, S_B02 = (SCH & SCH_ADAM_B02) != 0;
-  constexpr bool S_EV = S_SM || S_B02;  // the step's E in a VGPR
+  static_assert(SCH == 0 || (XW == 1 && MB == 1 && ADAM), "step schedule: one-rank train mode, one micro-batch");
+  constexpr bool S = SCH != 0;
   using LY = Lds<MB>;
   constexpr int RB = LY::RB, XT = LY::XT, LAB = LY::LAB, MSK = LY::MSK, LOGP = LY::LOGP, H1W = LY::H1W;
   constexpr int H1X = LY::H1X, PART = LY::PART, W2L = LY::W2L, B2L = LY::B2L, ABT = LY::ABT, TOTAL = LY::TOTAL;
@@ -536,7 +499,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
   // re-materialised work with the MFMA chains), so XW = 1 keeps deriving them
   const float p_drop = a.dropout;
   const bool drop = p_drop > 0.f;
-  const uint32_t drop_thr = S_DINT ? b5_drop_thr(p_drop) : 0u;  // SCH_DROP_INT
+  const uint32_t drop_thr = S ? b5_drop_thr(p_drop) : 0u;  // (b5_drop_int)
   const float scale = XW > 1 ? a.k_drop_scale : (drop ? 1.0f / (1.0f - p_drop) : 1.0f);
   const float l2b1 = XW > 1 ? a.k_l2b1 : log2f(a.b1), l2b2 = XW > 1 ? a.k_l2b2 : log2f(a.b2);
   const float c1 = 1.f - a.b1, c2 = 1.f - a.b2;
@@ -562,17 +525,19 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       Mo[j][h] = (v2f){m1[j][2 * h], m1[j][2 * h + 1]};
       Vo[j][h] = (v2f){v1[j][2 * h], v1[j][2 * h + 1]};
     }
-  // SCH_ADAM_SM: the small Adam pairs in the same form (unpacked behind the loop): {W2[r0 & 1][u], b1[u]}
-  // - its .x is taken from pw2 every step - and the two W0 slices
+  // Step schedule: the small Adam pairs in the same form, updated in place by adam_v2 like W1 and unpacked
+  // behind the loop (as scalar fmacs their moments landed in the gradient's register and went back through
+  // v_mov at the loop's back edge): {W2[r0 & 1][u], b1[u]} - its .x is taken from pw2 every step -, the two
+  // W0 slices, and {b0[u], b2} (the two adam_scaled calls, by adam_v2r)
   const v2f z2 = (v2f){0.f, 0.f};
-  v2f PSm = S_SM ? (v2f){0.f, pb1} : z2, MSm = S_SM ? (v2f){mw2, mb1} : z2, VSm = S_SM ? (v2f){vw2, vb1} : z2;
-  v2f PW0 = S_SM ? (v2f){w0[0], w0[1]} : z2, MW0 = S_SM ? (v2f){m0[0], m0[1]} : z2, VW0 = S_SM ? (v2f){v0[0], v0[1]} : z2;
-  // SCH_ADAM_B02: {b0[u], b2} the same way
-  v2f PB02 = S_B02 ? (v2f){pb0, pb2} : z2, MB02 = S_B02 ? (v2f){mb0, mb2} : z2, VB02 = S_B02 ? (v2f){vb0, vb2} : z2;
-  // SCH_INV_BS: 1 / B as every full batch's step evaluates it, wave-uniform in a scalar register
-  const uint32_t inv_bsz = S_INVB ? __builtin_amdgcn_readfirstlane(
-                                        __float_as_uint(__builtin_amdgcn_rcpf((float)(Bsz > 0 ? Bsz : 1))))
-                                  : 0u;
+  v2f PSm = S ? (v2f){0.f, pb1} : z2, MSm = S ? (v2f){mw2, mb1} : z2, VSm = S ? (v2f){vw2, vb1} : z2;
+  v2f PW0 = S ? (v2f){w0[0], w0[1]} : z2, MW0 = S ? (v2f){m0[0], m0[1]} : z2, VW0 = S ? (v2f){v0[0], v0[1]} : z2;
+  v2f PB02 = S ? (v2f){pb0, pb2} : z2, MB02 = S ? (v2f){mb0, mb2} : z2, VB02 = S ? (v2f){vb0, vb2} : z2;
+  // Step schedule: 1 / bs once per launch for bs = B, as every full batch's step evaluates it (the same v_cvt +
+  // v_rcp on the same value), wave-uniform in a scalar register
+  const uint32_t inv_bsz = S ? __builtin_amdgcn_readfirstlane(
+                                   __float_as_uint(__builtin_amdgcn_rcpf((float)(Bsz > 0 ? Bsz : 1))))
+                             : 0u;
   // ---- XW > 1: the moments of the owned W1 pairs only (slot t = pair rank + XW t), the exchange's
   // buffer descriptors, this rank's small-pair ownership
   const int xrank = XW > 1 ? (RK >= 0 ? RK : a.xg_rank) : 0;
@@ -627,15 +592,17 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     f1[hf] = b5_drop(a.seed, step_base, el0[hf], p_drop, scale);
     f2[hf] = b5_drop(a.seed, step_base, el1[hf], p_drop, scale);
   }
-  // SCH_PF_W0: every prefetch role sits in wave 0 (B * D0 + B <= 36 threads); a scalar condition
-  const bool pf_wave = !S_PF || __builtin_amdgcn_readfirstlane(w) == 0;
+  // Step schedule: the next batch's gather only in wave 0, behind a scalar branch.  At one micro-batch every
+  // prefetch role sits there (B * D0 + B <= 36 threads), yet all eight waves issued the loads and their
+  // address arithmetic and waited for them behind barrier A
+  const bool pf_wave = !S || __builtin_amdgcn_readfirstlane(w) == 0;
   float* h1x = lds + H1X + w * (KS * 4);
   float eye[4];  // one-hot of lane % 4 (B operands of the MFMA quad transposes)
 #pragma unroll
   for (int i = 0; i < 4; ++i) eye[i] = r0 == i ? 1.f : 0.f;
   const int cb = (l >> 2) & 1;  // loss role: class cb of row r0 (wave share l / 8)
   int xb = 0;
-  float tabA = 0.f, tabE = 0.f;  // SCH_ADAM_TAB: lane i's Adam scalars of step (64-step block start) + i
+  float tabA = 0.f, tabE = 0.f;  // step schedule: lane i's Adam scalars of step (64-step block start) + i
   if (a.tune == 1 && w >= NW / 2) __builtin_amdgcn_s_setprio(1);
   if (a.tune == 2 && w < NW / 2) __builtin_amdgcn_s_setprio(1);
   if constexpr (PROF) {
@@ -653,8 +620,9 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     const int bs_next = have_next ? min(Bsz, a.n_items - (sb + 1) * Bsz) : 0;
     uint32_t raw_next = 0u;
     int ridx_next2 = 0;
-    if constexpr (S_PF) {
+    if constexpr (S) {
       if (pf_wave) {  // wave-uniform: the other waves issue neither the loads nor their addresses
+        // (the row offset as one 32 x 32 -> 64-bit multiply-add: indices and strides are not negative)
         raw_next = pf_base[(size_t)(uint32_t)ridx_next * (uint32_t)pf_stride];
         const int nx2 = min((sb + 2) * Bsz + pb, a.n_items - 1);
         ridx_next2 = a.idx[nx2 < 0 ? 0 : nx2];
@@ -673,9 +641,9 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     float dz = 0.f, xbl = 0.f, tls = 0.f;  // last micro-batch's dlogit; XW > 1: batch loss; loss sum
     float h2 = 0.f, h1 = 0.f;
     float gw0s = 0.f, gw1s = 0.f, gb1s = 0.f, gbs = 0.f, g0s = 0.f, g1s = 0.f, db0s = 0.f;
-    float aA = 0.f, aE = 0.f, aEv = 0.f;
-    float f1n = 0.f, f2n = 0.f;           // SCH_DROP: next step's dropout factors (from the A -> B window)
-    f32x4_t wth[HQ + HB > 0 ? HQ + HB : 1][2];  // SCH_WT*: transposed W1 quads of k-blocks q < HQ + HB
+    float aA = 0.f, aE = 0.f, aEv = 0.f;  // Adam's per-step scalars; step schedule: E in a VGPR for the small updates
+    float f1n = 0.f, f2n = 0.f;           // step schedule: next step's dropout factors (from the A -> B window)
+    f32x4_t wth[1][2];                    // step schedule: transposed W1 quads of k-block 0 (from behind barrier B)
     v2f GO[NO];  // XW > 1 (reduce-scatter): gradients of the W1 pairs this rank owns
 #pragma unroll
     for (int t2 = 0; t2 < NO; ++t2) GO[t2] = (v2f){0.f, 0.f};
@@ -738,7 +706,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       const float4 xa = *reinterpret_cast<const float4*>(xT + r0 * RB + B * hf);
       const float4 xc = *reinterpret_cast<const float4*>(xT + (r0 + 4) * RB + B * hf);
       {
-        const float wa = S_SM ? PW0.x : w0[0], wc = S_SM ? PW0.y : w0[1];
+        const float wa = S ? PW0.x : w0[0], wc = S ? PW0.y : w0[1];
         const float acc0 = wa * xa.x + wc * xc.x, acc1 = wa * xa.y + wc * xc.y;
         const float acc2 = wa * xa.z + wc * xc.z, acc3 = wa * xa.w + wc * xc.w;
         const bool qb1 = (r0 >> 1) & 1, qb0 = r0 & 1;
@@ -746,7 +714,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         const float s0 = qb1 ? acc0 : acc2, s1 = qb1 ? acc1 : acc3;
         const float e0 = k0 + dpp<QP_X2>(s0), e1 = k1 + dpp<QP_X2>(s1);
         const float kq = qb0 ? e1 : e0, sq = qb0 ? e0 : e1;
-        h1 = fmaxf(kq + dpp<QP_X1>(sq) + (S_B02 ? PB02.x : pb0), 0.f) * f1[hf];
+        h1 = fmaxf(kq + dpp<QP_X1>(sq) + (S ? PB02.x : pb0), 0.f) * f1[hf];
         h1w[l] = h1;                    // [k = l / 4][row = l % 4]
         h1x[r0 * KS + (l >> 2)] = h1;   // [row][k]
       }
@@ -783,7 +751,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
           if (tid == 0) a.stage[0] = bs_st > 0 ? (uint32_t)(sb + 2) : 0u;
         }
         // next batch into the next input buffer (its last readers finished before the previous barrier B)
-        if (pf_wave) {  // (SCH_PF_W0: wave 0; otherwise constant true)
+        if (pf_wave) {  // (step schedule: wave 0; otherwise constant true)
           if (role) {
             const uint32_t v = (have_next && pb < bs_next) ? raw_next : 0u;
             uint32_t* dst = (role == 1) ? reinterpret_cast<uint32_t*>(lds + XT + xbn * DMAX * RB) + pk * RB + pb
@@ -818,34 +786,23 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         float q[NW];
 #pragma unroll
         for (int ww = 0; ww < NW; ++ww) q[ww] = pr[4 * ww];
-        if constexpr (SCH != 0) {
-          // ---- gradient-free work of the step, issued behind the LDS reads above and in front of
-          // their first use (pinned: the scheduler otherwise sinks it back into the backward)
+        if constexpr (S) {
+          // ---- step schedule: gradient-free work of the step, issued behind the LDS reads above and in
+          // front of their first use (pinned: the scheduler otherwise sinks it back into the backward)
           __builtin_amdgcn_sched_barrier(0);
-          if constexpr (HQ > 0) {
-#pragma unroll
-            for (int qq = 0; qq < HQ; ++qq)
-#pragma unroll
-              for (int j = 0; j < 2; ++j) {
-                const float wq[4] = {W[j][2 * qq].x, W[j][2 * qq].y, W[j][2 * qq + 1].x, W[j][2 * qq + 1].y};
-                wth[qq][j] = quad_transpose_mf(wq, eye);
-              }
-          }
-          if constexpr (S_DROP) {
-            // (the asm statements hold both ends: instruction selection may otherwise emit the hash in
-            // front of barrier A, and code sinking moves values only used next step back to the loop end)
+          {
+            // the next step's dropout factors, by the integer keep test (p_drop = 0: always 1).  The asm
+            // statements hold both ends: instruction selection may otherwise emit the hash in front of
+            // barrier A, and code sinking moves values only used next step back to the loop end
             uint32_t gnext = gstep + 1u;
             asm volatile("" : "+s"(gnext));
-            if constexpr (S_DINT) {  // the integer form of the same test
-              f1n = b5_drop_int(a.seed, gnext, el0[0], drop_thr, scale);
-              f2n = b5_drop_int(a.seed, gnext, el1[0], drop_thr, scale);
-            } else {
-              f1n = b5_drop(a.seed, gnext, el0[0], p_drop, scale);  // p_drop = 0: always 1
-              f2n = b5_drop(a.seed, gnext, el1[0], p_drop, scale);
-            }
+            f1n = b5_drop_int(a.seed, gnext, el0[0], drop_thr, scale);
+            f2n = b5_drop_int(a.seed, gnext, el1[0], drop_thr, scale);
             asm volatile("" : "+v"(f1n), "+v"(f2n));
           }
-          if constexpr (S_TAB) {
+          {
+            // Adam's per-step scalars A / E: lane i evaluates them for step t + i once every 64 steps, one
+            // readlane each per step (instead of 2 exp, 2 rcp, 1 rsq + ~8 VALU per step)
             const int ti = s & 63;
             if (ti == 0) {  // wave-uniform: the next 64 steps' scalars, one per lane
               asm volatile("");  // a real branch: without it the block is if-converted and runs every step
@@ -858,34 +815,36 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             }
             aA = rl(tabA, ti);
             aE = rl(tabE, ti);
-            if constexpr (S_EV) {  // one VGPR copy for the step's small updates (a v_fma takes one SGPR)
-              aEv = aE;
-              asm volatile("" : "+v"(aEv));
-            }
+            // E in one VGPR for the step's small updates (a v_fma takes one SGPR), instead of a v_mov from
+            // its SGPR in front of each
+            aEv = aE;
+            asm volatile("" : "+v"(aEv));
           }
           __builtin_amdgcn_sched_barrier(0);
         }
         const float z = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
-        h2 = fmaxf(z + (S_SM ? PSm.y : pb1), 0.f) * f2[hf];
-        float t0s = 0.f, t1s = 0.f, tcs = 0.f;  // row r0's shares; SCH_LOGIT_RS: only the one of class cb
-        if constexpr (S_LRS) {
-          // sum_bits2to5's first level compiles to fma(w, h2, ror4(w * h2)) - the lane's own product is fused
-          // into the add, the neighbour's is rounded -, so the same here, spelled out
+        h2 = fmaxf(z + (S ? PSm.y : pb1), 0.f) * f2[hf];
+        // row r0's logit share of class cb ([wave][class][row], lanes 0..7) and the h2 > 0 mask
+        if constexpr (S) {
+          // the share as a reduce-scatter over lane bits 2..5 instead of two all-reduces of which only class
+          // cb = lane bit 2 is stored: lane i - 4 has the opposite bit 2, so row_ror:4 delivers exactly the
+          // class lane i keeps, every later partner agrees on bit 2, and each level adds the two operands it
+          // added before.  sum_bits2to5's first level compiles to fma(w, h2, ror4(w * h2)) - the lane's own
+          // product is fused into the add, the neighbour's is rounded -, so the same here, spelled out
           const float wk = cb ? pw2[1] : pw2[0], ws = cb ? pw2[0] : pw2[1];
           const float send = ws * h2;
-          tcs = fmaf(wk, h2, dpp<ROR4>(send));  // lane i - 4: bit 2 flipped, its send is this lane's class
+          float tcs = fmaf(wk, h2, dpp<ROR4>(send));  // lane i - 4: bit 2 flipped, its send is this lane's class
           tcs += dpp<ROR8>(tcs);
           tcs = swap16_sum(tcs, tcs);
           tcs = swap32_sum(tcs, tcs);
-        } else {
-          t0s = sum_bits2to5(pw2[0] * h2), t1s = sum_bits2to5(pw2[1] * h2);
-        }
-        if constexpr (S_DZF) {  // [o = u][row r0]: word 64 w + l, one linear store per wave
+          // dZ2's ReLU / dropout factor (h2 > 0 ? scale : 0) published as floats [o = u][row r0] (word 64 w + l,
+          // one linear store per wave) instead of a ballot whose nibbles every consumer takes apart
           lds[LY::DZF + mpar * (H * 4) + u * 4 + r0] = h2 > 0.f ? scale : 0.f;
-          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = S_LRS ? tcs : (cb ? t1s : t0s);  // [wave][class][row]
+          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = tcs;
         } else {
+          const float t0s = sum_bits2to5(pw2[0] * h2), t1s = sum_bits2to5(pw2[1] * h2);
           const unsigned long long msk = __ballot(h2 > 0.f);
-          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = S_LRS ? tcs : (cb ? t1s : t0s);  // [wave][class][row]
+          if (l < 8) lds[LOGP + mpar * (NW * 8) + w * 8 + l] = cb ? t1s : t0s;
           if (l == 0)
             *reinterpret_cast<uint2*>(lds + MSK + mpar * (NW * 2) + w * 2) = make_uint2((uint32_t)msk, (uint32_t)(msk >> 32));
         }
@@ -896,8 +855,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
 
       // ---- loss: lane (share l / 8, class cb, row r0) -> logit (r0, cb) of the micro-batch
       uint2 mw0 = make_uint2(0u, 0u), mw1 = mw0;
-      float4 zf0 = make_float4(0.f, 0.f, 0.f, 0.f), zf1 = zf0;  // SCH_DZ2F: factors of outputs l, l + 64
-      if constexpr (S_DZF) {
+      float4 zf0 = make_float4(0.f, 0.f, 0.f, 0.f), zf1 = zf0;  // step schedule: dZ2 factors of outputs l, l + 64
+      if constexpr (S) {
         zf0 = *reinterpret_cast<const float4*>(lds + LY::DZF + mpar * (H * 4) + l * 4);
         zf1 = *reinterpret_cast<const float4*>(lds + LY::DZF + mpar * (H * 4) + (l + 64) * 4);
       } else {
@@ -905,30 +864,29 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         mw1 = *reinterpret_cast<const uint2*>(lds + MSK + mpar * (NW * 2) + 2 * ((l >> 4) + 4));
       }
       float lg0 = 0.f;
-      if constexpr (HB > 0) {
-        // SCH_WTB: the loss below is one dependent chain (LDS read, cross-lane adds, exp, rcp) in every
-        // wave at once; the matrix pipe is idle under it
+      if constexpr (S) {
+        // step schedule: dZ1's quad transposes of W1's first k-block (8 MFMAs, 8 registers) here, under the
+        // loss: there every wave runs one dependent chain (LDS read, cross-lane adds, exp, rcp) and the matrix
+        // pipe is idle.  W1 is rewritten by Adam only at the end of the step
         lg0 = lds[LOGP + mpar * (NW * 8) + l];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int qq = HQ; qq < HQ + HB; ++qq)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const float wq[4] = {W[j][2 * qq].x, W[j][2 * qq].y, W[j][2 * qq + 1].x, W[j][2 * qq + 1].y};
-            wth[qq][j] = quad_transpose_mf(wq, eye);
-          }
+        for (int j = 0; j < 2; ++j) {
+          const float wq[4] = {W[j][0].x, W[j][0].y, W[j][1].x, W[j][1].y};
+          wth[0][j] = quad_transpose_mf(wq, eye);
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
       float lv;
-      uint32_t inv_bs = inv_bsz;  // SCH_INV_BS: 1 / bs of this step
-      if constexpr (S_INVB) {
+      uint32_t inv_bs = inv_bsz;  // step schedule: 1 / bs of this step
+      if constexpr (S) {
         if (bs != Bsz) {  // wave-uniform: a dataset's last batch
           asm volatile("");  // a real branch: if-converted, the conversion and the reciprocal run every step
           inv_bs = __builtin_amdgcn_readfirstlane(__float_as_uint(__builtin_amdgcn_rcpf((float)(bs > 0 ? bs : 1))));
         }
       }
       {
-        float lg = HB > 0 ? lg0 : lds[LOGP + mpar * (NW * 8) + l];
+        float lg = S ? lg0 : lds[LOGP + mpar * (NW * 8) + l];
         lg += dpp<ROR8>(lg);          // shares w', w' ^ 1 (lane bit 3)
         lg = swap16_sum(lg, lg);      // lane bit 4
         lg = swap32_sum(lg, lg);      // lane bit 5
@@ -936,7 +894,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         const float zo = dpp<ROR4>(z);  // the other class of the same row (lane bit 2 flipped in the
                                         // row-replicated copies)
         const bool live = r0 + B * hf < bs;
-        const float invb = S_INVB ? __uint_as_float(inv_bs) : __builtin_amdgcn_rcpf((float)(bs > 0 ? bs : 1));
+        const float invb = S ? __uint_as_float(inv_bs) : __builtin_amdgcn_rcpf((float)(bs > 0 ? bs : 1));
         const float inv = live ? invb : 0.f;
         const float y = (cb == lab) ? 1.f : 0.f;
         if constexpr (LK == 0) {
@@ -965,8 +923,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         tl += dpp<ROR4>(tl);
         tls = hf == 0 ? tl : tls + tl;
         if (last) {
-          // (SCH_INV_BS: bs > 0 makes the loss block's operand (float)bs too)
-          const float bl = bs > 0 ? tls * (S_INVB ? __uint_as_float(inv_bs) : __builtin_amdgcn_rcpf((float)bs)) : 0.f;
+          // (step schedule: the loss block's value - bs > 0 makes its operand (float)bs too)
+          const float bl = bs > 0 ? tls * (S ? __uint_as_float(inv_bs) : __builtin_amdgcn_rcpf((float)bs)) : 0.f;
           if constexpr (ADAM && XW > 1) {
             // sync_dist: one granule to every peer now, the rank-ordered mean after the all-gather
             xbl = rl(bl, 0);
@@ -984,16 +942,16 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       }
       B5STAMP(5)
 
-      if (last && !S_TAB) {
+      if (last && !S) {  // (step schedule: from the 64-step table, in the A -> B window)
         const float step_size = a.lr * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, (float)t));
         const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(l2b2, (float)t));
         const float rss = __builtin_amdgcn_rcpf(step_size);
         aA = sqc2 * rbc2 * rss * rc1;
         aE = a.eps * rss * rc1;
-        if constexpr (S_EV) aEv = aE;
       }
-      // ---- dZ2 of outputs o = l + 64 j, the micro-batch's rows (old W2, mask bits of the owning wave)
-      if constexpr (S_DZF) {
+      // ---- dZ2 of outputs o = l + 64 j, the micro-batch's rows (old W2; the owning wave's factors - one float4
+      // read per output and one multiply per value -, or its mask bits)
+      if constexpr (S) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const float2 wv = j ? wv1 : wv0;
@@ -1002,7 +960,9 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float g = wv.x * dz3[r][0] + wv.y * dz3[r][1];
-            dz2m[hf][j][r] = g * fr[r];  // fr = scale: the same product; fr = 0: +-0 for +0
+            // fr = scale: the same product; fr = 0: +-0 for +0, and dZ2 is only an MFMA operand into
+            // accumulators that start at +0, where x * +-0 + (+0) = +0 either way
+            dz2m[hf][j][r] = g * fr[r];
           }
         }
       } else {
@@ -1034,10 +994,11 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         gdz = h2 > 0.f ? gdz * scale : 0.f;
         const float gb1 = quad_sum(gdz);
         float gbh;
-        if constexpr (S_DB2) {
-          // dz of lane 4 c + r is dlogit (r, c): the quad sum is (d0 + d1) + (d2 + d3) of class cb up to
-          // the order inside a commutative add; lane 1 takes class 1 from lane 5 (row_ror:12 reads lane
-          // i + 4).  Only wave 0's lanes 0 / 1 keep the value
+        if constexpr (S) {
+          // db2 of class l & 1 as one quad sum and one row rotation instead of two exec-masked blocks of
+          // readlane sums, in the same association: dz of lane 4 c + r is dlogit (r, c), so the quad sum is
+          // (d0 + d1) + (d2 + d3) of class cb up to the order inside a commutative add; lane 1 takes class 1
+          // from lane 5 (row_ror:12 reads lane i + 4).  Only wave 0's lanes 0 / 1 keep the value
           const float qs = quad_sum(dz);
           const float qo = dpp<0x12C>(qs);
           gbh = (l & 1) ? qo : qs;
@@ -1060,7 +1021,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             xg_own = gown;
             xg_bx = r0 == 1 ? gb1s : gb;  // (r0 0: db0, known after dZ1)
           } else if constexpr (ADAM) {
-            if constexpr (S_SM) {
+            if constexpr (S) {
               PSm.x = pown;
               adam_v2<WD>(PSm, (v2f){gown, gb1s}, MSm, VSm, a.b1, a.b2, a.wd, aA, aEv);
               pown = PSm.x;
@@ -1070,8 +1031,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             pw2[0] = dpp<QB0>(pown);
             pw2[1] = dpp<QB1>(pown);
             if (own_w2) lds[W2L + nbuf * (H * C) + u * C + r0] = pown;
-            if constexpr (!S_B02) {  // (SCH_ADAM_B02: with b0 at the dW0 / db0 tail)
-              adam_scaled<WD>(pb2, gb, mb2, vb2, a.b1, a.b2, a.wd, aA, S_SM ? aEv : aE);
+            if constexpr (!S) {  // (step schedule: with b0 at the dW0 / db0 tail)
+              adam_scaled<WD>(pb2, gb, mb2, vb2, a.b1, a.b2, a.wd, aA, aE);
               if (own_b2) lds[B2L + nbuf * 4 + l] = pb2;
             }
           } else {  // grad mode (one step): dW2[r0][u], db1[u], db2 to the flat gradient
@@ -1084,7 +1045,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       B5STAMP(6)
       // ---- dZ1 = W1^T dZ2 over this wave's k-slice, lane l keeps its own (unit u, row r0)
       float dz1 = 0.f;
-      if constexpr (DXM) {
+      {
         // on the 4x4x1 MFMA: each quad's 4x4 blocks of W1 (rows o = 4b + i + 64 j, columns k = 4q + m)
         // and of dZ2 are transposed across the quad (MFMA, exact), so the call index runs over the block's 8
         // outputs and lane (b, n) accumulates sum_o W1[o][4q + m] dZ2[o][n] for m = 0..3; the 16
@@ -1099,14 +1060,14 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
         float P[16];
 #pragma unroll
         for (int q = 0; q < KS / 4; ++q) {
-          // (behind the block whose W1 transposes were hoisted: dropped between the owners and dZ1, the
-          // headline kernel needs 12 registers more and spills 7)
+          // (behind the block whose W1 transposes ran under the loss: dropped between the owners and dZ1,
+          // the headline kernel needs 12 registers more and spills 7)
           if (q == 1) B5PRIO(0)
           f32x4_t acc[2];  // one chain per j (4 dependent MFMAs each)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             const float wq[4] = {W[j][2 * q].x, W[j][2 * q].y, W[j][2 * q + 1].x, W[j][2 * q + 1].y};
-            const f32x4_t wt = q < HQ + HB ? wth[q < HQ + HB ? q : 0][j] : quad_transpose_mf(wq, eye);
+            const f32x4_t wt = S && q == 0 ? wth[0][j] : quad_transpose_mf(wq, eye);
             acc[j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[j] = mfma4(wt[i], dzt[j][i], acc[j]);
@@ -1116,17 +1077,6 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
           for (int m = 0; m < 4; ++m) P[4 * q + m] = at[m];
         }
         dz1 = rs_bits2to5(P, l);
-      } else {
-        // one 16-value reduce-scatter per batch row (pass p leaves unit k's sum in lanes 4k..4k+3)
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          float P[16];
-#pragma unroll
-          for (int kk = 0; kk < KS; ++kk)
-            P[kk] = W[0][kk >> 1][kk & 1] * dz2m[hf][0][p] + W[1][kk >> 1][kk & 1] * dz2m[hf][1][p];
-          const float tot = rs_small<16>(P, l);
-          if (r0 == p) dz1 = tot;
-        }
       }
       dz1 = h1 > 0.f ? dz1 * scale : 0.f;
       B5PRIO(1)
@@ -1156,15 +1106,15 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
                 }
             }
           } else if constexpr (ADAM) {
-            if constexpr (S_SM)
+            if constexpr (S)
               adam_v2<WD>(PW0, (v2f){g0, g1}, MW0, VW0, a.b1, a.b2, a.wd, aA, aEv);
             else
               adam_pair<WD>(w0[0], g0, m0[0], v0[0], w0[1], g1, m0[1], v0[1], a.b1, a.b2, a.wd, aA, aE);  // d >= D0: stays 0
-            if constexpr (S_B02) {  // {b0[u], b2}; b2 published for the next step's barrier A
+            if constexpr (S) {  // {b0[u], b2} as one pair; b2 published here, still in front of the next barrier A
               adam_v2r<WD>(PB02, (v2f){db0s, gbs}, MB02, VB02, a.b1, a.b2, a.wd, aA, aEv);
               if (own_b2) lds[B2L + nbuf * 4 + l] = PB02.y;
             } else {
-              adam_scaled<WD>(pb0, db0s, mb0, vb0, a.b1, a.b2, a.wd, aA, S_SM ? aEv : aE);
+              adam_scaled<WD>(pb0, db0s, mb0, vb0, a.b1, a.b2, a.wd, aA, aE);
             }
           } else {
             if (r0 < D0) a.grad_out[wo0 + u * D0 + r0] = g0;
@@ -1179,7 +1129,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     }
     B5PRIO(0)
     // next step's dropout factors (independent work for the Adam stream below)
-    if constexpr (S_DROP) {
+    if constexpr (S) {
       f1[0] = f1n;
       f2[0] = f2n;
     } else {
@@ -1334,11 +1284,9 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     B5STAMP(8)
     xb = xbn;
   }
-  if constexpr (S_SM) {  // the small pairs back to their scalars (the write-back below)
+  if constexpr (S) {  // the small pairs back to their scalars (the write-back below)
     pb1 = PSm.y; mw2 = MSm.x; mb1 = MSm.y; vw2 = VSm.x; vb1 = VSm.y;
     w0[0] = PW0.x; w0[1] = PW0.y; m0[0] = MW0.x; m0[1] = MW0.y; v0[0] = VW0.x; v0[1] = VW0.y;
-  }
-  if constexpr (S_B02) {
     pb0 = PB02.x; pb2 = PB02.y; mb0 = MB02.x; mb2 = MB02.y; vb0 = VB02.x; vb2 = VB02.y;
   }
 
@@ -1492,13 +1440,12 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
 #undef B5PRIO
 
 // one launch of an instantiation; its dynamic-LDS limit (two 64-KB staging tiles) is raised once
-template <bool WD, int LK, bool PROF = false, bool DXM = true, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1,
-          int SCH = 0>
+template <bool WD, int LK, bool PROF = false, bool ADAM = true, int XW = 1, int RK = -1, int MB = 1, int SCH = 0>
 inline void b5_launch(size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
-  static const hipError_t attr = hipFuncSetAttribute((const void*)mlp_block5_kernel<WD, LK, PROF, DXM, ADAM, XW, RK, MB, SCH>,
+  static const hipError_t attr = hipFuncSetAttribute((const void*)mlp_block5_kernel<WD, LK, PROF, ADAM, XW, RK, MB, SCH>,
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   (void)attr;
-  hipLaunchKernelGGL((mlp_block5_kernel<WD, LK, PROF, DXM, ADAM, XW, RK, MB, SCH>), dim3(1), dim3(blk5::NT), bytes, st, sh, a);
+  hipLaunchKernelGGL((mlp_block5_kernel<WD, LK, PROF, ADAM, XW, RK, MB, SCH>), dim3(1), dim3(blk5::NT), bytes, st, sh, a);
 }
 
 

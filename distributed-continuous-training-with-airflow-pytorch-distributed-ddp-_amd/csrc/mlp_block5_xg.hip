@@ -13,13 +13,13 @@ static void b5_launch_xg(size_t bytes, hipStream_t st, const MlpShape& sh, const
     // the reference's configuration (cross-entropy, Adam without weight decay): one kernel per rank
     b5x::static_for<XW>([&](auto rc) {
       constexpr int R = decltype(rc)::value;
-      if (a.xg_rank == R) b5_launch<false, 0, false, true, true, XW, R>(bytes, st, sh, a);
+      if (a.xg_rank == R) b5_launch<false, 0, false, true, XW, R>(bytes, st, sh, a);
     });
   } else if (a.loss_kind == 0) {
-    b5_launch<true, 0, false, true, true, XW>(bytes, st, sh, a);
+    b5_launch<true, 0, false, true, XW>(bytes, st, sh, a);
   } else {
-    if (wd) b5_launch<true, 1, false, true, true, XW>(bytes, st, sh, a);
-    else b5_launch<false, 1, false, true, true, XW>(bytes, st, sh, a);
+    if (wd) b5_launch<true, 1, false, true, XW>(bytes, st, sh, a);
+    else b5_launch<false, 1, false, true, XW>(bytes, st, sh, a);
   }
 }
 
@@ -32,8 +32,8 @@ void mlp_launch_block5_xg_static(int world, size_t bytes, hipStream_t st, const 
 template <int XW>
 static void b5_launch_xg_rt(size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
   if (a.loss_kind == 0 && a.wd == 0.f) mlp_launch_block5_xg_static(XW, bytes, st, sh, a);
-  else if (a.loss_kind == 0) b5_launch<true, 0, false, true, true, XW>(bytes, st, sh, a);
-  else b5_launch<true, 1, false, true, true, XW>(bytes, st, sh, a);
+  else if (a.loss_kind == 0) b5_launch<true, 0, false, true, XW>(bytes, st, sh, a);
+  else b5_launch<true, 1, false, true, XW>(bytes, st, sh, a);
 }
 
 void mlp_launch_block5_xg_prof(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);

@@ -12,10 +12,10 @@ static void b5_launch_xg_prof(size_t bytes, hipStream_t st, const MlpShape& sh, 
   if (a.loss_kind == 0 && a.wd == 0.f) {  // the reference configuration: the compile-time-rank kernels
     b5x::static_for<XW>([&](auto rc) {
       constexpr int R = decltype(rc)::value;
-      if (a.xg_rank == R) b5_launch<false, 0, true, true, true, XW, R>(bytes, st, sh, a);
+      if (a.xg_rank == R) b5_launch<false, 0, true, true, XW, R>(bytes, st, sh, a);
     });
   } else {
-    b5_launch<true, 0, true, true, true, XW>(bytes, st, sh, a);  // (profiling: CE only)
+    b5_launch<true, 0, true, true, XW>(bytes, st, sh, a);  // (profiling: CE only)
   }
 }
 

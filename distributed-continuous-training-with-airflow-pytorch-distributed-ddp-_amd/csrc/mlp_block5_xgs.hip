@@ -11,7 +11,7 @@ template <int XW>
 static void b5_launch_xgs(size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
   b5x::static_for<XW>([&](auto rc) {
     constexpr int R = decltype(rc)::value;
-    if (a.xg_rank == R) b5_launch<false, 0, false, true, true, XW, R>(bytes, st, sh, a);
+    if (a.xg_rank == R) b5_launch<false, 0, false, true, XW, R>(bytes, st, sh, a);
   });
 }
 

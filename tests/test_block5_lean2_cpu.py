@@ -1,6 +1,6 @@
-"""Two of mlp_block5's round-12 schedule items (csrc/mlp_block5_impl.h), emulated on the host in float32.
+"""Two parts of mlp_block5's step schedule (csrc/mlp_block5_impl.h), emulated on the host in float32.
 
-SCH_LOGIT_RS: the two logit shares of a lane were all-reduced over lane bits 2..5 (bku::sum_bits2to5) and only
+The logit-share reduce-scatter: the two logit shares of a lane were all-reduced over lane bits 2..5 (bku::sum_bits2to5) and only
 the one of class cb = lane bit 2 was stored; now the lane keeps its class, sends the other through row_ror:4
 and runs the same three further levels.  The emulation follows the cross-lane reads of csrc/mlp_block_util.h
 (row_ror:N: lane i of a 16-lane row reads lane (i - N) % 16; the permlane swaps pair lane i with i ^ 16 and
@@ -8,7 +8,7 @@ i ^ 32) and compares all 64 lanes bit for bit; rotating the other way (another a
 addends) must not pass, so the comparison can tell the difference.  A second check runs the first level as
 the kernels do, the lane's own product fused into the add.
 
-SCH_INV_BS: 1 / bs is evaluated once per launch for bs = B and per step only when bs != B."""
+The batch-size reciprocal: 1 / bs is evaluated once per launch for bs = B and per step only when bs != B."""
 import numpy as np
 import pytest
 

@@ -1,4 +1,4 @@
-"""mlp_block5's integer dropout keep test (SCH_DROP_INT, csrc/mlp_block5_impl.h): the kernel drops an element
+"""mlp_block5's integer dropout keep test (b5_drop_int, csrc/mlp_block5_impl.h): the kernel drops an element
 when ``(h >> 8) < ceil(p * 2^24)`` instead of ``u01(h) = (h >> 8) * 2^-24 < p``.  Both sides depend on the hash
 only through its 24 high bits, so the equivalence is checked over every one of the 2^24 values, in the
 kernel's fp32 arithmetic.  The host mirrors of the masks (ops/fused_mlp.py) keep the float compare and are
