@@ -34,19 +34,19 @@ static T* P(uintptr_t x) {
 }
 
 struct MlpPlan {
-  std::vector<char> shape;
+  dct::MlpShape shape{};
   int nt = 0, maxblk = 0, supported = 0;
   int use_wave = 0;  // single-wave register-resident kernel (narrow MLPs), see mlp_wave.hip
+  int use_tile = 0;  // mlp_tile.hip runs this plan's training launches
   MlpPlan(const std::vector<int>& dims, int bmax) {
     if (dims.size() < 2 || dims.size() > 5) throw std::invalid_argument("MLP needs 1..4 linear layers");
     for (int d : dims)
       if (d < 1 || d > 4096) throw std::invalid_argument("MLP layer width out of range");
-    shape.resize(dct_mlp_shape_size());
-    if (dct_mlp_make_shape(shape.data(), dims.data(), (int)dims.size() - 1, bmax) != 0)
+    if (dct::mlp_make_shape(&shape, dims.data(), (int)dims.size() - 1, bmax) != 0)
       throw std::invalid_argument("bad MLP shape");
     supported = dct_mlp_select(sh(), &nt, &maxblk);
     dct::knobs_reload();  // plan time: the DCT_* knobs of this process's launches
-    reinterpret_cast<dct::MlpShape*>(shape.data())->mlp_block = dct::knobs().mlp_block;
+    shape.mlp_block = dct::knobs().mlp_block;
     const bool force_lds = dct::knobs().mlp_force_lds != 0;
     use_wave = (!force_lds && dct_mlp_wave_supported(dims.data(), (int)dims.size() - 1, 1)) ? 1 : 0;
     if (use_wave) supported = 1;
@@ -59,11 +59,10 @@ struct MlpPlan {
       use_wave = 0;
     } else if (dct::knobs().mlp_block == dct::MLP_BLOCK_TILE) {
       use_tile = tile_ok ? 1 : 0;
-      if (!tile_ok) reinterpret_cast<dct::MlpShape*>(shape.data())->mlp_block = -1;
+      if (!tile_ok) shape.mlp_block = -1;
     }
   }
-  int use_tile = 0;  // mlp_tile.hip runs this plan's training launches
-  const dct::MlpShape* sh() const { return reinterpret_cast<const dct::MlpShape*>(shape.data()); }
+  const dct::MlpShape* sh() const { return &shape; }
   // the trainer of a launch (mlp_select.h): launch_train and the Python query `trainer` both ask here
   dct::MlpChoice select(const dct::MlpLaunchKey& k) const {
     return dct::mlp_select_trainer(*sh(), use_wave != 0, use_tile != 0, k);
@@ -171,7 +170,7 @@ static void launch_train(const MlpPlan& plan, dct::MlpArgs& a, uintptr_t stream)
       check((int)dct::mlp_launch_block3(*sh, a, reinterpret_cast<hipStream_t>(st)), "mlp_train");
       break;
     case dct::MLP_LDS:
-      check(dct_mlp_lds_train(plan.shape.data(), &a, st), "mlp_train");
+      check(dct_mlp_lds_train(*sh, &a, st), "mlp_train");
       break;
     case dct::MLP_NONE:
       throw std::runtime_error(std::string("no fused MLP trainer takes this launch: ") + c.why_none);
@@ -353,7 +352,7 @@ PYBIND11_MODULE(_dct_native, m) {
             a.loss_kind = loss_kind;
             a.eval_acc = P<float>(acc_out);
             a.logits_out = P<float>(logits_out);
-            check(dct_mlp_eval(plan.shape.data(), &a, grid, reinterpret_cast<void*>(stream)), "mlp_eval");
+            check(dct_mlp_eval(*plan.sh(), &a, grid, reinterpret_cast<void*>(stream)), "mlp_eval");
           },
           py::arg("p"), py::arg("X"), py::arg("ldx"), py::arg("Y"), py::arg("idx"), py::arg("n_items"),
           py::arg("loss_kind"), py::arg("acc_out"), py::arg("logits_out"), py::arg("grid"), py::arg("stream"));

@@ -990,8 +990,8 @@ static hipError_t launch_gemm2(dct::GemmArgs g, hipStream_t st) {
 // the executor's Adam - sums them in slice order); colsum (+)= column sums of dZ by atomics.
 // dZ [K][M], X [K][N] bf16 row-major.  Returns hipErrorInvalidValue when the shape does not take the
 // LDS-DMA kernel or the slices would not each hold >= 1 k-tile.
-extern "C" int dct_gemm_bf16_dw_partials(const uint16_t* dZ, const uint16_t* X, float* part, float* colsum, int M,
-                                         int N, int K, int splits, void* stream) {
+static int gemm_bf16_dw_partials(const uint16_t* dZ, const uint16_t* X, float* part, float* colsum, int M, int N,
+                                 int K, int splits, void* stream) {
   dct::GemmArgs g{};
   g.A = dZ; g.B = X; g.C = part; g.M = M; g.N = N; g.K = K; g.lda = M; g.ldb = N; g.ldc = N;
   g.epilogue = dct::EPI_NONE; g.out_f32 = 1; g.accumulate = 0; g.alpha = 1.0f;
@@ -1045,7 +1045,7 @@ extern "C" int dct_gemm_bf16_dw_partials_adam(const uint16_t* dZ, const uint16_t
 extern "C" int dct_gemm_bf16_dw_partials_adam_ex(const uint16_t* dZ, const uint16_t* X, float* part, float* colsum,
                                                  int M, int N, int K, int splits, const dct::AdamRange* r, int f4,
                                                  void* stream) {
-  if (!r) return dct_gemm_bf16_dw_partials(dZ, X, part, colsum, M, N, K, splits, stream);
+  if (!r) return gemm_bf16_dw_partials(dZ, X, part, colsum, M, N, K, splits, stream);
   dct::GemmArgs g{};
   g.A = dZ; g.B = X; g.C = part; g.M = M; g.N = N; g.K = K; g.lda = M; g.ldb = N; g.ldc = N;
   g.epilogue = dct::EPI_NONE; g.out_f32 = 1; g.accumulate = 0; g.alpha = 1.0f;
@@ -1085,9 +1085,6 @@ extern "C" int dct_gemm_dw_auto_splits(int M, int N, int K) {
   const int splits = std::min(nk / 8, (device_cus() + tiles - 1) / tiles);
   return splits < 1 ? 1 : splits;
 }
-
-extern "C" int dct_bias_act_bwd(const void* dY, const void* act_aux, uint16_t* dZ, float* dbias, int M, int N,
-                                int ldy, int act, int accumulate_bias, void* stream);
 
 extern "C" int dct_gemm_bf16_ex(const uint16_t* A, const uint16_t* B, void* C, const float* bias, int M, int N, int K,
                                 int lda, int ldb, int ldc, int trans_a, int trans_b, int epilogue, int out_f32,

@@ -1,4 +1,7 @@
-// C API of the general NN kernels (GEMM, loss, norm, attention, gather).
+// C API of the general launchers: GEMM, skinny layers, loss, norm, attention, TabTransformer, batch gather and
+// step bookkeeping, flat Adam, the xGMI helpers.  Every unit that defines one of them includes this header, so a
+// declaration that disagrees with its definition does not compile (tests/test_native_api_cpu.py).  The small-MLP
+// trainers' API is mlp_fused.h.
 #pragma once
 #include <stdint.h>
 #include "knobs.h"
@@ -70,8 +73,11 @@ struct AdamRange {
 }  // namespace dct
 
 extern "C" {
-// dW = dZ^T X as split-K partials (dct_gemm_bf16_dw_partials) with Adam over r's range in extra
-// workgroups of the same launch, co-resident with the GEMM tiles (r == nullptr: the GEMM alone)
+// dW = dZ^T X as `splits` split-K slices stored to part[splits][M][N] (no reduce: the consumer - the
+// executor's Adam - sums them in slice order; colsum (+)= column sums of dZ by atomics; dZ [K][M], X [K][N]
+// bf16 row-major) with Adam over r's range in extra workgroups of the same launch, co-resident with the GEMM
+// tiles (r == nullptr: the GEMM alone).  hipErrorInvalidValue when the shape does not take the LDS-DMA
+// kernel or the slices would not each hold >= 1 k-tile.
 int dct_gemm_bf16_dw_partials_adam(const uint16_t* dZ, const uint16_t* X, float* part, float* colsum, int M, int N,
                                    int K, int splits, const dct::AdamRange* r, void* stream);
 // the same with the Adam body picked: f4 = 0 one element per thread (the executor's), 1 float4
@@ -114,8 +120,6 @@ int dct_skinny_dx(const uint16_t* dZ, const uint16_t* W, const uint16_t* aux, ui
                   void* stream);
 int dct_skinny_dw(const uint16_t* dZ, const uint16_t* X, float* dW, float* db, int B, int K, int C, void* stream);
 int dct_skinny_head_supported(int K, int C);
-int dct_gemm_bf16_dw_partials(const uint16_t* dZ, const uint16_t* X, float* part, float* colsum, int M, int N, int K,
-                              int splits, void* stream);
 int dct_gemm_dw_auto_splits(int M, int N, int K);
 int dct_skinny_head(const uint16_t* H, const uint16_t* W, const float* bias, const int* labels, uint16_t* dH,
                     float* dW, float* db, float* loss_sum, int B, int K, int C, float grad_scale, int loss_kind,
@@ -128,6 +132,10 @@ int dct_bias_act_bwd(const void* dY, const void* act_aux, uint16_t* dZ, float* d
 // dlogits = dL/dz * grad_scale (bf16 if logits_bf16 else fp32).
 int dct_loss_fwd_bwd(const void* logits, int logits_bf16, const int* labels, void* dlogits, float* loss_sum,
                      float* correct_sum, int M, int C, float grad_scale, int loss_kind, void* stream);
+// the same with the loss sum scaled: *loss_sum += loss_scale * (the rows' loss)
+int dct_loss_fwd_bwd_ex(const void* logits, int logits_bf16, const int* labels, void* dlogits, float* loss_sum,
+                        float* correct_sum, int M, int C, float grad_scale, int loss_kind, float loss_scale,
+                        void* stream);
 int dct_layernorm_fwd(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int M, int N,
                       float eps, int in_bf16, int out_bf16, void* stream);
 int dct_layernorm_bwd(const void* dy, const void* x, const float* w, const float* mean, const float* rstd, void* dx,
@@ -171,6 +179,43 @@ int dct_gemm_bf16_dw_grouped_embed(int n, const uint16_t* const* dZ, const uint1
                                    const float* ex, const float* edh, float* edE, float* edc, int eB, int eF,
                                    void* stream);
 int dct_gather_rows(const void* src, const int* idx, void* dst, int64_t n_rows, int row_bytes, void* stream);
+// Step bookkeeping of the graph-captured training steps (step_kernels.hip).
+// batch gather: row r (< B) of xdst / ydst is dataset row idx[(*cursor) * stride + r] (wrapping inside
+// [0, n_items) for a partial last batch); 16-byte copies (row_bytes % 16 == 0, X and xdst 16-B aligned)
+int dct_gather_batch(const void* X, int row_bytes, const int* Y, const int* idx, const int* cursor, int stride,
+                     int B, int n_items, void* xdst, int* ydst, void* stream);
+// the same with the step prologue riding along: *step_counter += 1 (when set) and
+// zero: buffer base; nr ranges [off[q], off[q] + cnt[q]) of it (off[q] % 4 == 0), nr <= 4
+int dct_gather_batch_step_ranges(const void* X, int row_bytes, const int* Y, const int* idx, const int* cursor,
+                                 int stride, int B, int n_items, void* xdst, int* ydst, int* step_counter, float* zero,
+                                 int nr, const int64_t* off, const int64_t* cnt, void* stream);
+// prologue of the graph-replayed autograd step: int64 rows idx[(*cursor) * B + r] -> xdst / ydst,
+// *step_counter += 1, zero[0, zero_n) cleared
+int dct_ag_step_prologue(const void* X, int row_bytes, const int64_t* Y, const int64_t* idx, const int* cursor, int B,
+                         int64_t n_items, void* xdst, int64_t* ydst, int* step_counter, float* zero, int64_t zero_n,
+                         void* stream);
+// Zero n fp32 values with a kernel (graph-captured steps: a kernel node instead of a memset node)
+int dct_zero_f32(float* p, int64_t n, void* stream);
+// step epilogue: loss_out[*cursor] = *slot (inside loss_cap), *cursor += 1
+int dct_step_end(int* cursor, const float* slot, float* loss_out, int loss_cap, void* stream);
+// Flat Adam over [0, n) (optim.hip): fp32 master update + optional bf16 shadow p_bf16; step t, or the device
+// step_counter when set
+int dct_adam_flat(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                  float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
+                  const int* step_counter, void* stream);
+// the same + the step epilogue in its first thread (cursor set: loss_out[*cursor] = *loss_slot, cursor += 1)
+int dct_adam_flat_step(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                       float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
+                       const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
+                       void* stream);
+// dct_adam_flat_step with up to three gradient ranges read from split-K partials of up to 8 slices
+// (see AdamArgs)
+int dct_adam_flat_step_parts(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                             float b1, float b2, float eps, float wd, float grad_scale, int decoupled,
+                             const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
+                             int loss_cap, int nparts, const int64_t* part_off, const int64_t* part_n,
+                             const float* const* part, const int* part_splits, void* stream);
+int dct_f32_to_bf16(const float* in, uint16_t* out, int64_t n, void* stream);
 // device-side barrier of the xGMI peer exchange (step_kernels.hip; barrier slots at byte offset off)
 int dct_xg_barrier(void* recv, void* const* peers, int64_t off, unsigned* status, int world, int rank, unsigned tag,
                    long long timeout_ticks, void* stream);

@@ -45,5 +45,3 @@ const Knobs& knobs() {
 }
 
 }  // namespace dct
-
-extern "C" void dct_knobs_reload() { dct::knobs_reload(); }

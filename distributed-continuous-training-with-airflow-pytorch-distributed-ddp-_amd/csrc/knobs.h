@@ -1,5 +1,5 @@
 // Process-wide tuning / A-B knobs of the native launchers.  Every DCT_* environment variable the
-// C++ side honours is read HERE, into one struct, at plan / bind time (dct_knobs_reload: the
+// C++ side honours is read HERE, into one struct, at plan / bind time (dct::knobs_reload: the
 // Python plan constructors call it - FusedMLPKernel, the step executors, the engines), never on a
 // launch path: launchers only read the struct.  Defaults are the measured-best settings; the
 // knobs exist for A/B runs, tests and debugging (README "Environment knobs"); variants that measured

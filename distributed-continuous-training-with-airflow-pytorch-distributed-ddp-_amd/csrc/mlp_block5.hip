@@ -8,9 +8,6 @@
 
 namespace dct {
 
-void mlp_launch_block5_xg(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);
-void mlp_launch_block5_b8(size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);
-
 // in-kernel data-parallel launches of this kernel: 2 .. 8 ranks (one node), train mode; the profiling
 // instantiations exist for 2 / 4 / 8
 static bool b5_xg_world_ok(int w) { return w >= 2 && w <= 8; }

@@ -1448,5 +1448,14 @@ inline void b5_launch(size_t bytes, hipStream_t st, const MlpShape& sh, const Ml
   hipLaunchKernelGGL((mlp_block5_kernel<WD, LK, PROF, ADAM, XW, RK, MB, SCH>), dim3(1), dim3(blk5::NT), bytes, st, sh, a);
 }
 
+// The launchers one mlp_block5*.hip unit hands a launch on to in another; one definition each.
+// mlp_block5_b8.hip, from mlp_launch_block5: two micro-batches per step, every world size
+void mlp_launch_block5_b8(size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);
+// mlp_block5_xg.hip, from mlp_launch_block5: the data-parallel launches at batch <= 4
+void mlp_launch_block5_xg(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);
+// mlp_block5_xgs.hip, from mlp_launch_block5_xg: the per-rank kernels at 3 / 5 / 6 / 7 ranks
+void mlp_launch_block5_xg_static(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);
+// mlp_block5_xgprof.hip, from mlp_launch_block5_xg: the profiling launches at 2 / 4 / 8 ranks
+void mlp_launch_block5_xg_prof(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);
 
 }  // namespace dct

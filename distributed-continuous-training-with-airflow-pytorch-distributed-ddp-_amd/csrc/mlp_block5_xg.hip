@@ -23,8 +23,6 @@ static void b5_launch_xg(size_t bytes, hipStream_t st, const MlpShape& sh, const
   }
 }
 
-void mlp_launch_block5_xg_static(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);
-
 // world sizes that do not divide the 16 W1 pairs per lane (3, 5, 6, 7 ranks; pair XW t + rank, the last
 // slots of some ranks empty): the reference configuration on per-rank kernels (mlp_block5_xgs.hip),
 // every other one on runtime-rank kernels with the weight-decay term compiled in (wd = 0 adds
@@ -35,8 +33,6 @@ static void b5_launch_xg_rt(size_t bytes, hipStream_t st, const MlpShape& sh, co
   else if (a.loss_kind == 0) b5_launch<true, 0, false, true, XW>(bytes, st, sh, a);
   else b5_launch<true, 1, false, true, XW>(bytes, st, sh, a);
 }
-
-void mlp_launch_block5_xg_prof(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a);
 
 void mlp_launch_block5_xg(int world, size_t bytes, hipStream_t st, const MlpShape& sh, const MlpArgs& a) {
   if (a.prof) return mlp_launch_block5_xg_prof(world, bytes, st, sh, a);  // mlp_block5_xgprof.hip

@@ -36,37 +36,11 @@
 
 #include "kernels.h"
 #include "mlp_executor.h"
-#include "mlp_fused.h"
 #include "runtime.h"
 
 #ifndef EXEC_DX_NT
 #define EXEC_DX_NT 1
 #endif
-
-extern "C" {
-int dct_gather_batch(const void* X, int row_bytes, const int* Y, const int* idx, const int* cursor, int stride,
-                     int B, int n_items, void* xdst, int* ydst, void* stream);
-int dct_gather_batch_step(const void* X, int row_bytes, const int* Y, const int* idx, const int* cursor, int stride,
-                          int B, int n_items, void* xdst, int* ydst, int* step_counter, float* zero,
-                          int64_t zero_n, void* stream);
-int dct_gather_batch_step_ranges(const void* X, int row_bytes, const int* Y, const int* idx, const int* cursor,
-                                 int stride, int B, int n_items, void* xdst, int* ydst, int* step_counter, float* zero,
-                                 int nr, const int64_t* off, const int64_t* cnt, void* stream);
-int dct_loss_fwd_bwd_ex(const void* logits, int logits_bf16, const int* labels, void* dlogits, float* loss_sum,
-                        float* correct_sum, int M, int C, float grad_scale, int loss_kind, float loss_scale,
-                        void* stream);
-int dct_adam_flat_step(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
-                       float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
-                       const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
-                       void* stream);
-int dct_zero_f32(float* p, int64_t n, void* stream);
-int dct_step_end(int* cursor, const float* slot, float* loss_out, int loss_cap, void* stream);
-int dct_adam_flat_step_parts(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
-                             float b1, float b2, float eps, float wd, float grad_scale, int decoupled,
-                             const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
-                             int loss_cap, int nparts, const int64_t* part_off, const int64_t* part_n,
-                             const float* const* part, const int* part_splits, void* stream);
-}
 
 namespace dct {
 

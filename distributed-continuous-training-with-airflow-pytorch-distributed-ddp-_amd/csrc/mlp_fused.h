@@ -1,4 +1,5 @@
-// Host/device-shared descriptors of the fused MLP kernels (see mlp_fused_impl.h).
+// Host/device-shared descriptors of the fused MLP kernels (see mlp_fused_impl.h) and the C API of the small-MLP
+// trainers; the general launchers (GEMM, Adam, step kernels, ...) are kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,7 +12,7 @@ constexpr int MLP_MAXL = 4;
 constexpr size_t MLP_LDS_BUDGET = 160 * 1024;  // bytes of LDS one workgroup of the LDS trainer / evaluator may lay out
 
 // Everything a launch needs about one MLP architecture, computed once on the host
-// (dct_mlp_make_shape): LDS layout, per-layer work split of the forward / dX phases and
+// (mlp_make_shape): LDS layout, per-layer work split of the forward / dX phases and
 // the ownership of weight blocks for the dW + Adam phase.
 struct MlpShape {
   int L;
@@ -125,6 +126,9 @@ struct MlpArgs {
 
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
 
+// fills *sh for dims[0 .. L] and plans of up to bmax rows per step (mlp_block = -1: auto, until the plan stamps
+// its knob copy); -1 when L is outside 2 .. MLP_MAXL, else 0 with sh->supported set
+int mlp_make_shape(MlpShape* sh, const int* dims, int L, int bmax);
 hipError_t mlp_launch_train_L2(const MlpShape& sh, const MlpArgs& a, hipStream_t st);
 hipError_t mlp_launch_train_L3(const MlpShape& sh, const MlpArgs& a, hipStream_t st);
 hipError_t mlp_launch_train_L4(const MlpShape& sh, const MlpArgs& a, hipStream_t st);
@@ -148,11 +152,9 @@ hipError_t mlp_launch_eval_L4(const MlpShape& sh, const MlpArgs& a, int grid, hi
 }  // namespace dct
 
 extern "C" {
-int dct_mlp_shape_size();
-int dct_mlp_make_shape(void* out, const int* dims, int L, int bmax);
 int dct_mlp_select(const dct::MlpShape* sh, int* nt, int* maxblk);
-int dct_mlp_lds_train(const void* shape, const dct::MlpArgs* a, void* stream);  // the generic LDS trainer
-int dct_mlp_eval(const void* shape, const dct::MlpArgs* a, int grid, void* stream);
+int dct_mlp_lds_train(const dct::MlpShape& sh, const dct::MlpArgs* a, void* stream);  // the generic LDS trainer
+int dct_mlp_eval(const dct::MlpShape& sh, const dct::MlpArgs* a, int grid, void* stream);
 int dct_mlp_wave_supported(const int* dims, int L, int B);
 // rows != 0: the row-parallel kernels (mlp_select.h MLP_WAVE_ROWS), else the single-wave kernel
 int dct_mlp_wave_train(const int* dims, int L, const dct::MlpArgs* a, int rows, void* stream);
@@ -161,16 +163,4 @@ size_t dct_mlp_xg_slab_granules(const int* dims, int L);
 int dct_mlp_tile_supported(const int* dims, int L);
 long long dct_mlp_tile_ws_floats(const int* dims, int L, int B);
 int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream);
-int dct_adam_flat(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
-                  float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
-                  const int* step_counter, void* stream);
-int dct_f32_to_bf16(const float* in, uint16_t* out, int64_t n, void* stream);
-int dct_zero_f32(float* p, int64_t n, void* stream);
-int dct_adam_flat_step(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
-                       float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
-                       const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
-                       void* stream);
-int dct_ag_step_prologue(const void* X, int row_bytes, const int64_t* Y, const int64_t* idx, const int* cursor, int B,
-                         int64_t n_items, void* xdst, int64_t* ydst, int* step_counter, float* zero, int64_t zero_n,
-                         void* stream);
 }

@@ -125,12 +125,6 @@ using dct::MlpShape;
 
 extern "C" {
 
-int dct_mlp_shape_size() { return (int)sizeof(MlpShape); }
-
-int dct_mlp_make_shape(void* out, const int* dims, int L, int bmax) {
-  return dct::mlp_make_shape(reinterpret_cast<MlpShape*>(out), dims, L, bmax);
-}
-
 int dct_mlp_select(const MlpShape* sh, int* nt, int* maxblk) {
   *nt = sh->nt;
   *maxblk = sh->maxq;
@@ -138,8 +132,7 @@ int dct_mlp_select(const MlpShape* sh, int* nt, int* maxblk) {
 }
 
 // the generic LDS trainer: no exchange, no staged batches (mlp_select.h sends those elsewhere)
-int dct_mlp_lds_train(const void* shape, const MlpArgs* a, void* stream) {
-  const MlpShape& sh = *reinterpret_cast<const MlpShape*>(shape);
+int dct_mlp_lds_train(const MlpShape& sh, const MlpArgs* a, void* stream) {
   if (!sh.supported) return (int)hipErrorInvalidValue;
   if (a->B < 1 || a->B > sh.bmax || a->xg_world > 1 || a->stage) return (int)hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -151,8 +144,7 @@ int dct_mlp_lds_train(const void* shape, const MlpArgs* a, void* stream) {
   }
 }
 
-int dct_mlp_eval(const void* shape, const MlpArgs* a, int grid, void* stream) {
-  const MlpShape& sh = *reinterpret_cast<const MlpShape*>(shape);
+int dct_mlp_eval(const MlpShape& sh, const MlpArgs* a, int grid, void* stream) {
   if ((size_t)sh.lds_floats * 4 > dct::MLP_LDS_BUDGET) return (int)hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   switch (sh.L) {

@@ -81,6 +81,6 @@ extern "C" int dct_mlp_supported(const int* dims, int L, int batch) {
   if (L < 1 || batch < 1) return 0;
   if (batch > 16) return dct_mlp_tile_ws_floats(dims, L, batch) > 0 ? 1 : 0;  // the batch-tiled trainer
   dct::MlpShape sh;
-  if (dct_mlp_make_shape(&sh, dims, L, batch <= 4 ? 4 : 16) != 0) return 0;
+  if (dct::mlp_make_shape(&sh, dims, L, batch <= 4 ? 4 : 16) != 0) return 0;
   return sh.supported;
 }

@@ -62,8 +62,6 @@ int dct_adam_flat_step(float* p, const float* g, float* m, float* v, uint16_t* p
   return (int)hipGetLastError();
 }
 
-// dct_adam_flat_step with up to three gradient ranges read from split-K partials of up to 8 slices
-// (see AdamArgs)
 int dct_adam_flat_step_parts(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
                              float b1, float b2, float eps, float wd, float grad_scale, int decoupled,
                              const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "dct_common.h"
+#include "kernels.h"
 
 namespace dct {
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "dct_common.h"
+#include "kernels.h"
 
 namespace dct {
 
@@ -87,21 +88,6 @@ __global__ __launch_bounds__(256) void ag_prologue_kernel(const uint4* __restric
     xdst[e] = X[(size_t)row * row_vec + v];
     if (v == 0) ydst[r] = Y[row];
   }
-}
-
-// step prologue: Adam step counter += 1 (read by adam_flat), loss/correct sums = 0
-__global__ void step_begin_kernel(int* step_counter, float* stats) {
-  if (threadIdx.x == 0) {
-    step_counter[0] += 1;
-    stats[0] = 0.f;
-    stats[1] = 0.f;
-  }
-}
-
-// after the loss kernel: the batch-mean loss goes into the gradient buffer's extra slot so
-// the DDP all-reduce averages it across ranks together with the gradients (sync_dist)
-__global__ void loss_to_slot_kernel(const float* stats, float* slot, float inv_rows) {
-  if (threadIdx.x == 0) slot[0] = stats[0] * inv_rows;
 }
 
 // step epilogue: loss_out[*cursor] = reduced loss, cursor += 1
@@ -258,7 +244,6 @@ int dct_reducer_check(unsigned long long* s, void* stream) {
   return (int)hipGetLastError();
 }
 
-// zero: buffer base; nr ranges [off[q], off[q] + cnt[q]) of it (off[q] % 4 == 0), nr <= 4
 int dct_gather_batch_step_ranges(const void* X, int row_bytes, const int* Y, const int* idx, const int* cursor,
                                  int stride, int B, int n_items, void* xdst, int* ydst, int* step_counter, float* zero,
                                  int nr, const int64_t* off, const int64_t* cnt, void* stream) {
@@ -286,16 +271,7 @@ int dct_gather_batch_step_ranges(const void* X, int row_bytes, const int* Y, con
   return (int)hipGetLastError();
 }
 
-int dct_gather_batch_step(const void* X, int row_bytes, const int* Y, const int* idx, const int* cursor, int stride,
-                          int B, int n_items, void* xdst, int* ydst, int* step_counter, float* zero,
-                          int64_t zero_n, void* stream) {
-  const int64_t off = 0;
-  return dct_gather_batch_step_ranges(X, row_bytes, Y, idx, cursor, stride, B, n_items, xdst, ydst, step_counter,
-                                      zero, zero ? 1 : 0, &off, &zero_n, stream);
-}
-
-// Zero n fp32 values with a kernel (graph-captured steps: a kernel node instead of a memset node,
-// see gather_batch_kernel).
+// a kernel node instead of a memset node in graph-captured steps: see gather_batch_kernel
 int dct_zero_f32(float* p, int64_t n, void* stream) {
   if (n <= 0) return 0;
   if (((uintptr_t)p) & 15) return (int)hipErrorInvalidValue;
@@ -312,8 +288,8 @@ int dct_zero_f32(float* p, int64_t n, void* stream) {
 
 int dct_gather_batch(const void* X, int row_bytes, const int* Y, const int* idx, const int* cursor, int stride,
                      int B, int n_items, void* xdst, int* ydst, void* stream) {
-  return dct_gather_batch_step(X, row_bytes, Y, idx, cursor, stride, B, n_items, xdst, ydst, nullptr, nullptr, 0,
-                               stream);
+  return dct_gather_batch_step_ranges(X, row_bytes, Y, idx, cursor, stride, B, n_items, xdst, ydst, nullptr, nullptr,
+                                      0, nullptr, nullptr, stream);
 }
 
 int dct_ag_step_prologue(const void* X, int row_bytes, const int64_t* Y, const int64_t* idx, const int* cursor, int B,
@@ -329,18 +305,6 @@ int dct_ag_step_prologue(const void* X, int row_bytes, const int64_t* Y, const i
   grid = grid > 2048 ? 2048 : (grid < 1 ? 1 : grid);
   hipLaunchKernelGGL(dct::ag_prologue_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      (const uint4*)X, rv, Y, idx, cursor, B, n_items, (uint4*)xdst, ydst, step_counter, zero, zero_n);
-  return (int)hipGetLastError();
-}
-
-int dct_step_begin(int* step_counter, float* stats, void* stream) {
-  hipLaunchKernelGGL(dct::step_begin_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                     step_counter, stats);
-  return (int)hipGetLastError();
-}
-
-int dct_loss_to_slot(const float* stats, float* slot, float inv_rows, void* stream) {
-  hipLaunchKernelGGL(dct::loss_to_slot_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), stats,
-                     slot, inv_rows);
   return (int)hipGetLastError();
 }
 

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "dct_common.h"
+#include "kernels.h"
 
 namespace dct {
 namespace ttb {

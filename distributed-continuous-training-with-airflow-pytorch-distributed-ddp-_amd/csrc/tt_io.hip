@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "dct_common.h"
+#include "kernels.h"
 
 namespace dct {
 namespace ttio {

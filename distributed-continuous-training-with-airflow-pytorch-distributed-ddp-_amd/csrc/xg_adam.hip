@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "dct_common.h"
+#include "kernels.h"
 
 namespace dct {
 

@@ -5,7 +5,8 @@ tools/isa_same.py OLD.s NEW.s [--sub REGEX REPL]...
 Kernels are paired by demangled name; each --sub rewrites the OLD names first (a refactor that drops or
 renumbers a template argument).  A pair is identical when three texts agree once the kernel's own mangled
 name and the function index of local labels (.LBB<n>_, .Lfunc_end<n>, ...) are normalised: the code from the
-kernel's label to its .Lfunc_end, the .amdhsa_kernel descriptor, and the kernel's metadata entry (register,
+kernel's label to its .Lfunc_end (without the assembler's comments, which carry function indices too and move
+when a unit gains or loses a kernel), the .amdhsa_kernel descriptor, and the kernel's metadata entry (register,
 spill, LDS and scratch figures).  Prints one line per kernel - name, instruction count, identical yes / no -
 and the first differing lines of a pair that is not; exit status 1 if any pair differs or is unpaired.
 tools/isa_mix.py shows the opcode mix of a differing pair."""
@@ -36,6 +37,7 @@ def kernels(path):
         desc = s[j:s.index(".end_amdhsa_kernel", j)]
         (ent,) = [e for e in entries if re.search(r"^    \.name: +" + re.escape(n) + "$", e, re.M)]
         texts = []
+        code = re.sub(r"[ \t]*;.*", "", code)  # assembler comments name other blocks by function index (BB<n>_<k>)
         for t in (code, desc, ent):
             t = t.replace(n, "KERNEL")
             t = re.sub(r"\.L([A-Za-z_]+?)(\d+)(_\d+)?\b", lambda m: ".L" + m.group(1) + "N" + (m.group(3) or ""), t)
