@@ -418,6 +418,121 @@ PYBIND11_MODULE(_dct_native, m) {
                                                   reinterpret_cast<void*>(stream)),
                 "gemm_bf16_dw_partials_adam");
         });
+  // ---- test-only faces of the wide-MLP step's launchers (tests/test_wide_step_kernels_gpu.py): thin lambdas over
+  // kernels.h, every field an argument, so each launcher is checked on its own against an fp64 reference
+  py::class_<dct::AdamRange>(m, "AdamRange")
+      .def(py::init([](uintptr_t p, uintptr_t g, uintptr_t mo, uintptr_t vo, uintptr_t p_bf16, int64_t n, float lr,
+                       float b1, float b2, float eps, float wd, float grad_scale, int decoupled,
+                       uintptr_t step_counter, const std::vector<int64_t>& part_off,
+                       const std::vector<int64_t>& part_n, const std::vector<uintptr_t>& part,
+                       const std::vector<int>& part_splits, int64_t lo, int64_t hi) {
+             const size_t np = part_off.size();
+             if (np > 3 || part_n.size() != np || part.size() != np || part_splits.size() != np)
+               throw std::invalid_argument("AdamRange: at most 3 part ranges, lists of one length");
+             dct::AdamRange r{};
+             r.p = P<float>(p); r.g = P<const float>(g); r.m = P<float>(mo); r.v = P<float>(vo);
+             r.p_bf16 = P<uint16_t>(p_bf16); r.n = n;
+             r.lr = lr; r.b1 = b1; r.b2 = b2; r.eps = eps; r.wd = wd; r.grad_scale = grad_scale;
+             r.decoupled = decoupled;
+             r.step_counter = P<const int>(step_counter);
+             r.nparts = (int)np;
+             for (size_t q = 0; q < np; ++q) {
+               r.part_off[q] = part_off[q]; r.part_n[q] = part_n[q]; r.part[q] = P<const float>(part[q]);
+               r.part_splits[q] = part_splits[q];
+             }
+             r.lo = lo; r.hi = hi;
+             return r;
+           }),
+           py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
+           py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("grad_scale"), py::arg("decoupled"),
+           py::arg("step_counter"), py::arg("part_off"), py::arg("part_n"), py::arg("part"), py::arg("part_splits"),
+           py::arg("lo"), py::arg("hi"));
+  m.def("adam_range",
+        [](const dct::AdamRange& r, uintptr_t cursor, uintptr_t loss_slot, uintptr_t loss_out, int loss_cap,
+           uintptr_t stream) {
+          check(dct_adam_range(&r, P<int>(cursor), P<const float>(loss_slot), P<float>(loss_out), loss_cap,
+                               reinterpret_cast<void*>(stream)),
+                "adam_range");
+        },
+        py::arg("r"), py::arg("cursor"), py::arg("loss_slot"), py::arg("loss_out"), py::arg("loss_cap"),
+        py::arg("stream"));
+  m.def("adam_flat_step_parts",
+        [](uintptr_t p, uintptr_t g, uintptr_t mo, uintptr_t vo, uintptr_t p_bf16, int64_t n, float lr, float b1,
+           float b2, float eps, float wd, float grad_scale, int decoupled, uintptr_t step_counter, uintptr_t cursor,
+           uintptr_t loss_slot, uintptr_t loss_out, int loss_cap, const std::vector<int64_t>& part_off,
+           const std::vector<int64_t>& part_n, const std::vector<uintptr_t>& part,
+           const std::vector<int>& part_splits, uintptr_t stream) {
+          const size_t np = part_off.size();
+          if (part_n.size() != np || part.size() != np || part_splits.size() != np)
+            throw std::invalid_argument("adam_flat_step_parts: list lengths differ");
+          std::vector<const float*> pp(np);
+          for (size_t q = 0; q < np; ++q) pp[q] = P<const float>(part[q]);
+          check(dct_adam_flat_step_parts(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo),
+                                         P<uint16_t>(p_bf16), n, lr, b1, b2, eps, wd, grad_scale, decoupled,
+                                         P<const int>(step_counter), P<int>(cursor), P<const float>(loss_slot),
+                                         P<float>(loss_out), loss_cap, (int)np, part_off.data(), part_n.data(),
+                                         pp.data(), part_splits.data(), reinterpret_cast<void*>(stream)),
+                "adam_flat_step_parts");
+        },
+        py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
+        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("grad_scale"), py::arg("decoupled"),
+        py::arg("step_counter"), py::arg("cursor"), py::arg("loss_slot"), py::arg("loss_out"), py::arg("loss_cap"),
+        py::arg("part_off"), py::arg("part_n"), py::arg("part"), py::arg("part_splits"), py::arg("stream"));
+  // r = None: the GEMM alone
+  m.def("gemm_bf16_dw_partials_adam",
+        [](uintptr_t dz, uintptr_t x, uintptr_t part, uintptr_t colsum, int M, int N, int K, int splits,
+           const dct::AdamRange* r, int f4, uintptr_t stream) {
+          check(dct_gemm_bf16_dw_partials_adam_ex(P<const uint16_t>(dz), P<const uint16_t>(x), P<float>(part),
+                                                  P<float>(colsum), M, N, K, splits, r, f4,
+                                                  reinterpret_cast<void*>(stream)),
+                "gemm_bf16_dw_partials_adam");
+        },
+        py::arg("dz"), py::arg("x"), py::arg("part"), py::arg("colsum"), py::arg("M"), py::arg("N"), py::arg("K"),
+        py::arg("splits"), py::arg("r").none(true), py::arg("f4"), py::arg("stream"));
+  // nz = len(zoff) (the launcher refuses more than the 4 the struct holds)
+  m.def("gemm_bf16_gather_fwd",
+        [](uintptr_t X, int ldx, uintptr_t W, uintptr_t C, uintptr_t bias, int M, int N, int K, int epilogue,
+           uintptr_t aux, uintptr_t idx, uintptr_t cursor, int stride, int n_items, uintptr_t a_out, uintptr_t Y,
+           uintptr_t ydst, uintptr_t step_counter, uintptr_t zero, const std::vector<int64_t>& zoff,
+           const std::vector<int64_t>& zcnt, uintptr_t stream) {
+          if (zoff.size() != zcnt.size()) throw std::invalid_argument("gemm_bf16_gather_fwd: list lengths differ");
+          dct::GatherFwd ga{};
+          ga.idx = P<const int>(idx); ga.cursor = P<const int>(cursor); ga.stride = stride; ga.n_items = n_items;
+          ga.a_out = P<uint16_t>(a_out); ga.Y = P<const int>(Y); ga.ydst = P<int>(ydst);
+          ga.step_counter = P<int>(step_counter); ga.zero = P<float>(zero);
+          ga.nz = (int)zoff.size();
+          for (size_t q = 0; q < zoff.size() && q < 4; ++q) { ga.zoff[q] = zoff[q]; ga.zcnt[q] = zcnt[q]; }
+          check(dct_gemm_bf16_gather_fwd(P<const uint16_t>(X), ldx, P<const uint16_t>(W), P<uint16_t>(C),
+                                         P<const float>(bias), M, N, K, epilogue, P<void>(aux), &ga,
+                                         reinterpret_cast<void*>(stream)),
+                "gemm_bf16_gather_fwd");
+        },
+        py::arg("X"), py::arg("ldx"), py::arg("W"), py::arg("C"), py::arg("bias"), py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("epilogue"), py::arg("aux"), py::arg("idx"), py::arg("cursor"), py::arg("stride"),
+        py::arg("n_items"), py::arg("a_out"), py::arg("Y"), py::arg("ydst"), py::arg("step_counter"),
+        py::arg("zero"), py::arg("zoff"), py::arg("zcnt"), py::arg("stream"));
+  // nr = len(off); no step counter, no ranges: dct_gather_batch
+  m.def("gather_batch_step_ranges",
+        [](uintptr_t X, int row_bytes, uintptr_t Y, uintptr_t idx, uintptr_t cursor, int stride, int B, int n_items,
+           uintptr_t xdst, uintptr_t ydst, uintptr_t step_counter, uintptr_t zero, const std::vector<int64_t>& off,
+           const std::vector<int64_t>& cnt, uintptr_t stream) {
+          if (off.size() != cnt.size()) throw std::invalid_argument("gather_batch_step_ranges: list lengths differ");
+          check(dct_gather_batch_step_ranges(P<const void>(X), row_bytes, P<const int>(Y), P<const int>(idx),
+                                             P<const int>(cursor), stride, B, n_items, P<void>(xdst), P<int>(ydst),
+                                             P<int>(step_counter), P<float>(zero), (int)off.size(), off.data(),
+                                             cnt.data(), reinterpret_cast<void*>(stream)),
+                "gather_batch_step_ranges");
+        },
+        py::arg("X"), py::arg("row_bytes"), py::arg("Y"), py::arg("idx"), py::arg("cursor"), py::arg("stride"),
+        py::arg("B"), py::arg("n_items"), py::arg("xdst"), py::arg("ydst"), py::arg("step_counter"), py::arg("zero"),
+        py::arg("off"), py::arg("cnt"), py::arg("stream"));
+  m.def("step_end",
+        [](uintptr_t cursor, uintptr_t slot, uintptr_t loss_out, int loss_cap, uintptr_t stream) {
+          check(dct_step_end(P<int>(cursor), P<const float>(slot), P<float>(loss_out), loss_cap,
+                             reinterpret_cast<void*>(stream)),
+                "step_end");
+        },
+        py::arg("cursor"), py::arg("slot"), py::arg("loss_out"), py::arg("loss_cap"), py::arg("stream"));
   m.def("ag_step_prologue",
         [](uintptr_t X, int row_bytes, uintptr_t Y, uintptr_t idx, uintptr_t cursor, int B, int64_t n_items,
            uintptr_t xdst, uintptr_t ydst, uintptr_t step_counter, uintptr_t zero, int64_t zero_n, uintptr_t stream) {
