@@ -1151,6 +1151,9 @@ static int tt_block_fwd_impl(const uintptr_t* p, int n_ptrs, int Bsz, int T, int
   a.qkv = (uint16_t*)p[16]; a.o = (uint16_t*)p[17]; a.lse = (float*)p[18];
   a.h1 = (float*)p[19]; a.a2 = (uint16_t*)p[20]; a.mean2 = (float*)p[21]; a.rstd2 = (float*)p[22];
   a.f = (uint16_t*)p[23]; a.pre = (uint16_t*)p[24]; a.out = (float*)p[25]; a.wT = (uint16_t*)p[26];
+  // inference writes `out` (and pool) alone: layer_norm_rows stores the statistics wherever it is handed a
+  // destination, Args::save or not, so a caller's mean / rstd buffers are withheld from it here
+  if (!save) a.mean1 = a.rstd1 = a.mean2 = a.rstd2 = nullptr;
   a.prof = n_ptrs == 28 ? (uint64_t*)p[27] : nullptr;
   a.pool = pool;
   if (pool && (((uintptr_t)pool) & 15)) return (int)hipErrorInvalidValue;
