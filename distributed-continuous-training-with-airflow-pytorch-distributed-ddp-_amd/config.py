@@ -62,6 +62,8 @@ class OptimConfig:
     betas: Sequence[float] = (0.9, 0.999)
     eps: float = 1e-8
     weight_decay: float = 0.0
+    gradient_clip_val: Optional[float] = None  # Trainer(gradient_clip_val): None or 0 = no clipping
+    gradient_clip_algorithm: str = "norm"  # norm (global L2 norm, clip_grad_norm_) | value (clip_grad_value_)
 
 
 @dataclass

@@ -36,10 +36,17 @@ struct AdamArgs {
   int64_t part_off[3], part_n[3];
   const float* part[3];
   int part_splits[3];
+  // optional gradient clipping (adam_flat_range<.., CLIP>; last, so every other field keeps its kernel-argument
+  // offset): clip_coef = the device coefficient of dct_grad_clip_coef, multiplied into grad_scale (CLIP >= 1);
+  // clip_value > 0: g clamped to [-clip_value, clip_value] after scaling (CLIP == 2)
+  const float* clip_coef;
+  float clip_value;
 };
 
+template <bool CLAMP = false>
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamArgs& a) {
   g *= a.grad_scale;
+  if constexpr (CLAMP) g = g > a.clip_value ? a.clip_value : (g < -a.clip_value ? -a.clip_value : g);  // NaN stays
   if (a.decoupled) {
     p -= a.lr * a.wd * p;
   } else {
@@ -56,6 +63,17 @@ __device__ __forceinline__ void adam_bias_correction(AdamArgs& a) {
   const float t = (float)__hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   a.step_size = a.lr / (1.f - pow_t(log2f(a.b1), t));
   a.rbc2 = rsqrtf(1.f - pow_t(log2f(a.b2), t));
+}
+
+// what a range reads once from device memory before its first update: the step count and (CLIP) the clip coefficient
+template <int CLIP>
+__device__ __forceinline__ void adam_device_scalars(AdamArgs& a) {
+  if constexpr (CLIP == 0) {
+    adam_bias_correction(a);
+  } else {
+    if (a.step_counter) adam_bias_correction(a);
+    if (a.clip_coef) a.grad_scale *= __hip_atomic_load(a.clip_coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 // elements [lo, hi) of the flat buffers (lo % 4 == 0; hi == n or hi % 4 == 0), worked by workgroups
@@ -104,7 +122,8 @@ __device__ __forceinline__ void adam_scalar_range(AdamArgs a, int64_t lo, int64_
   }
 }
 
-template <bool PARTS, int S = 4>
+// CLIP: 0 no clipping (every launch but dct_adam_flat_step_clipped), 1 the device coefficient, 2 the clamp too
+template <bool PARTS, int S = 4, int CLIP = 0>
 __device__ __forceinline__ void adam_flat_range(AdamArgs a, int64_t lo, int64_t hi, int blk, int nblk) {
   if (a.cursor && blk == 0 && threadIdx.x == 0) {
     const int c = a.cursor[0];
@@ -114,7 +133,7 @@ __device__ __forceinline__ void adam_flat_range(AdamArgs a, int64_t lo, int64_t 
   // the device step count is read AFTER the first element's loads are issued (first pass of the loop),
   // so its memory round trip overlaps theirs: one latency before the first store instead of two
   // (a 17.7 k-parameter launch is all latency: ~4.6 -> see BASELINE.md)
-  bool pending = a.step_counter != nullptr;
+  bool pending = a.step_counter != nullptr || (CLIP != 0 && a.clip_coef != nullptr);
   const int64_t n4 = (hi < a.n ? hi : a.n) >> 2;
   const int64_t stride = (int64_t)nblk * blockDim.x;
   float4* p4 = reinterpret_cast<float4*>(a.p);
@@ -154,13 +173,13 @@ __device__ __forceinline__ void adam_flat_range(AdamArgs a, int64_t lo, int64_t 
       }
     }
     if (pending) {
-      adam_bias_correction(a);
+      adam_device_scalars<CLIP>(a);
       pending = false;
     }
-    adam_one(p.x, g.x, m.x, v.x, a);
-    adam_one(p.y, g.y, m.y, v.y, a);
-    adam_one(p.z, g.z, m.z, v.z, a);
-    adam_one(p.w, g.w, m.w, v.w, a);
+    adam_one<CLIP == 2>(p.x, g.x, m.x, v.x, a);
+    adam_one<CLIP == 2>(p.y, g.y, m.y, v.y, a);
+    adam_one<CLIP == 2>(p.z, g.z, m.z, v.z, a);
+    adam_one<CLIP == 2>(p.w, g.w, m.w, v.w, a);
     p4[i] = p;
     m4[i] = m;
     v4[i] = v;
@@ -177,10 +196,10 @@ __device__ __forceinline__ void adam_flat_range(AdamArgs a, int64_t lo, int64_t 
   const int64_t tail0 = (a.n >> 2) << 2;
   const int64_t gt = (int64_t)blk * blockDim.x + threadIdx.x;
   if (hi >= a.n && gt < a.n - tail0) {
-    if (pending) adam_bias_correction(a);
+    if (pending) adam_device_scalars<CLIP>(a);
     const int64_t i = tail0 + gt;
     float p = a.p[i], m = a.m[i], v = a.v[i];
-    adam_one(p, a.g[i], m, v, a);
+    adam_one<CLIP == 2>(p, a.g[i], m, v, a);
     a.p[i] = p;
     a.m[i] = m;
     a.v[i] = v;
@@ -191,6 +210,12 @@ __device__ __forceinline__ void adam_flat_range(AdamArgs a, int64_t lo, int64_t 
 template <bool PARTS, int S = 4>
 __global__ __launch_bounds__(256) void adam_flat_kernel(AdamArgs a) {
   adam_flat_range<PARTS, S>(a, 0, a.n, blockIdx.x, gridDim.x);
+}
+
+// the clipped step (dct_adam_flat_step_clipped): g from the flat buffer only
+template <int CLIP>
+__global__ __launch_bounds__(256) void adam_flat_clip_kernel(AdamArgs a) {
+  adam_flat_range<false, 4, CLIP>(a, 0, a.n, blockIdx.x, gridDim.x);
 }
 
 template <int S>

@@ -398,6 +398,33 @@ PYBIND11_MODULE(_dct_native, m) {
                                    reinterpret_cast<void*>(stream)),
                 "adam_flat_step");
         });
+  // gradient clipping: {norm, coef} of g on the device, and the flat Adam step that reads the coefficient
+  m.def("grad_clip_workspace_floats", &dct_grad_clip_workspace_floats);
+  m.def("grad_clip_coef",
+        [](uintptr_t g, int64_t n, float grad_scale, float max_norm, uintptr_t partial, uintptr_t ticket,
+           uintptr_t stats, uintptr_t stream) {
+          check(dct_grad_clip_coef(P<const float>(g), n, grad_scale, max_norm, P<float>(partial), P<unsigned>(ticket),
+                                   P<float>(stats), reinterpret_cast<void*>(stream)),
+                "grad_clip_coef");
+        },
+        py::arg("g"), py::arg("n"), py::arg("grad_scale"), py::arg("max_norm"), py::arg("partial"), py::arg("ticket"),
+        py::arg("stats"), py::arg("stream"));
+  m.def("adam_flat_step_clipped",
+        [](uintptr_t p, uintptr_t g, uintptr_t mo, uintptr_t vo, uintptr_t p_bf16, int64_t n, float lr, float b1,
+           float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled, uintptr_t step_counter,
+           uintptr_t cursor, uintptr_t loss_slot, uintptr_t loss_out, int loss_cap, uintptr_t clip_coef,
+           float clip_value, uintptr_t stream) {
+          check(dct_adam_flat_step_clipped(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo),
+                                           P<uint16_t>(p_bf16), n, lr, b1, b2, eps, wd, t, grad_scale, decoupled,
+                                           P<const int>(step_counter), P<int>(cursor), P<const float>(loss_slot),
+                                           P<float>(loss_out), loss_cap, P<const float>(clip_coef), clip_value,
+                                           reinterpret_cast<void*>(stream)),
+                "adam_flat_step_clipped");
+        },
+        py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
+        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("t"), py::arg("grad_scale"),
+        py::arg("decoupled"), py::arg("step_counter"), py::arg("cursor"), py::arg("loss_slot"), py::arg("loss_out"),
+        py::arg("loss_cap"), py::arg("clip_coef"), py::arg("clip_value"), py::arg("stream"));
   // Adam over [0, n) of p / g / m / v (step t read from step_counter): riding in a split-K dW launch
   // of dZ^T X (mode 0: one element per thread - the executor's body; 1: the float4 body) or as its own
   // launch (mode 2, dct_adam_range) - tests/test_packed_fp32_gpu.py compares them bit for bit
@@ -886,10 +913,11 @@ PYBIND11_MODULE(_dct_native, m) {
   py::class_<dct::MlpStepExecutor>(m, "MlpStepExecutor")
       .def(py::init<const std::vector<int>&, int, int, int, uintptr_t, uintptr_t, uintptr_t, uintptr_t, uintptr_t,
                     const std::vector<uintptr_t>&, const std::vector<uintptr_t>&, uintptr_t, uintptr_t, uintptr_t,
-                    uintptr_t, dct::BucketReducer*>(),
+                    uintptr_t, dct::BucketReducer*, float, int, uintptr_t>(),
            py::arg("dims"), py::arg("batch"), py::arg("act"), py::arg("loss_kind"), py::arg("p"), py::arg("p_bf16"),
            py::arg("g"), py::arg("m"), py::arg("v"), py::arg("acts"), py::arg("pre"), py::arg("dz0"), py::arg("dz1"),
-           py::arg("ybuf"), py::arg("stats"), py::arg("reducer") = nullptr, py::keep_alive<1, 17>())
+           py::arg("ybuf"), py::arg("stats"), py::arg("reducer") = nullptr, py::arg("clip_val") = 0.f,
+           py::arg("clip_algorithm") = 0, py::arg("clip_ws") = (uintptr_t)0, py::keep_alive<1, 17>())
       .def("set_adam", &dct::MlpStepExecutor::set_adam, py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
            py::arg("wd"), py::arg("decoupled") = 0)
       .def("step", &dct::MlpStepExecutor::step, py::arg("X"), py::arg("row_bytes"), py::arg("Y"), py::arg("idx"),

@@ -215,6 +215,19 @@ int dct_adam_flat_step_parts(float* p, const float* g, float* m, float* v, uint1
                              const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
                              int loss_cap, int nparts, const int64_t* part_off, const int64_t* part_n,
                              const float* const* part, const int* part_splits, void* stream);
+// Gradient clipping by global L2 norm (optim.hip): stats = {norm, coef} of g[0, n) on the device, norm =
+// |grad_scale| sqrt(sum g^2), coef = min(max_norm / (norm + 1e-6), 1).  partial: dct_grad_clip_workspace_floats()
+// floats; ticket: one zeroed uint32 the launch leaves zeroed.  Every sum in a fixed order: the same bits every launch.
+int dct_grad_clip_workspace_floats(void);
+int dct_grad_clip_coef(const float* g, int64_t n, float grad_scale, float max_norm, float* partial, unsigned* ticket,
+                       float* stats, void* stream);
+// dct_adam_flat_step on a clipped gradient: grad_scale is multiplied by *clip_coef (optional, read on the device:
+// stats + 1 of dct_grad_clip_coef), then clip_value > 0 clamps the scaled g to [-clip_value, clip_value].  g itself
+// is not rewritten.  Null clip_coef and clip_value == 0: dct_adam_flat_step itself.
+int dct_adam_flat_step_clipped(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                               float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
+                               const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
+                               int loss_cap, const float* clip_coef, float clip_value, void* stream);
 int dct_f32_to_bf16(const float* in, uint16_t* out, int64_t n, void* stream);
 // device-side barrier of the xGMI peer exchange (step_kernels.hip; barrier slots at byte offset off)
 int dct_xg_barrier(void* recv, void* const* peers, int64_t off, unsigned* status, int world, int rank, unsigned tag,

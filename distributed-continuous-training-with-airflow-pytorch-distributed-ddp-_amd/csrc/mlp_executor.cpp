@@ -52,11 +52,19 @@ MlpStepExecutor::MlpStepExecutor(const std::vector<int>& dims, int batch, int ac
                                  uintptr_t p_bf16, uintptr_t g, uintptr_t m, uintptr_t v,
                                  const std::vector<uintptr_t>& acts, const std::vector<uintptr_t>& pre,
                                  uintptr_t dz0, uintptr_t dz1, uintptr_t ybuf, uintptr_t stats,
-                                 BucketReducer* reducer)
-    : dims_(dims), B_(batch), act_(act), loss_kind_(loss_kind), reducer_(reducer) {
+                                 BucketReducer* reducer, float clip_val, int clip_algorithm, uintptr_t clip_ws)
+    : dims_(dims), B_(batch), act_(act), loss_kind_(loss_kind), reducer_(reducer), clip_val_(clip_val),
+      clip_algorithm_(clip_algorithm), clip_ws_(reinterpret_cast<float*>(clip_ws)) {
   knobs_reload();  // plan time: this executor keeps its own copy of the DCT_* knobs its launches read
   fused_head_knob_ = knobs().fused_head != 0;
   dw_into_adam_knob_ = knobs().dw_into_adam != 0;
+  if (!(clip_val_ >= 0.f) || clip_algorithm_ < 0 || clip_algorithm_ > 1)
+    throw std::invalid_argument("MlpStepExecutor: clip_val must be >= 0 and clip_algorithm 0 (norm) or 1 (value)");
+  if (clip_val_ > 0.f) {
+    if (clip_algorithm_ == 0 && (!clip_ws_ || (clip_ws & 15)))
+      throw std::invalid_argument("MlpStepExecutor: clipping by norm needs a 16-byte aligned clip_ws");
+    dw_into_adam_knob_ = false;  // Adam needs the whole gradient in g: no split-K slices, no riding ranges
+  }
   L_ = (int)dims.size() - 1;
   if (L_ < 1) throw std::invalid_argument("MlpStepExecutor: need at least one layer");
   if ((int)acts.size() != L_ + 1) throw std::invalid_argument("MlpStepExecutor: need L+1 activation buffers");
@@ -296,6 +304,18 @@ void MlpStepExecutor::step(uintptr_t X, int row_bytes, uintptr_t Y, uintptr_t id
     }
   }
   if (reducer_) reducer_->finalize(stream);
+  if (clip_val_ > 0.f) {  // the norm over g[0, P) (not the loss slot), then one flat Adam that reads the coefficient
+    const bool by_norm = clip_algorithm_ == 0;
+    if (by_norm)
+      ck(dct_grad_clip_coef(g_, P_, 1.0f, clip_val_, clip_ws_ + 4, reinterpret_cast<unsigned*>(clip_ws_ + 2), clip_ws_,
+                            st),
+         "grad clip");
+    ck(dct_adam_flat_step_clipped(p_, g_, m_, v_, pb_, P_, lr_, b1_, b2_, eps_, wd_, 1, 1.0f, decoupled_, sc, cur,
+                                  g_ + P_, reinterpret_cast<float*>(loss_out), loss_cap,
+                                  by_norm ? clip_ws_ + 1 : nullptr, by_norm ? 0.f : clip_val_, st),
+       "clipped adam");
+    return;
+  }
   if (adam_hi < P_) {  // the rest of Adam ([0, woff[1]) of a ridden step) + the step epilogue
     const AdamRange rr = adam_range(0, adam_hi);
     ck(dct_adam_range(&rr, cur, g_ + P_, reinterpret_cast<float*>(loss_out), loss_cap, st), "adam");

@@ -16,10 +16,15 @@ class MlpStepExecutor {
   //   acts[l] bf16 [batch][d_l] (acts[0] = gathered input, acts[L] = logits),
   //   pre[l] bf16 [batch][d_l] pre-activations (GELU only), dz0/dz1 bf16 [batch][max d],
   //   ybuf int32 [batch], stats fp32 [2].
+  // Gradient clipping (clip_val > 0; off by default): clip_algorithm 0 = by the global L2 norm of g[0, P) (the loss
+  // slot g[P] excluded), 1 = by value.  A clipped step needs the whole gradient before any Adam runs, so such an
+  // executor plans no split-K partials and no riding Adam (as under DCT_DW_INTO_ADAM=0): every dW accumulates into g,
+  // then dct_grad_clip_coef and one clipped flat Adam.  clip_ws (norm clipping): zeroed fp32 words owned by the caller,
+  // {norm, coef, ticket, pad, partials[dct_grad_clip_workspace_floats()]}.
   MlpStepExecutor(const std::vector<int>& dims, int batch, int act, int loss_kind, uintptr_t p, uintptr_t p_bf16,
                   uintptr_t g, uintptr_t m, uintptr_t v, const std::vector<uintptr_t>& acts,
                   const std::vector<uintptr_t>& pre, uintptr_t dz0, uintptr_t dz1, uintptr_t ybuf, uintptr_t stats,
-                  BucketReducer* reducer);
+                  BucketReducer* reducer, float clip_val = 0.f, int clip_algorithm = 0, uintptr_t clip_ws = 0);
   void set_adam(float lr, float b1, float b2, float eps, float wd, int decoupled);
   void set_adam_ride(bool on) { adam_ride_ = on; }
   bool adam_ride() const { return adam_ride_; }
@@ -71,6 +76,9 @@ class MlpStepExecutor {
   BucketReducer* reducer_ = nullptr;
   float lr_ = 1e-3f, b1_ = 0.9f, b2_ = 0.999f, eps_ = 1e-8f, wd_ = 0.f;
   int decoupled_ = 0;
+  float clip_val_ = 0.f;  // > 0: gradient clipping (constructor)
+  int clip_algorithm_ = 0;
+  float* clip_ws_ = nullptr;
   // split-K dW slices handed to Adam (plan_partials): device buffers [splits][M][N]
   float* part_[3] = {nullptr, nullptr, nullptr};
   int part_layer_[3] = {-1, -1, -1}, part_splits_[3] = {1, 1, 1};

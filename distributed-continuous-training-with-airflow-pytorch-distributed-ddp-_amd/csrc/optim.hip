@@ -7,6 +7,8 @@
 // (<= 2048 workgroups, grid-stride), bias correction folded into two scalars.
 // Optional outputs: a bf16 shadow copy of the updated weights for the MFMA GEMM path, and
 // gradient pre-scaling (e.g. 1/world_size when the all-reduce summed).
+// Gradient clipping: a norm kernel leaves {norm, coef} on the device and the Adam launch behind it
+// reads the coefficient (or clamps by value); the gradient buffer is not rewritten.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,6 +27,77 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* in, uint1
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = f32_to_bf16(in[i]);
 }
 
+// Global L2 norm of the flat gradient and the clip coefficient, on the device (gradient clipping by norm,
+// torch.nn.utils.clip_grad_norm_): stats = {|grad_scale| sqrt(sum g_i^2), min(max_norm / (norm + 1e-6), 1)}.
+// The Adam launch that follows reads stats[1] (AdamArgs::clip_coef), so a captured step replays with no host round trip.
+// One launch, <= CLIP_MAX_GRID workgroups (a function of n alone), every sum in a fixed order - no float atomics into
+// an accumulator, the same bits on every launch and on every rank that holds the same gradient:
+//   thread   four accumulators (one per float4 component) over its grid-stride float4s, (x + y) + (z + w), then
+//            the n % 4 tail (workgroup 0, threads 0 .. 2, one element each)
+//   wave     xor butterfly 32 .. 1 (wave_sum)
+//   group    the four wave sums through LDS, in wave order
+//   grid     one partial per workgroup; the last workgroup to arrive (agent-scope ticket, reset to 0 for the next
+//            launch or replay; nothing waits) sums them: lane l takes partials l, l + 64, .., then the butterfly.
+//            Partial and ticket are memory-side atomics ordered by s_waitcnt, and the partials are read by atomics
+//            too (as the head loss of tt_io.hip): no agent-scope fences.
+constexpr int CLIP_BLOCK = 256;     // threads of a workgroup (tests/clip_cases.py counts the additions from these)
+constexpr int CLIP_MAX_GRID = 256;  // workgroups: one per compute unit pulling on HBM; 3.4 M gradients are 13 passes
+
+struct ClipArgs {
+  const float* g;
+  int64_t n;
+  float grad_scale, max_norm;
+  float* partial;    // [CLIP_MAX_GRID]
+  unsigned* ticket;  // 0 between launches
+  float* stats;      // {norm, coef}
+};
+
+__global__ __launch_bounds__(CLIP_BLOCK) void grad_clip_coef_kernel(ClipArgs a) {
+  __shared__ float wsums[CLIP_BLOCK / 64];
+  __shared__ unsigned last;
+  const int64_t n4 = a.n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * CLIP_BLOCK;
+  const float4* g4 = reinterpret_cast<const float4*>(a.g);
+  float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
+#pragma unroll 4
+  for (int64_t i = (int64_t)blockIdx.x * CLIP_BLOCK + threadIdx.x; i < n4; i += stride) {
+    const float4 g = g4[i];
+    sx += g.x * g.x;
+    sy += g.y * g.y;
+    sz += g.z * g.z;
+    sw += g.w * g.w;
+  }
+  float s = (sx + sy) + (sz + sw);
+  if (blockIdx.x == 0 && (int64_t)threadIdx.x < a.n - (n4 << 2)) {
+    const float t = a.g[(n4 << 2) + threadIdx.x];
+    s += t * t;
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) wsums[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float v = wsums[0];
+#pragma unroll
+    for (int w = 1; w < CLIP_BLOCK / 64; ++w) v += wsums[w];
+    atomicExch(a.partial + blockIdx.x, v);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (last && threadIdx.x < 64) {
+    float t = 0.f;
+    for (unsigned i = threadIdx.x; i < gridDim.x; i += 64) t += atomicAdd(a.partial + i, 0.f);
+    t = wave_sum(t);
+    if (threadIdx.x == 0) {
+      const float norm = fabsf(a.grad_scale) * sqrtf(t);
+      const float c = a.max_norm / (norm + 1e-6f);
+      a.stats[0] = norm;
+      a.stats[1] = c > 1.0f ? 1.0f : c;  // (a NaN stays a NaN, as torch.clamp(max=1))
+      __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 }  // namespace dct
 
 static inline int grid_for(int64_t work, int block) {
@@ -34,15 +107,11 @@ static inline int grid_for(int64_t work, int block) {
   return (int)g;
 }
 
-extern "C" {
-
-int dct_adam_flat_step(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
-                       float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
-                       const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
-                       void* stream) {
-  if (n <= 0) return 0;
-  if (cursor && !loss_slot) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return (int)hipErrorInvalidValue;
+// AdamArgs of a flat step at host step count t (dct_adam_flat_step and its clipped form)
+static dct::AdamArgs flat_step_args(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                                    float b1, float b2, float eps, float wd, int64_t t, float grad_scale,
+                                    int decoupled, const int* step_counter, int* cursor, const float* loss_slot,
+                                    float* loss_out, int loss_cap) {
   dct::AdamArgs a{};
   a.p = p; a.g = g; a.m = m; a.v = v; a.p_bf16 = p_bf16; a.n = n;
   a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps; a.wd = wd;
@@ -57,8 +126,60 @@ int dct_adam_flat_step(float* p, const float* g, float* m, float* v, uint16_t* p
   a.loss_slot = loss_slot;
   a.loss_out = loss_out;
   a.loss_cap = loss_cap;
+  return a;
+}
+
+extern "C" {
+
+int dct_adam_flat_step(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                       float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
+                       const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
+                       void* stream) {
+  if (n <= 0) return 0;
+  if (cursor && !loss_slot) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return (int)hipErrorInvalidValue;
+  dct::AdamArgs a = flat_step_args(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, step_counter,
+                                   cursor, loss_slot, loss_out, loss_cap);
   hipLaunchKernelGGL(dct::adam_flat_kernel<false>, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+
+int dct_grad_clip_workspace_floats(void) { return dct::CLIP_MAX_GRID; }
+
+int dct_grad_clip_coef(const float* g, int64_t n, float grad_scale, float max_norm, float* partial, unsigned* ticket,
+                       float* stats, void* stream) {
+  if (n <= 0 || !g || !partial || !ticket || !stats || !(max_norm >= 0.f) || ((uintptr_t)g & 15))
+    return (int)hipErrorInvalidValue;
+  dct::ClipArgs a{};
+  a.g = g; a.n = n; a.grad_scale = grad_scale; a.max_norm = max_norm;
+  a.partial = partial; a.ticket = ticket; a.stats = stats;
+  int64_t grid = ((n >> 2) + dct::CLIP_BLOCK - 1) / dct::CLIP_BLOCK;
+  grid = std::min<int64_t>(std::max<int64_t>(grid, 1), dct::CLIP_MAX_GRID);
+  hipLaunchKernelGGL(dct::grad_clip_coef_kernel, dim3((unsigned)grid), dim3(dct::CLIP_BLOCK), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+
+int dct_adam_flat_step_clipped(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                               float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
+                               const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
+                               int loss_cap, const float* clip_coef, float clip_value, void* stream) {
+  if (!(clip_value >= 0.f)) return (int)hipErrorInvalidValue;
+  if (!clip_coef && clip_value == 0.f)  // no clipping: the unclipped kernel, bit for bit
+    return dct_adam_flat_step(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, step_counter,
+                              cursor, loss_slot, loss_out, loss_cap, stream);
+  if (n <= 0) return 0;
+  if (cursor && !loss_slot) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return (int)hipErrorInvalidValue;
+  dct::AdamArgs a = flat_step_args(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, step_counter,
+                                   cursor, loss_slot, loss_out, loss_cap);
+  a.clip_coef = clip_coef;
+  a.clip_value = clip_value;
+  const dim3 grid(grid_for((n + 3) / 4, 256));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (clip_value > 0.f) hipLaunchKernelGGL(dct::adam_flat_clip_kernel<2>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(dct::adam_flat_clip_kernel<1>, grid, dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
 

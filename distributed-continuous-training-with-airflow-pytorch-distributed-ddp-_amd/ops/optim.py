@@ -16,11 +16,57 @@ import torch
 from ._native import native, ptr, stream_handle
 
 
+CLIP_ALGORITHMS = ("norm", "value")
+
+
+def check_clip_args(clip_val, clip_algorithm: str):
+    """(clip_val or None, algorithm) of ``gradient_clip_val`` / ``gradient_clip_algorithm`` as Lightning reads them:
+    None or 0 is off; a negative value or an unknown algorithm raises ValueError."""
+    if clip_algorithm not in CLIP_ALGORITHMS:
+        raise ValueError(f"gradient_clip_algorithm must be one of {CLIP_ALGORITHMS}, got {clip_algorithm!r}")
+    if clip_val is None:
+        return None, clip_algorithm
+    clip_val = float(clip_val)
+    if not clip_val >= 0.0:
+        raise ValueError(f"gradient_clip_val must be >= 0, got {clip_val}")
+    return (clip_val or None), clip_algorithm
+
+
+def clip_workspace(device) -> torch.Tensor:
+    """Zeroed fp32 words of the norm kernel (csrc/optim.hip): {norm, coef, ticket, pad, one partial per workgroup}.
+    Allocated once per optimizer: a captured step graph needs static addresses, and the ticket stays 0 between
+    launches."""
+    n = 4 + (native().grad_clip_workspace_floats() if torch.device(device).type == "cuda" else 0)
+    return torch.zeros(n, dtype=torch.float32, device=device)
+
+
+def grad_clip_coef_(g: torch.Tensor, max_norm: float, ws: torch.Tensor, grad_scale: float = 1.0) -> torch.Tensor:
+    """ws[0:2] = {norm, coef} of ``torch.nn.utils.clip_grad_norm_(.., max_norm)`` over the flat gradient ``g`` scaled by
+    ``grad_scale``: norm = sqrt(sum (grad_scale g)^2), coef = min(max_norm / (norm + 1e-6), 1).  ``g`` is not
+    rewritten - the Adam step multiplies the coefficient in.  On the GPU one kernel, nothing read back; returns
+    ws[0:2] (``ws``: clip_workspace())."""
+    if g.dtype != torch.float32 or not g.is_contiguous() or ws.device != g.device or ws.dtype != torch.float32:
+        raise ValueError("grad_clip_coef_: g and ws must be contiguous fp32 on one device")
+    if not max_norm >= 0.0:
+        raise ValueError("grad_clip_coef_: max_norm must be >= 0")
+    if g.is_cuda:
+        native().grad_clip_coef(ptr(g), g.numel(), float(grad_scale), float(max_norm), ptr(ws[4:]), ptr(ws[2:]),
+                                ptr(ws), stream_handle(g.device))
+    else:
+        norm = g.norm() * abs(float(grad_scale))
+        ws[0] = norm
+        ws[1] = torch.clamp(max_norm / (norm + 1e-6), max=1.0)
+    return ws[:2]
+
+
 def adam_flat_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float,
                betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
                decoupled: bool = False, p_bf16: Optional[torch.Tensor] = None,
-               step_counter: Optional[torch.Tensor] = None):
-    """In-place Adam on flat fp32 buffers; ``step`` is the 1-based step count after this update."""
+               step_counter: Optional[torch.Tensor] = None, clip_coef: Optional[torch.Tensor] = None,
+               clip_value: float = 0.0):
+    """In-place Adam on flat fp32 buffers; ``step`` is the 1-based step count after this update.  ``clip_coef`` (a
+    one-element fp32 tensor on p's device, grad_clip_coef_'s ws[1:2]) is multiplied into ``grad_scale``;
+    ``clip_value`` > 0 clamps the scaled gradient to [-clip_value, clip_value].  ``g`` is not rewritten."""
     n = p.numel()
     for t in (g, m, v):
         if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous() or t.device != p.device:
@@ -30,12 +76,22 @@ def adam_flat_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
             raise ValueError("p_bf16 must be a bf16 buffer of the same size")
         if step_counter is not None and not (step_counter.is_cuda and step_counter.dtype == torch.int32):
             raise ValueError("step_counter must be a cuda int32 tensor")
+        if clip_coef is not None or clip_value:
+            native().adam_flat_step_clipped(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_bf16), n, float(lr),
+                                            float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                            max(1, int(step)), float(grad_scale), int(decoupled), ptr(step_counter),
+                                            0, 0, 0, 0, ptr(clip_coef), float(clip_value), stream_handle(p.device))
+            return
         native().adam_flat(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_bf16), n, float(lr), float(betas[0]),
                            float(betas[1]), float(eps), float(weight_decay), max(1, int(step)), float(grad_scale),
                            int(decoupled), ptr(step_counter), stream_handle(p.device))
         return
     b1, b2 = betas
     gg = g * grad_scale if grad_scale != 1.0 else g
+    if clip_coef is not None:
+        gg = gg * clip_coef  # (torch multiplies even by 1.0: exact)
+    if clip_value:
+        gg = gg.clamp(-clip_value, clip_value)
     if decoupled:
         p.mul_(1 - lr * weight_decay)
     elif weight_decay:
@@ -67,9 +123,14 @@ class FlatAdam:
 
     def __init__(self, flat_param: torch.Tensor, flat_grad: torch.Tensor, param_shapes: Sequence[torch.Size],
                  lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 amsgrad: bool = False):
+                 amsgrad: bool = False, clip_val: Optional[float] = None, clip_algorithm: str = "norm"):
         if amsgrad:
             raise NotImplementedError("amsgrad is not supported")
+        self.clip_val, self.clip_algorithm = check_clip_args(clip_val, clip_algorithm)
+        # {norm, coef, ..} of the last step (clipping by norm): allocated here, once - static addresses for a capture
+        self.clip_ws: Optional[torch.Tensor] = None
+        if self.clip_val is not None and self.clip_algorithm == "norm":
+            self.clip_ws = clip_workspace(flat_param.device)
         self.p = flat_param
         self.g = flat_grad
         self.m = torch.zeros_like(flat_param)
@@ -99,6 +160,23 @@ class FlatAdam:
             counter = self._device_counter()
             if bump_counter:
                 counter.add_(1)
+        clip_coef, clip_value = None, 0.0
+        if self.clip_val is not None:
+            # the gradient is clipped inside Adam (flat_g keeps the unclipped values): by norm, one kernel leaves the
+            # coefficient on the device for the Adam launch behind it - no host round trip, graph-replayable
+            if self.clip_algorithm == "norm":
+                clip_coef = grad_clip_coef_(self.g, self.clip_val, self.clip_ws, grad_scale)[1:]
+            else:
+                clip_value = self.clip_val
+        if epilogue is not None and self.clip_val is not None:
+            cursor, loss, loss_out = epilogue
+            b1, b2 = g["betas"]
+            native().adam_flat_step_clipped(ptr(self.p), ptr(self.g), ptr(self.m), ptr(self.v), ptr(self.p_bf16),
+                                            self.p.numel(), float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                                            float(g["weight_decay"]), max(1, self.step_count), float(grad_scale), 0,
+                                            ptr(counter), ptr(cursor), ptr(loss), ptr(loss_out), loss_out.numel(),
+                                            ptr(clip_coef), float(clip_value), stream_handle(self.p.device))
+            return
         if epilogue is not None:
             cursor, loss, loss_out = epilogue
             b1, b2 = g["betas"]
@@ -109,7 +187,16 @@ class FlatAdam:
                                     stream_handle(self.p.device))
             return
         adam_flat_(self.p, self.g, self.m, self.v, self.step_count, g["lr"], g["betas"], g["eps"],
-                   g["weight_decay"], grad_scale=grad_scale, p_bf16=self.p_bf16, step_counter=counter)
+                   g["weight_decay"], grad_scale=grad_scale, p_bf16=self.p_bf16, step_counter=counter,
+                   clip_coef=clip_coef, clip_value=clip_value)
+
+    def clip_stats(self):
+        """(norm, coef) of the last step's clipping by norm as Python floats (synchronises: tests and logging);
+        (nan, 1.0) when nothing computes a norm (clipping off or by value)."""
+        if self.clip_ws is None:
+            return float("nan"), 1.0
+        norm, coef = self.clip_ws[:2].tolist()
+        return norm, coef
 
     def _device_counter(self) -> torch.Tensor:
         c = getattr(self, "_counter", None)

@@ -32,7 +32,7 @@ from ..data.sampler import distributed_indices
 from ..ops._native import reload_knobs
 from ..ops.fused_mlp import FusedMLPKernel, mlp_num_params
 from ..ops.nn import BatchGather, bound_params, fold_batch_gather, join_side_work, unit_loss_seed
-from ..ops.optim import FlatAdam, adam_flat_
+from ..ops.optim import FlatAdam, adam_flat_, check_clip_args
 from ..parallel.dist import DistContext, init_native_comm
 from ..parallel.reducer import NativeBucketReducer, TorchBucketReducer, plan_buckets
 from ..utils.debug import assert_reducer_complete, check_device
@@ -543,8 +543,12 @@ class AutogradEngine(_EngineBase):
     name = "autograd"
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, bucket_cap_bytes: int = 8 << 20,
-                 first_bucket_bytes: int = 1 << 20):
+                 first_bucket_bytes: int = 1 << 20, gradient_clip_val: Optional[float] = None,
+                 gradient_clip_algorithm: str = "norm"):
         super().__init__(model, ctx, batch_size, seed)
+        # gradient clipping (Trainer(gradient_clip_val, gradient_clip_algorithm)): after the all-reduce, on the
+        # averaged gradient, inside the flat Adam - p.grad keeps the unclipped gradient (ops/optim.py)
+        self.clip_val, self.clip_algorithm = check_clip_args(gradient_clip_val, gradient_clip_algorithm)
         dev = ctx.device
         self.device = dev
         model.to(dev)
@@ -615,7 +619,8 @@ class AutogradEngine(_EngineBase):
         opt = model.configure_optimizers()
         hp = adam_hparams_from(opt)
         if hp is not None:
-            self.optimizer = FlatAdam(self.flat_p, self.flat_g, [p.shape for p in params], **hp)
+            self.optimizer = FlatAdam(self.flat_p, self.flat_g, [p.shape for p in params], clip_val=self.clip_val,
+                                      clip_algorithm=self.clip_algorithm, **hp)
             self.torch_optimizer = None
         else:
             self.optimizer = None
@@ -715,9 +720,23 @@ class AutogradEngine(_EngineBase):
         if self.optimizer is not None:
             self.optimizer.step()
         else:
+            if self.clip_val is not None:
+                if self.clip_algorithm == "norm":
+                    norm = torch.nn.utils.clip_grad_norm_(self.params, self.clip_val)
+                    self._torch_clip_stats = (norm, torch.clamp(self.clip_val / (norm + 1e-6), max=1.0))
+                else:
+                    torch.nn.utils.clip_grad_value_(self.params, self.clip_val)
             self.torch_optimizer.step()
         self._pm(4)
         return loss
+
+    def grad_clip_stats(self) -> Tuple[float, float]:
+        """(total gradient norm, clip coefficient) of the last step as Python floats; (nan, 1.0) when no norm is
+        computed (clipping off or by value).  Synchronises: for tests and logging."""
+        if self.optimizer is not None:
+            return self.optimizer.clip_stats()
+        st = getattr(self, "_torch_clip_stats", None)
+        return (float(st[0]), float(st[1])) if st is not None else (float("nan"), 1.0)
 
     def train_step(self, rows: torch.Tensor, batch_idx: int):
         """One optimizer step.  ``last_step_mode`` tells the Trainer how training_step ran:

@@ -35,7 +35,7 @@ import torch
 
 from ..data.sampler import distributed_indices
 from ..ops._native import native
-from ..ops.optim import FlatAdam
+from ..ops.optim import FlatAdam, check_clip_args, clip_workspace
 from ..parallel.dist import DistContext, init_native_comm
 from ..parallel.reducer import NativeBucketReducer, plan_buckets
 from ..utils.debug import enabled as debug_enabled
@@ -76,8 +76,12 @@ class GraphMLPEngine:
         return spec["dropout"] == 0.0 and spec["dims"][0] % 8 == 0 and batch_size >= 1
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,
-                 bucket_cap_bytes: int = 8 << 20, first_bucket_bytes: int = 1 << 20, use_graph: Optional[bool] = None):
+                 bucket_cap_bytes: int = 8 << 20, first_bucket_bytes: int = 1 << 20, use_graph: Optional[bool] = None,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm"):
         native().reload_knobs()  # bind time: the native launchers' DCT_* knobs
+        # gradient clipping: the executor then keeps every dW in g (no split-K slices handed to Adam, no riding Adam,
+        # as under DCT_DW_INTO_ADAM=0), takes the norm of g[:P] after the all-reduce and runs one clipped flat Adam
+        self.clip_val, self.clip_algorithm = check_clip_args(gradient_clip_val, gradient_clip_algorithm)
         self.model = model
         self.ctx = ctx
         self.B = int(batch_size)
@@ -134,16 +138,32 @@ class GraphMLPEngine:
             self.reducer = NativeBucketReducer(self.comm, self.g, plan,
                                                timing=reducer_timing_enabled(),
                                                check=debug_enabled())
+        clip = {}
+        self.clip_ws = None
+        if self.clip_val is not None:
+            by_norm = self.clip_algorithm == "norm"
+            self.clip_ws = clip_workspace(dev) if by_norm else None
+            clip = dict(clip_val=self.clip_val, clip_algorithm=0 if by_norm else 1,
+                        clip_ws=self.clip_ws.data_ptr() if by_norm else 0)
         self.exe = nat.MlpStepExecutor(self.dims, B, ACT_IDS["relu"], LOSS_IDS[self.loss], self.p.data_ptr(),
                                        self.p_bf16.data_ptr(), self.g.data_ptr(), self.m.data_ptr(),
                                        self.v.data_ptr(), [a.data_ptr() for a in self.acts], [],
                                        self.dz[0].data_ptr(), self.dz[1].data_ptr(), self.ybuf.data_ptr(),
-                                       self.stats.data_ptr(), self.reducer._r if self.reducer is not None else None)
+                                       self.stats.data_ptr(), self.reducer._r if self.reducer is not None else None,
+                                       **clip)
         a = adam
         self.exe.set_adam(a["lr"], a["betas"][0], a["betas"][1], a["eps"], a["weight_decay"], 0)
         self._graph = None
         self._graph_key = None
         self.graph_used = False
+
+    def grad_clip_stats(self) -> Tuple[float, float]:
+        """(total gradient norm, clip coefficient) of the last step as Python floats; (nan, 1.0) when no norm is
+        computed (clipping off or by value).  Synchronises: for tests and logging."""
+        if self.clip_ws is None:
+            return float("nan"), 1.0
+        norm, coef = self.clip_ws[:2].tolist()
+        return norm, coef
 
     # ------------------------------------------------------------------ params
     def _linear_params(self):

@@ -29,6 +29,7 @@ from ..ckpt.callbacks import ModelCheckpoint
 from ..ckpt.lightning_io import build_checkpoint, load_checkpoint, save_checkpoint
 from ..data.dataset import dataset_tensors
 from ..data.sampler import distributed_indices
+from ..ops.optim import check_clip_args
 from ..parallel.dist import DistContext, init_distributed, shutdown
 from .engines import AutogradEngine, FusedMLPEngine, adam_hparams_from
 from .graph_engine import GraphMLPEngine
@@ -67,7 +68,11 @@ class Trainer:
                  strategy: Any = "auto", logger=None, callbacks: Optional[Sequence] = None,
                  log_every_n_steps: int = 50, num_sanity_val_steps: int = 2, engine: str = "auto",
                  steps_per_launch: int = 0, enable_progress_bar: bool = True, default_root_dir: Optional[str] = None,
-                 max_steps: int = -1, fault_inject: Optional[Tuple[int, int]] = None, verbose: bool = True):
+                 max_steps: int = -1, fault_inject: Optional[Tuple[int, int]] = None, verbose: bool = True,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm"):
+        # Lightning's two arguments: None or 0 is off; ValueError for a negative value or an unknown algorithm
+        self.gradient_clip_val, self.gradient_clip_algorithm = check_clip_args(gradient_clip_val,
+                                                                               gradient_clip_algorithm)
         self.max_epochs = int(max_epochs)
         self.max_steps = int(max_steps)
         self.accelerator = accelerator
@@ -225,7 +230,13 @@ class Trainer:
         if choice == "auto":
             choice = os.environ.get("DCT_ENGINE", "auto")
         adam = adam_hparams_from(model.configure_optimizers())
+        clip = dict(gradient_clip_val=self.gradient_clip_val, gradient_clip_algorithm=self.gradient_clip_algorithm)
+        if self.gradient_clip_val is not None and choice == "fused":
+            raise RuntimeError("engine='fused' cannot clip gradients: the persistent small-MLP kernels apply Adam "
+                               "inside the launch (use engine='auto', 'graph' or 'autograd' with gradient_clip_val)")
         fused_ok = adam is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size)
+        if self.gradient_clip_val is not None:
+            fused_ok = False  # clipping: the graph engine where it applies, otherwise autograd
         if choice == "auto" and fused_ok and batch_size > 16 and GraphMLPEngine.applicable(model, ctx.device, batch_size):
             fused_ok = False  # batch > 16: the graph engine keeps the models it takes; the batch-tiled trainer the rest
         if choice in ("auto", "fused") and fused_ok:
@@ -234,12 +245,12 @@ class Trainer:
             raise RuntimeError("engine='fused' requested but the model/device/batch is not supported by it")
         if choice in ("auto", "graph") and adam is not None and GraphMLPEngine.applicable(model, ctx.device, batch_size):
             return GraphMLPEngine(model, ctx, batch_size, seed, adam, self.strategy.bucket_cap_bytes,
-                                  self.strategy.first_bucket_bytes)
+                                  self.strategy.first_bucket_bytes, **clip)
         if choice == "graph":
             raise RuntimeError("engine='graph' requested but the model/device is not supported by it")
         model.to(ctx.device)
         return AutogradEngine(model, ctx, batch_size, seed, self.strategy.bucket_cap_bytes,
-                              self.strategy.first_bucket_bytes)
+                              self.strategy.first_bucket_bytes, **clip)
 
     # ------------------------------------------------------------------ checkpoints
     def _checkpoint_dict(self, batches_in_epoch: int = 0, val_batches: int = 0) -> Dict[str, Any]:

@@ -36,6 +36,10 @@ def parse_args(argv=None):
     p.add_argument("--epochs", type=int, default=cfg.train.max_epochs)
     p.add_argument("--batch-size", type=int, default=cfg.data.batch_size)
     p.add_argument("--lr", type=float, default=cfg.optim.lr)
+    p.add_argument("--gradient-clip-val", type=float, default=cfg.optim.gradient_clip_val,
+                   help="clip gradients before the optimizer step (default: no clipping)")
+    p.add_argument("--gradient-clip-algorithm", default=cfg.optim.gradient_clip_algorithm, choices=("norm", "value"),
+                   help="norm: global L2 norm (clip_grad_norm_); value: element-wise (clip_grad_value_)")
     p.add_argument("--model", default=cfg.model.name)
     p.add_argument("--tracking-uri", default=cfg.tracking.tracking_uri)
     p.add_argument("--experiment", default=cfg.tracking.experiment_name)
@@ -95,6 +99,8 @@ def main(argv=None) -> int:
         callbacks=[checkpoint_callback],
         log_every_n_steps=a.log_every_n_steps,
         engine=a.engine,
+        gradient_clip_val=a.gradient_clip_val,
+        gradient_clip_algorithm=a.gradient_clip_algorithm,
     )
     last = os.path.join(a.model_dir, "last.ckpt")
     # --resume, or a torchrun elastic restart after a failed rank: continue from last.ckpt
