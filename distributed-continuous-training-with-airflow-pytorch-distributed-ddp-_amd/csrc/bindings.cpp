@@ -675,6 +675,18 @@ PYBIND11_MODULE(_dct_native, m) {
       py::arg("correct_sum"), py::arg("M"), py::arg("C"), py::arg("grad_scale"), py::arg("loss_kind"),
       py::arg("stream"));
   m.def(
+      "loss_fwd_bwd_ex",
+      [](uintptr_t logits, int logits_bf16, uintptr_t labels, uintptr_t dlogits, uintptr_t loss_sum,
+         uintptr_t correct_sum, int M, int C, float grad_scale, int loss_kind, float loss_scale, uintptr_t stream) {
+        check(dct_loss_fwd_bwd_ex(P<const void>(logits), logits_bf16, P<const int>(labels), P<void>(dlogits),
+                                  P<float>(loss_sum), P<float>(correct_sum), M, C, grad_scale, loss_kind, loss_scale,
+                                  reinterpret_cast<void*>(stream)),
+              "loss_fwd_bwd_ex");
+      },
+      py::arg("logits"), py::arg("logits_bf16"), py::arg("labels"), py::arg("dlogits"), py::arg("loss_sum"),
+      py::arg("correct_sum"), py::arg("M"), py::arg("C"), py::arg("grad_scale"), py::arg("loss_kind"),
+      py::arg("loss_scale"), py::arg("stream"));
+  m.def(
       "layernorm_fwd",
       [](uintptr_t x, uintptr_t w, uintptr_t b, uintptr_t y, uintptr_t mean, uintptr_t rstd, int M, int N, float eps,
          int in_bf16, int out_bf16, uintptr_t stream) {

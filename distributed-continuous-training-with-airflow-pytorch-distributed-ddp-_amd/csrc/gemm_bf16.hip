@@ -861,9 +861,16 @@ static bool gemm_v2_ok(const dct::GemmArgs& g, int ta, int tb) {
   if (g.K % dct::GBK) return false;
   auto aligned = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
   if (!aligned(g.A) || !aligned(g.B) || g.lda % 8 || g.ldb % 8) return false;
+  // gemm2_body's epilogue reads bias + col0 and residual + o0 as float4 whenever C, ldc and aux allow vector stores
+  if ((g.bias && !aligned(g.bias)) || (g.residual && !aligned(g.residual))) return false;
   if (ta && g.M % 8) return false;    // MC image of A: 8-row chunks inside [0, M)
   if (!tb && g.N % 8) return false;   // MC image of B
   return true;
+}
+
+// EPI_RELU_MASK and EPI_GELU_GRAD read aux in both kernels: a null aux is refused, not dereferenced
+static bool epilogue_aux_ok(int epilogue, const void* aux) {
+  return !((epilogue == dct::EPI_RELU_MASK || epilogue == dct::EPI_GELU_GRAD) && !aux);
 }
 
 // Two-pass split-K partials.  Auto mode takes it for <= 4 slices per tile: 1024 x 1024 x 4096 dW
@@ -1090,6 +1097,7 @@ extern "C" int dct_gemm_bf16_ex(const uint16_t* A, const uint16_t* B, void* C, c
                                 int lda, int ldb, int ldc, int trans_a, int trans_b, int epilogue, int out_f32,
                                 int accumulate, void* aux, float* colsum, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
+  if (!epilogue_aux_ok(epilogue, aux)) return (int)hipErrorInvalidValue;
   dct::GemmArgs g{};
   g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -1104,13 +1112,14 @@ extern "C" int dct_gemm_bf16_ex(const uint16_t* A, const uint16_t* B, void* C, c
     if (trans_a && !trans_b) return (int)launch_gemm2<true, false>(g, st);
     return (int)launch_gemm2<true, true>(g, st);
   }
+  // generic path: the A rows' sums come from the column-sum kernel, which takes op(A) = A^T only (trans_a: A is
+  // [K][M]).  Row sums of a row-major A have no kernel here: refuse before anything is launched.
+  if (colsum && !trans_a) return (int)hipErrorNotSupported;
   g.colsum = nullptr;
   int e = dct_gemm_bf16(A, B, C, bias, M, N, K, lda, ldb, ldc, trans_a, trans_b, epilogue, out_f32, accumulate, aux,
                         stream);
   if (e || !colsum) return e;
-  // generic path: the A rows' sums by the column-sum kernel (op(A) = A^T when trans_a: A is [K][M])
-  if (trans_a) return dct_bias_act_bwd(A, nullptr, nullptr, colsum, K, M, lda, 0, 1, stream);
-  return (int)hipErrorNotSupported;
+  return dct_bias_act_bwd(A, nullptr, nullptr, colsum, K, M, lda, 0, 1, stream);
 }
 
 // Grouped dW: C_i (+)= dZ_i^T X_i (+ colsum_i += column sums of dZ_i) for i < n (n <= 4), one
@@ -1265,7 +1274,8 @@ extern "C" int dct_gemm_bf16_bt(const uint16_t* A, const uint16_t* B, void* C, c
   g.vec_b = ((((uintptr_t)B) & 15) == 0) && (ldb % 8 == 0);
   g.bt_out = bt_out; g.bt_ld = bt_ld;
   const bool split_k = out_f32 && epilogue == dct::EPI_NONE;  // (launch_gemm2 splits only fp32 EPI_NONE outputs)
-  if (!gemm_v2_ok(g, 0, 1) || split_k || (((uintptr_t)bt_out) & 15) || (bt_ld % 8) || (N % 8))
+  if (!gemm_v2_ok(g, 0, 1) || split_k || (((uintptr_t)bt_out) & 15) || (bt_ld % 8) || (N % 8) ||
+      !epilogue_aux_ok(epilogue, aux))
     return (int)hipErrorInvalidValue;
   return (int)launch_gemm2<false, true>(g, reinterpret_cast<hipStream_t>(stream));
 }
@@ -1314,6 +1324,7 @@ extern "C" int dct_gemm_bf16(const uint16_t* A, const uint16_t* B, void* C, cons
                              int lda, int ldb, int ldc, int trans_a, int trans_b, int epilogue, int out_f32,
                              int accumulate, void* aux, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
+  if (!epilogue_aux_ok(epilogue, aux)) return (int)hipErrorInvalidValue;
   dct::GemmArgs g{};
   g.A = A; g.B = B; g.C = C; g.bias = bias; g.aux = aux;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;

@@ -96,6 +96,9 @@ int dct_reducer_check(unsigned long long* s, void* stream);
 int dct_phase_accum(unsigned long long* b, int n, void* stream);
 int dct_gemm_bf16_bt(const uint16_t* A, const uint16_t* B, void* C, const float* bias, int M, int N, int K, int lda,
                      int ldb, int ldc, int epilogue, int out_f32, void* aux, uint16_t* bt_out, int bt_ld, void* stream);
+// C (+)= op(A) op(B) with the epilogue (see gemm_bf16.hip).  The LDS-DMA kernels take K % 64 == 0, 16-byte aligned A,
+// B, bias and residual, lda / ldb % 8 == 0 and M % 8 == 0 (trans_a) / N % 8 == 0 (!trans_b); every other launch runs
+// the generic kernel.  EPI_RELU_MASK / EPI_GELU_GRAD with a null aux: hipErrorInvalidValue, nothing launched.
 int dct_gemm_bf16(const uint16_t* A, const uint16_t* B, void* C, const float* bias, int M, int N, int K, int lda,
                   int ldb, int ldc, int trans_a, int trans_b, int epilogue, int out_f32, int accumulate, void* aux,
                   void* stream);
@@ -103,7 +106,9 @@ int dct_gemm_bf16(const uint16_t* A, const uint16_t* B, void* C, const float* bi
 // GatherFwd.  hipErrorInvalidValue (nothing launched) when the shape does not take the LDS-DMA kernels.
 int dct_gemm_bf16_gather_fwd(const uint16_t* X, int ldx, const uint16_t* W, uint16_t* C, const float* bias, int M,
                              int N, int K, int epilogue, void* aux, const dct::GatherFwd* ga, void* stream);
-// same, plus colsum[m] += sum over k of op(A)[m][k] (fused bias gradient; colsum accumulates)
+// same, plus colsum[m] += sum over k of op(A)[m][k] (fused bias gradient; colsum accumulates).  A shape that
+// does not take the LDS-DMA kernels has the column-sum kernel for trans_a only: with colsum and trans_a == 0 it
+// returns hipErrorNotSupported and launches nothing (C and colsum untouched).
 int dct_gemm_bf16_ex(const uint16_t* A, const uint16_t* B, void* C, const float* bias, int M, int N, int K, int lda,
                      int ldb, int ldc, int trans_a, int trans_b, int epilogue, int out_f32, int accumulate, void* aux,
                      float* colsum, void* stream);
@@ -125,7 +130,9 @@ int dct_skinny_head(const uint16_t* H, const uint16_t* W, const float* bias, con
                     float* dW, float* db, float* loss_sum, int B, int K, int C, float grad_scale, int loss_kind,
                     float loss_scale, int relu_mask, void* stream);
 // dZ = dY * act'(aux) (bf16 out); dbias[n] (+)= sum_m dZ[m][n]. dY is bf16. For RELU aux is
-// the activation OUTPUT (bf16), for GELU the pre-activation (bf16), for NONE unused.
+// the activation OUTPUT (bf16), for GELU the pre-activation (bf16), for NONE unused (null aux with RELU / GELU:
+// hipErrorInvalidValue).  accumulate_bias == 0: dbias = the sum, whatever dbias held (from M > 64 on the launch
+// clears dbias[0, N) with dct_zero_f32 first, which wants dbias 16-byte aligned: hipErrorInvalidValue otherwise).
 int dct_bias_act_bwd(const void* dY, const void* act_aux, uint16_t* dZ, float* dbias, int M, int N, int ldy, int act,
                      int accumulate_bias, void* stream);
 // Row-wise CE (loss_kind 0) or MSE-vs-onehot (1): loss/correct sums (atomic fp32) and

@@ -506,6 +506,14 @@ int dct_bias_act_bwd(const void* dY, const void* act_aux, uint16_t* dZ, float* d
   dim3 grid((ncc + 63) / 64, (unsigned)grid_cap((M + 63) / 64, 1, std::max(64, 512 / std::max(1, (ncc + 63) / 64))));
   const bool vec = (N % 8 == 0) && (ldy % 8 == 0) && ((((uintptr_t)dY) | ((uintptr_t)act_aux) | ((uintptr_t)dZ)) & 15) == 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (act != dct::ACT_NONE && !act_aux) return (int)hipErrorInvalidValue;  // the kernel reads aux for RELU / GELU
+  if (dbias && !accumulate_bias && grid.y > 1) {
+    // several row blocks per column add their sums atomically: dbias = sum needs dbias cleared first (a kernel
+    // node, so the launch stays capture-safe).  One row block (M <= 64) stores instead.
+    const int e = dct_zero_f32(dbias, N, stream);
+    if (e) return e;
+    accumulate_bias = 1;
+  }
   if (vec)
     hipLaunchKernelGGL(dct::bias_act_bwd_kernel<true>, grid, dim3(256), 0, st, (const uint16_t*)dY,
                        (const uint16_t*)act_aux, dZ, dbias, M, N, ldy, act, accumulate_bias);
