@@ -7,6 +7,8 @@
 * ``best_model_path`` / ``best_model_score`` / ``last_model_path`` / ``best_k_models`` and the
   callback ``state_dict`` stored in the checkpoint under Lightning's state key.
 Only global rank 0 touches the filesystem; the trainer barriers all ranks afterwards.
+
+``LearningRateMonitor`` logs the scheduled learning rate (``lr-Adam``), per epoch or per logged step.
 """
 from __future__ import annotations
 
@@ -169,3 +171,27 @@ class ModelCheckpoint:
                 self.kth_value = kv
             self.last_model_path = sd.get("last_model_path", "")
         self.current_score = f(sd.get("current_score"))
+
+
+class LearningRateMonitor:
+    """Lightning's ``LearningRateMonitor``: logs the learning rate of a fit whose ``configure_optimizers()`` returned
+    an lr scheduler, under ``lr-<Optimizer>`` (``lr-Adam``; the scheduler dict's ``name`` when given).
+
+    ``logging_interval="epoch"``: one point per epoch, the rate of its first step, at that step.  ``"step"``: the rate
+    of every ``log_every_n_steps``-th step, at the steps ``train_loss`` is logged at.  None: the scheduler's own
+    interval.  The values are the schedule's host copy of the rates the device reads (trainer/lr_schedule.py): nothing
+    is read back from the device."""
+
+    def __init__(self, logging_interval: Optional[str] = None):
+        if logging_interval not in (None, "step", "epoch"):
+            raise ValueError("logging_interval should be `step` or `epoch` or `None`.")
+        self.logging_interval = logging_interval
+
+    def points(self, schedule, first: int, n: int, every: int):
+        """[(global step, rate)] for the epoch whose n optimizer steps are global steps first .. first + n - 1."""
+        interval = self.logging_interval or schedule.interval
+        if interval == "step":
+            every = max(1, int(every))
+            k0 = (-first) % every or every  # first k in 1..n with (first + k) % every == 0, as train_loss
+            return [(first + k - 1, schedule.rate_for(first + k - 1)) for k in range(k0, n + 1, every)]
+        return [(first, schedule.rate_for(first))]

@@ -75,7 +75,8 @@ def cpu_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
 def build_checkpoint(state_dict: Dict[str, torch.Tensor], epoch: int, global_step: int,
                      optimizer_states: Optional[List[Dict]] = None, callbacks: Optional[Dict[str, Dict]] = None,
                      hyper_parameters: Optional[Dict[str, Any]] = None, hparams_name: Optional[str] = "kwargs",
-                     batches_in_epoch: int = 0, val_batches: int = 0) -> Dict[str, Any]:
+                     batches_in_epoch: int = 0, val_batches: int = 0,
+                     lr_schedulers: Optional[List[Dict]] = None) -> Dict[str, Any]:
     ckpt: Dict[str, Any] = {
         "epoch": int(epoch),
         "global_step": int(global_step),
@@ -84,7 +85,7 @@ def build_checkpoint(state_dict: Dict[str, torch.Tensor], epoch: int, global_ste
         "loops": loops_state(epoch, global_step, batches_in_epoch, val_batches),
         "callbacks": callbacks or {},
         "optimizer_states": optimizer_states or [],
-        "lr_schedulers": [],
+        "lr_schedulers": list(lr_schedulers or []),  # [scheduler.state_dict()] (trainer/lr_schedule.py)
     }
     if hyper_parameters is not None:
         ckpt["hparams_name"] = hparams_name

@@ -7,6 +7,7 @@
 
 #include "dct_common.h"
 #include "kernels.h"
+#include "lr_table.h"
 
 namespace dct {
 
@@ -41,6 +42,9 @@ struct AdamArgs {
   // clip_value > 0: g clamped to [-clip_value, clip_value] after scaling (CLIP == 2)
   const float* clip_coef;
   float clip_value;
+  // optional learning-rate table (lr_table.h; after the clip fields for the same reason): with step_counter, the rate
+  // of the step is lr_tab's entry for *step_counter - 1 steps taken instead of lr
+  const float* lr_tab;
 };
 
 template <bool CLAMP = false>
@@ -58,9 +62,14 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   p -= a.step_size * m / denom;
 }
 
-// step_size / rbc2 from the device step counter t (graph-replayable launches)
+// step_size / rbc2 from the device step counter t (graph-replayable launches); with a rate table, lr (step_size and
+// the decoupled weight-decay term of adam_one) is the table's entry for this step: the counter already includes the
+// step being applied, so t - 1 steps were taken before it.  That load depends on the counter's - one more round
+// trip, paid only when a table is set.
 __device__ __forceinline__ void adam_bias_correction(AdamArgs& a) {
-  const float t = (float)__hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int ti = __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  a.lr = lr_for(a.lr_tab, a.lr, ti - 1);
+  const float t = (float)ti;
   a.step_size = a.lr / (1.f - pow_t(log2f(a.b1), t));
   a.rbc2 = rsqrtf(1.f - pow_t(log2f(a.b2), t));
 }
@@ -226,7 +235,8 @@ __global__ __launch_bounds__(256) void adam_range_kernel(AdamArgs a, int64_t lo,
 // AdamArgs of an AdamRange (kernels.h), validated; *max_sp = the deepest slice count (S of the kernel)
 inline int adam_args_from_range(const AdamRange& r, AdamArgs& a, int* max_sp) {
   if (r.n <= 0 || r.lo < 0 || r.lo % 4 || r.hi > r.n || r.lo >= r.hi || (r.hi % 4 && r.hi != r.n) || !r.step_counter ||
-      r.nparts < 0 || r.nparts > 3 || (((uintptr_t)r.p | (uintptr_t)r.g | (uintptr_t)r.m | (uintptr_t)r.v) & 15))
+      r.nparts < 0 || r.nparts > 3 ||
+      (((uintptr_t)r.p | (uintptr_t)r.g | (uintptr_t)r.m | (uintptr_t)r.v | (uintptr_t)r.lr_tab) & 15))
     return (int)hipErrorInvalidValue;
   a = AdamArgs{};
   a.p = r.p; a.g = r.g; a.m = r.m; a.v = r.v; a.p_bf16 = r.p_bf16; a.n = r.n;
@@ -234,6 +244,7 @@ inline int adam_args_from_range(const AdamRange& r, AdamArgs& a, int* max_sp) {
   a.grad_scale = r.grad_scale;
   a.decoupled = r.decoupled;
   a.step_counter = r.step_counter;
+  a.lr_tab = r.lr_tab;
   a.nparts = r.nparts;
   *max_sp = 1;
   for (int q = 0; q < r.nparts; ++q) {

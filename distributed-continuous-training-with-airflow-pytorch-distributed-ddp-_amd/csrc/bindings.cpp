@@ -296,13 +296,16 @@ PYBIND11_MODULE(_dct_native, m) {
              float eps, float wd, float dropout, uint32_t seed, uint32_t step_base, uintptr_t loss_out, int mode,
              int loss_kind, uintptr_t step_counter, uintptr_t cursor, uintptr_t prof, uintptr_t pending,
              uintptr_t stage, uintptr_t stream, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
-             uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t tile_ws, int64_t tile_ws_floats) {
+             uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t tile_ws, int64_t tile_ws_floats,
+             uintptr_t lr_tab) {
+            if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             dct::MlpArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
                                                    b1, b2, eps, wd, dropout, seed, step_base, loss_out, mode,
                                                    loss_kind, step_counter, cursor, prof, pending, stage, xg_recv,
                                                    xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll);
             a.tile_ws = P<float>(tile_ws);
             a.tile_ws_floats = tile_ws_floats;
+            a.lr_tab = P<const float>(lr_tab);
             launch_train(plan, a, stream);
           },
           py::arg("p"), py::arg("m"), py::arg("v"), py::arg("grad_out"), py::arg("X"), py::arg("ldx"), py::arg("Y"),
@@ -312,14 +315,16 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("cursor"), py::arg("prof") = 0, py::arg("pending") = 0, py::arg("stage") = 0,
           py::arg("stream") = 0, py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL, py::arg("xg_poll") = 0,
-          py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0)
+          py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0, py::arg("lr_tab") = (uintptr_t)0)
       .def(
           "prepare_train",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t X, int ldx, uintptr_t Y,
              uintptr_t idx, int n_items, int B, float lr, float b1, float b2, float eps, float wd, float dropout,
              uint32_t seed, uintptr_t loss_out, int64_t loss_len, int loss_kind, uintptr_t step_counter,
              uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank, uintptr_t xg_status,
-             int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks, uintptr_t tile_ws, int64_t tile_ws_floats) {
+             int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks, uintptr_t tile_ws, int64_t tile_ws_floats,
+             uintptr_t lr_tab) {
+            if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             auto l = std::make_unique<MlpLaunch>(MlpLaunch{plan});
             l->base = make_train_args(plan, p, mo, vo, 0, X, ldx, Y, idx, n_items, B, 1, 0, lr, b1, b2, eps, wd,
                                       dropout, seed, 0, loss_out, 0, loss_kind, step_counter, 0, 0, 0, 0, xg_recv,
@@ -327,6 +332,7 @@ PYBIND11_MODULE(_dct_native, m) {
             l->base.xg_ticks = P<unsigned long long>(xg_ticks);
             l->base.tile_ws = P<float>(tile_ws);
             l->base.tile_ws_floats = tile_ws_floats;
+            l->base.lr_tab = P<const float>(lr_tab);
             l->n_items = n_items;
             l->loss_len = loss_out ? loss_len : 0;
             return l;
@@ -336,7 +342,8 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("dropout"), py::arg("seed"), py::arg("loss_out"), py::arg("loss_len"), py::arg("loss_kind"),
           py::arg("step_counter"), py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL,
-          py::arg("xg_poll") = 0, py::arg("xg_ticks") = 0, py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0)
+          py::arg("xg_poll") = 0, py::arg("xg_ticks") = 0, py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0,
+          py::arg("lr_tab") = (uintptr_t)0)
       .def(
           "eval",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items,
@@ -362,42 +369,49 @@ PYBIND11_MODULE(_dct_native, m) {
       "adam_flat",
       [](uintptr_t p, uintptr_t g, uintptr_t mo, uintptr_t vo, uintptr_t p_bf16, int64_t n, float lr, float b1,
          float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled, uintptr_t step_counter,
-         uintptr_t stream) {
-        check(dct_adam_flat(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo), P<uint16_t>(p_bf16), n, lr,
-                            b1, b2, eps, wd, t, grad_scale, decoupled, P<const int>(step_counter),
-                            reinterpret_cast<void*>(stream)),
+         uintptr_t stream, uintptr_t lr_tab) {
+        check(dct_adam_flat_step_lr(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo), P<uint16_t>(p_bf16), n,
+                                    lr, b1, b2, eps, wd, t, grad_scale, decoupled, P<const int>(step_counter), nullptr,
+                                    nullptr, nullptr, 0, nullptr, 0.f, P<const float>(lr_tab),
+                                    reinterpret_cast<void*>(stream)),
               "adam_flat");
       },
       py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
       py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("t"), py::arg("grad_scale"),
-      py::arg("decoupled"), py::arg("step_counter"), py::arg("stream"));
+      py::arg("decoupled"), py::arg("step_counter"), py::arg("stream"), py::arg("lr_tab") = (uintptr_t)0);
   m.def("xg_adam_buffer_bytes", &dct_xg_adam_buffer_bytes, py::arg("n"), py::arg("world"));
   m.def(
       "xg_allreduce_adam",
       [](uintptr_t g, uintptr_t p, uintptr_t mo, uintptr_t vo, int64_t n, int64_t np, uintptr_t step_counter,
          float lr, float b1, float b2, float eps, float wd, const dct::PeerExchange& xg, double timeout_s,
-         uintptr_t stream) {
+         uintptr_t stream, uintptr_t lr_tab) {
         if (xg.bytes() < dct_xg_adam_buffer_bytes(n, xg.world()))
           throw std::invalid_argument("xg_allreduce_adam: exchange buffer too small for n");
-        check(dct_xg_allreduce_adam(P<float>(g), P<float>(p), P<float>(mo), P<float>(vo), n, np,
-                                    P<const int>(step_counter), lr, b1, b2, eps, wd, P<void>(xg.recv()),
-                                    P<void* const>(xg.peers()), P<unsigned>(xg.status()), xg.world(), xg.rank(),
-                                    (long long)(timeout_s * 1e8), reinterpret_cast<void*>(stream)),
+        check(dct_xg_allreduce_adam_lr(P<float>(g), P<float>(p), P<float>(mo), P<float>(vo), n, np,
+                                       P<const int>(step_counter), lr, b1, b2, eps, wd, P<void>(xg.recv()),
+                                       P<void* const>(xg.peers()), P<unsigned>(xg.status()), xg.world(), xg.rank(),
+                                       (long long)(timeout_s * 1e8), P<const float>(lr_tab),
+                                       reinterpret_cast<void*>(stream)),
               "xg_allreduce_adam");
       },
       py::arg("g"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("n"), py::arg("P"), py::arg("step_counter"),
       py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("xg"),
-      py::arg("timeout_s"), py::arg("stream"));
+      py::arg("timeout_s"), py::arg("stream"), py::arg("lr_tab") = (uintptr_t)0);
   m.def("adam_flat_step",
         [](uintptr_t p, uintptr_t g, uintptr_t mo, uintptr_t vo, uintptr_t p_bf16, int64_t n, float lr, float b1,
            float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled, uintptr_t step_counter,
-           uintptr_t cursor, uintptr_t loss_slot, uintptr_t loss_out, int loss_cap, uintptr_t stream) {
-          check(dct_adam_flat_step(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo), P<uint16_t>(p_bf16), n,
-                                   lr, b1, b2, eps, wd, t, grad_scale, decoupled, P<const int>(step_counter),
-                                   P<int>(cursor), P<const float>(loss_slot), P<float>(loss_out), loss_cap,
-                                   reinterpret_cast<void*>(stream)),
+           uintptr_t cursor, uintptr_t loss_slot, uintptr_t loss_out, int loss_cap, uintptr_t stream,
+           uintptr_t lr_tab) {
+          check(dct_adam_flat_step_lr(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo), P<uint16_t>(p_bf16),
+                                      n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, P<const int>(step_counter),
+                                      P<int>(cursor), P<const float>(loss_slot), P<float>(loss_out), loss_cap, nullptr,
+                                      0.f, P<const float>(lr_tab), reinterpret_cast<void*>(stream)),
                 "adam_flat_step");
-        });
+        },
+        py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
+        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("t"), py::arg("grad_scale"),
+        py::arg("decoupled"), py::arg("step_counter"), py::arg("cursor"), py::arg("loss_slot"), py::arg("loss_out"),
+        py::arg("loss_cap"), py::arg("stream"), py::arg("lr_tab") = (uintptr_t)0);
   // gradient clipping: {norm, coef} of g on the device, and the flat Adam step that reads the coefficient
   m.def("grad_clip_workspace_floats", &dct_grad_clip_workspace_floats);
   m.def("grad_clip_coef",
@@ -413,18 +427,19 @@ PYBIND11_MODULE(_dct_native, m) {
         [](uintptr_t p, uintptr_t g, uintptr_t mo, uintptr_t vo, uintptr_t p_bf16, int64_t n, float lr, float b1,
            float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled, uintptr_t step_counter,
            uintptr_t cursor, uintptr_t loss_slot, uintptr_t loss_out, int loss_cap, uintptr_t clip_coef,
-           float clip_value, uintptr_t stream) {
-          check(dct_adam_flat_step_clipped(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo),
-                                           P<uint16_t>(p_bf16), n, lr, b1, b2, eps, wd, t, grad_scale, decoupled,
-                                           P<const int>(step_counter), P<int>(cursor), P<const float>(loss_slot),
-                                           P<float>(loss_out), loss_cap, P<const float>(clip_coef), clip_value,
-                                           reinterpret_cast<void*>(stream)),
+           float clip_value, uintptr_t stream, uintptr_t lr_tab) {
+          check(dct_adam_flat_step_lr(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo), P<uint16_t>(p_bf16),
+                                      n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, P<const int>(step_counter),
+                                      P<int>(cursor), P<const float>(loss_slot), P<float>(loss_out), loss_cap,
+                                      P<const float>(clip_coef), clip_value, P<const float>(lr_tab),
+                                      reinterpret_cast<void*>(stream)),
                 "adam_flat_step_clipped");
         },
         py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
         py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("t"), py::arg("grad_scale"),
         py::arg("decoupled"), py::arg("step_counter"), py::arg("cursor"), py::arg("loss_slot"), py::arg("loss_out"),
-        py::arg("loss_cap"), py::arg("clip_coef"), py::arg("clip_value"), py::arg("stream"));
+        py::arg("loss_cap"), py::arg("clip_coef"), py::arg("clip_value"), py::arg("stream"),
+        py::arg("lr_tab") = (uintptr_t)0);
   // Adam over [0, n) of p / g / m / v (step t read from step_counter): riding in a split-K dW launch
   // of dZ^T X (mode 0: one element per thread - the executor's body; 1: the float4 body) or as its own
   // launch (mode 2, dct_adam_range) - tests/test_packed_fp32_gpu.py compares them bit for bit
@@ -452,7 +467,7 @@ PYBIND11_MODULE(_dct_native, m) {
                        float b1, float b2, float eps, float wd, float grad_scale, int decoupled,
                        uintptr_t step_counter, const std::vector<int64_t>& part_off,
                        const std::vector<int64_t>& part_n, const std::vector<uintptr_t>& part,
-                       const std::vector<int>& part_splits, int64_t lo, int64_t hi) {
+                       const std::vector<int>& part_splits, int64_t lo, int64_t hi, uintptr_t lr_tab) {
              const size_t np = part_off.size();
              if (np > 3 || part_n.size() != np || part.size() != np || part_splits.size() != np)
                throw std::invalid_argument("AdamRange: at most 3 part ranges, lists of one length");
@@ -468,12 +483,13 @@ PYBIND11_MODULE(_dct_native, m) {
                r.part_splits[q] = part_splits[q];
              }
              r.lo = lo; r.hi = hi;
+             r.lr_tab = P<const float>(lr_tab);
              return r;
            }),
            py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
            py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("grad_scale"), py::arg("decoupled"),
            py::arg("step_counter"), py::arg("part_off"), py::arg("part_n"), py::arg("part"), py::arg("part_splits"),
-           py::arg("lo"), py::arg("hi"));
+           py::arg("lo"), py::arg("hi"), py::arg("lr_tab") = (uintptr_t)0);
   m.def("adam_range",
         [](const dct::AdamRange& r, uintptr_t cursor, uintptr_t loss_slot, uintptr_t loss_out, int loss_cap,
            uintptr_t stream) {
@@ -488,23 +504,25 @@ PYBIND11_MODULE(_dct_native, m) {
            float b2, float eps, float wd, float grad_scale, int decoupled, uintptr_t step_counter, uintptr_t cursor,
            uintptr_t loss_slot, uintptr_t loss_out, int loss_cap, const std::vector<int64_t>& part_off,
            const std::vector<int64_t>& part_n, const std::vector<uintptr_t>& part,
-           const std::vector<int>& part_splits, uintptr_t stream) {
+           const std::vector<int>& part_splits, uintptr_t stream, uintptr_t lr_tab) {
           const size_t np = part_off.size();
           if (part_n.size() != np || part.size() != np || part_splits.size() != np)
             throw std::invalid_argument("adam_flat_step_parts: list lengths differ");
           std::vector<const float*> pp(np);
           for (size_t q = 0; q < np; ++q) pp[q] = P<const float>(part[q]);
-          check(dct_adam_flat_step_parts(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo),
-                                         P<uint16_t>(p_bf16), n, lr, b1, b2, eps, wd, grad_scale, decoupled,
-                                         P<const int>(step_counter), P<int>(cursor), P<const float>(loss_slot),
-                                         P<float>(loss_out), loss_cap, (int)np, part_off.data(), part_n.data(),
-                                         pp.data(), part_splits.data(), reinterpret_cast<void*>(stream)),
+          check(dct_adam_flat_step_parts_lr(P<float>(p), P<const float>(g), P<float>(mo), P<float>(vo),
+                                            P<uint16_t>(p_bf16), n, lr, b1, b2, eps, wd, grad_scale, decoupled,
+                                            P<const int>(step_counter), P<int>(cursor), P<const float>(loss_slot),
+                                            P<float>(loss_out), loss_cap, (int)np, part_off.data(), part_n.data(),
+                                            pp.data(), part_splits.data(), P<const float>(lr_tab),
+                                            reinterpret_cast<void*>(stream)),
                 "adam_flat_step_parts");
         },
         py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
         py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("grad_scale"), py::arg("decoupled"),
         py::arg("step_counter"), py::arg("cursor"), py::arg("loss_slot"), py::arg("loss_out"), py::arg("loss_cap"),
-        py::arg("part_off"), py::arg("part_n"), py::arg("part"), py::arg("part_splits"), py::arg("stream"));
+        py::arg("part_off"), py::arg("part_n"), py::arg("part"), py::arg("part_splits"), py::arg("stream"),
+        py::arg("lr_tab") = (uintptr_t)0);
   // r = None: the GEMM alone
   m.def("gemm_bf16_dw_partials_adam",
         [](uintptr_t dz, uintptr_t x, uintptr_t part, uintptr_t colsum, int M, int N, int K, int splits,
@@ -932,6 +950,7 @@ PYBIND11_MODULE(_dct_native, m) {
            py::arg("clip_algorithm") = 0, py::arg("clip_ws") = (uintptr_t)0, py::keep_alive<1, 17>())
       .def("set_adam", &dct::MlpStepExecutor::set_adam, py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
            py::arg("wd"), py::arg("decoupled") = 0)
+      .def("set_lr_table", &dct::MlpStepExecutor::set_lr_table, py::arg("lr_tab"))
       .def("step", &dct::MlpStepExecutor::step, py::arg("X"), py::arg("row_bytes"), py::arg("Y"), py::arg("idx"),
            py::arg("n_items"), py::arg("cursor"), py::arg("step_counter"), py::arg("loss_out"), py::arg("loss_cap"),
            py::arg("rows"), py::arg("stream"))

@@ -68,6 +68,7 @@ struct AdamRange {
   const float* part[3];
   int part_splits[3];
   int64_t lo, hi;
+  const float* lr_tab;  // optional rate table (lr_table.h), last: the fields above keep their offsets
 };
 
 }  // namespace dct
@@ -235,6 +236,19 @@ int dct_adam_flat_step_clipped(float* p, const float* g, float* m, float* v, uin
                                float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
                                const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
                                int loss_cap, const float* clip_coef, float clip_value, void* stream);
+// dct_adam_flat_step_clipped / dct_adam_flat_step_parts with a learning-rate table (lr_table.h): the step's rate is
+// lr_tab's entry for *step_counter - 1 steps taken (step_counter required with a table: hipErrorInvalidValue without,
+// and for a table that is not 16-byte aligned).  Null lr_tab: the launch without one, bit for bit.  The launchers
+// cannot read the header: a table with len >= 1 (word 4 readable) is the caller's duty, here and in AdamRange.
+int dct_adam_flat_step_lr(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr, float b1,
+                          float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
+                          const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
+                          const float* clip_coef, float clip_value, const float* lr_tab, void* stream);
+int dct_adam_flat_step_parts_lr(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                                float b1, float b2, float eps, float wd, float grad_scale, int decoupled,
+                                const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
+                                int loss_cap, int nparts, const int64_t* part_off, const int64_t* part_n,
+                                const float* const* part, const int* part_splits, const float* lr_tab, void* stream);
 int dct_f32_to_bf16(const float* in, uint16_t* out, int64_t n, void* stream);
 // device-side barrier of the xGMI peer exchange (step_kernels.hip; barrier slots at byte offset off)
 int dct_xg_barrier(void* recv, void* const* peers, int64_t off, unsigned* status, int world, int rank, unsigned tag,
@@ -244,4 +258,10 @@ int64_t dct_xg_adam_buffer_bytes(int64_t n, int world);
 int dct_xg_allreduce_adam(float* g, float* p, float* m, float* v, int64_t n, int64_t P, const int* step_counter,
                           float lr, float b1, float b2, float eps, float wd, void* recv, void* const* peers,
                           unsigned* status, int world, int rank, long long timeout_ticks, void* stream);
+// the same with a learning-rate table (lr_table.h; null: the launch above): the rate of the step after
+// *step_counter - 1 steps
+int dct_xg_allreduce_adam_lr(float* g, float* p, float* m, float* v, int64_t n, int64_t P, const int* step_counter,
+                             float lr, float b1, float b2, float eps, float wd, void* recv, void* const* peers,
+                             unsigned* status, int world, int rank, long long timeout_ticks, const float* lr_tab,
+                             void* stream);
 }

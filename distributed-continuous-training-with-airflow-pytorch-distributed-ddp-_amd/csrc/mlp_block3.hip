@@ -205,6 +205,8 @@ __global__ __launch_bounds__(blk3::NT, 1) void mlp_block3_kernel(MlpShape sh, Ml
     const int sb = s + cur0;
     const int bs = min(Bsz, a.n_items - sb * Bsz);
     const uint32_t gstep = step_base + (uint32_t)s;
+    // rate table: the step's rate as one wave-uniform load, issued here at the top of the step (null: the scalar)
+    const float lr_s = ADAM ? lr_for(a.lr_tab, a.lr, t0 + s) : a.lr;
     const int xbn = xb == 2 ? 0 : xb + 1;
     const int pbuf = s & 1, nbuf = pbuf ^ 1;
     const float* xT = lds + XT + xb * DMAX * 4;
@@ -366,7 +368,7 @@ __global__ __launch_bounds__(blk3::NT, 1) void mlp_block3_kernel(MlpShape sh, Ml
     B3STAMP(5)
 
     const int t = t0 + s + 1;
-    const float step_size = a.lr / (1.f - pow_t(l2b1, (float)t));
+    const float step_size = lr_s / (1.f - pow_t(l2b1, (float)t));
     const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(l2b2, (float)t));
     const float rss = __builtin_amdgcn_rcpf(step_size);
     // adam_scaled's folded denominator (moments held as m / (1 - b1), v / (1 - b2))

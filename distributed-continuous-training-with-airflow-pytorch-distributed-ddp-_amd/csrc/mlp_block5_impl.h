@@ -635,6 +635,12 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
     const uint32_t xtag = gstep + 1u;  // XW > 1: this step's exchange tag and parity slab
     const int xpar = (int)(gstep & 1u);
     const int t = t0 + s + 1;
+    // rate table, per-step form (the kernels without the 64-step lane table): one wave-uniform load, issued here at
+    // the top of the step, consumed where the last micro-batch forms Adam's scalars
+    float lr_s = a.lr;
+    if constexpr (!S && ADAM) {
+      if (a.lr_tab) lr_s = lr_for(a.lr_tab, a.lr, t - 1);
+    }
     // per micro-batch state that outlives it: dZ2 (the one dW1 pass runs over every micro-batch), and
     // the gradient sums of the small parameters (the last micro-batch applies Adam to them)
     float dz2m[MB][2][4];
@@ -807,7 +813,8 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
             if (ti == 0) {  // wave-uniform: the next 64 steps' scalars, one per lane
               asm volatile("");  // a real branch: without it the block is if-converted and runs every step
               const float tl = (float)(t + l);
-              const float step_size = a.lr * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, tl));
+              // (a rate table: lane l's entry for the step after t - 1 + l steps, one 256-byte load per 64 steps)
+              const float step_size = lr_for(a.lr_tab, a.lr, t - 1 + l) * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, tl));
               const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(l2b2, tl));
               const float rss = __builtin_amdgcn_rcpf(step_size);
               tabA = sqc2 * rbc2 * rss * rc1;
@@ -943,7 +950,7 @@ __global__ __launch_bounds__(blk5::NT, 1) void mlp_block5_kernel(MlpShape sh, Ml
       B5STAMP(5)
 
       if (last && !S) {  // (step schedule: from the 64-step table, in the A -> B window)
-        const float step_size = a.lr * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, (float)t));
+        const float step_size = lr_s * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, (float)t));
         const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(l2b2, (float)t));
         const float rss = __builtin_amdgcn_rcpf(step_size);
         aA = sqc2 * rbc2 * rss * rc1;

@@ -196,6 +196,7 @@ void MlpStepExecutor::step(uintptr_t X, int row_bytes, uintptr_t Y, uintptr_t id
     r.p = p_; r.g = g_; r.m = m_; r.v = v_; r.p_bf16 = pb_; r.n = P_;
     r.lr = lr_; r.b1 = b1_; r.b2 = b2_; r.eps = eps_; r.wd = wd_; r.grad_scale = 1.0f; r.decoupled = decoupled_;
     r.step_counter = sc;
+    r.lr_tab = lr_tab_;
     for (int q = 0; q < nparts_; ++q) {
       if (!part_used[q]) continue;
       const int lq = part_layer_[q];
@@ -310,9 +311,9 @@ void MlpStepExecutor::step(uintptr_t X, int row_bytes, uintptr_t Y, uintptr_t id
       ck(dct_grad_clip_coef(g_, P_, 1.0f, clip_val_, clip_ws_ + 4, reinterpret_cast<unsigned*>(clip_ws_ + 2), clip_ws_,
                             st),
          "grad clip");
-    ck(dct_adam_flat_step_clipped(p_, g_, m_, v_, pb_, P_, lr_, b1_, b2_, eps_, wd_, 1, 1.0f, decoupled_, sc, cur,
-                                  g_ + P_, reinterpret_cast<float*>(loss_out), loss_cap,
-                                  by_norm ? clip_ws_ + 1 : nullptr, by_norm ? 0.f : clip_val_, st),
+    ck(dct_adam_flat_step_lr(p_, g_, m_, v_, pb_, P_, lr_, b1_, b2_, eps_, wd_, 1, 1.0f, decoupled_, sc, cur, g_ + P_,
+                             reinterpret_cast<float*>(loss_out), loss_cap, by_norm ? clip_ws_ + 1 : nullptr,
+                             by_norm ? 0.f : clip_val_, lr_tab_, st),
        "clipped adam");
     return;
   }
@@ -332,12 +333,13 @@ void MlpStepExecutor::step(uintptr_t X, int row_bytes, uintptr_t Y, uintptr_t id
     ++np;
   }
   if (np)
-    ck(dct_adam_flat_step_parts(p_, g_, m_, v_, pb_, P_, lr_, b1_, b2_, eps_, wd_, 1.0f, decoupled_, sc, cur, g_ + P_,
-                                reinterpret_cast<float*>(loss_out), loss_cap, np, poff, pn, pp, psp, st),
+    ck(dct_adam_flat_step_parts_lr(p_, g_, m_, v_, pb_, P_, lr_, b1_, b2_, eps_, wd_, 1.0f, decoupled_, sc, cur,
+                                   g_ + P_, reinterpret_cast<float*>(loss_out), loss_cap, np, poff, pn, pp, psp,
+                                   lr_tab_, st),
        "adam");
   else
-    ck(dct_adam_flat_step(p_, g_, m_, v_, pb_, P_, lr_, b1_, b2_, eps_, wd_, 1, 1.0f, decoupled_, sc, cur, g_ + P_,
-                          reinterpret_cast<float*>(loss_out), loss_cap, st),
+    ck(dct_adam_flat_step_lr(p_, g_, m_, v_, pb_, P_, lr_, b1_, b2_, eps_, wd_, 1, 1.0f, decoupled_, sc, cur, g_ + P_,
+                             reinterpret_cast<float*>(loss_out), loss_cap, nullptr, 0.f, lr_tab_, st),
        "adam");
 }
 

@@ -26,6 +26,9 @@ class MlpStepExecutor {
                   const std::vector<uintptr_t>& pre, uintptr_t dz0, uintptr_t dz1, uintptr_t ybuf, uintptr_t stats,
                   BucketReducer* reducer, float clip_val = 0.f, int clip_algorithm = 0, uintptr_t clip_ws = 0);
   void set_adam(float lr, float b1, float b2, float eps, float wd, int decoupled);
+  // learning-rate table (lr_table.h; 0 = none): every Adam of the step - the riding ranges, the adam_range launch and
+  // the flat launches - reads its rate there at the device step count.  A fixed address: set before the step is captured.
+  void set_lr_table(uintptr_t lr_tab) { lr_tab_ = reinterpret_cast<const float*>(lr_tab); }
   void set_adam_ride(bool on) { adam_ride_ = on; }
   bool adam_ride() const { return adam_ride_; }
   // full-batch steps gather the batch inside the first forward GEMM (dct_gemm_bf16_gather_fwd) instead
@@ -76,6 +79,7 @@ class MlpStepExecutor {
   BucketReducer* reducer_ = nullptr;
   float lr_ = 1e-3f, b1_ = 0.9f, b2_ = 0.999f, eps_ = 1e-8f, wd_ = 0.f;
   int decoupled_ = 0;
+  const float* lr_tab_ = nullptr;  // set_lr_table
   float clip_val_ = 0.f;  // > 0: gradient clipping (constructor)
   int clip_algorithm_ = 0;
   float* clip_ws_ = nullptr;

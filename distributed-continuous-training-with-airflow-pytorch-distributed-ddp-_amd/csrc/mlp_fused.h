@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "knobs.h"
+#include "lr_table.h"
 
 namespace dct {
 
@@ -122,6 +123,11 @@ struct MlpArgs {
   // the fold kernel's arrival counter in its last four floats
   float* tile_ws;
   long long tile_ws_floats;
+  // optional learning-rate table (lr_table.h; last, so every other field keeps its kernel-argument offset): train
+  // launches take the rate of the step that runs after `taken` = t0 + s (or *step_counter + s) steps from it instead
+  // of lr.  Grad-mode launches apply no Adam and ignore it, except the single-wave kernel's update-then-grad, whose
+  // pending update is the step after *step_counter - 1.
+  const float* lr_tab;
 };
 
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)

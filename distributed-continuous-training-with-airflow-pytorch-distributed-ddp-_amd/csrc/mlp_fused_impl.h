@@ -512,6 +512,8 @@ __global__ __launch_bounds__(NT) void mlp_train_kernel(MlpShape sh, MlpArgs a) {
     const int sb = s + cur0;
     const int bs = min(B, a.n_items - sb * B);
     const uint32_t gstep = step_base + (uint32_t)s;
+    // rate table: the step's rate as one wave-uniform load, issued here at the top of the step (null: the scalar)
+    const float lr_s = adam ? lr_for(a.lr_tab, a.lr, t0 + s) : a.lr;
     float* A0 = lds + sh.a0_lds[buf];
     const int* lab = reinterpret_cast<const int*>(lds + sh.lab_lds[buf]);
     // issue next batch's values (idx known) and the idx of the batch after it
@@ -585,7 +587,7 @@ __global__ __launch_bounds__(NT) void mlp_train_kernel(MlpShape sh, MlpArgs a) {
     const int t = t0 + s + 1;
     const float bc1 = 1.f - pow_t(log2f(a.b1), (float)t);
     const float bc2 = 1.f - pow_t(log2f(a.b2), (float)t);
-    const float step_size = a.lr / bc1;
+    const float step_size = lr_s / bc1;
     const float rbc2 = __builtin_amdgcn_rsqf(bc2);
 #pragma unroll
     for (int j = 0; j < MAXQ; ++j) {

@@ -393,7 +393,7 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
         const int t = tcur + 1;
         const float bc1 = 1.f - pow_t(log2f(a.b1), (float)t);
         const float bc2 = 1.f - pow_t(log2f(a.b2), (float)t);
-        const float step_size = a.lr / bc1;
+        const float step_size = lr_for(a.lr_tab, a.lr, tcur) / bc1;  // (next to the counter read above)
         const float rbc2 = __builtin_amdgcn_rsqf(bc2);
         float pv = a.p[e], mv = a.m[e], vv = a.v[e];
         adam_elem(pv, g, mv, vv, a.b1, a.b2, a.wd, step_size, rbc2, a.eps);

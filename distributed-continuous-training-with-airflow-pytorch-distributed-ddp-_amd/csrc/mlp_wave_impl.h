@@ -435,7 +435,7 @@ __global__ __launch_bounds__(64) void mlp_wave_kernel(WaveShape sh, MlpArgs a) {
   if (fuse_upd && __hip_atomic_load(a.pending, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
     // previous step's all-reduced gradients are in grad_out: apply its Adam update first
     const float tt = (float)t0;
-    const float step_size = a.lr * __builtin_amdgcn_rcpf(1.f - pow_t(log2f(a.b1), tt));
+    const float step_size = lr_for(a.lr_tab, a.lr, t0 - 1) * __builtin_amdgcn_rcpf(1.f - pow_t(log2f(a.b1), tt));
     const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(log2f(a.b2), tt));
     if (own1) {
 #pragma unroll
@@ -555,6 +555,8 @@ __global__ __launch_bounds__(64) void mlp_wave_kernel(WaveShape sh, MlpArgs a) {
     const int sb = s + cur0;
     const int bs = min(B, a.n_items - sb * B);
     const uint32_t gstep = step_base + (uint32_t)s;
+    // rate table: the step's rate as one wave-uniform load, issued here at the top of the step (null: the scalar)
+    const float lr_s = adam ? lr_for(a.lr_tab, a.lr, t0 + s) : a.lr;
     WSTAMP(-1)
     // issue: values of batch sb+1 (idx already in registers) and idx of batch sb+2
     load_vals(sb + 1, ridx_a, nxt);
@@ -785,7 +787,7 @@ __global__ __launch_bounds__(64) void mlp_wave_kernel(WaveShape sh, MlpArgs a) {
     WSTAMP(4)
     if (adam) {
       const int t = t0 + s + 1;
-      const float step_size = a.lr * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, (float)t));
+      const float step_size = lr_s * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, (float)t));
       const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(l2b2, (float)t));
       if (own1) {
 #pragma unroll
@@ -1047,6 +1049,8 @@ __device__ __forceinline__ void mlp_rows_wave(const WaveShape& sh, const MlpArgs
   // one optimizer step; returns false when the launch must stop (exchange timeout)
   auto step = [&](const int s, uint32_t& vslot, int& islot) -> bool {
     RSTAMP(-1)
+    // rate table: the step's rate as one wave-uniform load, issued here at the top of the step (null: the scalar)
+    const float lr_s = lr_for(a.lr_tab, a.lr, t0 + s);
     const int bs = min(B, a.n_items - s * B);
     const bool live = w < bs;
     const uint32_t gstep = step_base + (uint32_t)s;
@@ -1174,7 +1178,7 @@ __device__ __forceinline__ void mlp_rows_wave(const WaveShape& sh, const MlpArgs
     }
     if (j == 0) lslot[par][w] = lb;
     const int t_adam = t0 + s + 1;
-    const float step_size = a.lr * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, (float)t_adam));
+    const float step_size = lr_s * __builtin_amdgcn_rcpf(1.f - pow_t(l2b1, (float)t_adam));
     const float rbc2 = __builtin_amdgcn_rsqf(1.f - pow_t(l2b2, (float)t_adam));
     RSTAMP(4)
     __syncthreads();  // barrier 1: every row's gradients are in LDS

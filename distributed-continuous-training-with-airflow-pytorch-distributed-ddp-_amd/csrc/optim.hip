@@ -135,14 +135,8 @@ int dct_adam_flat_step(float* p, const float* g, float* m, float* v, uint16_t* p
                        float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
                        const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
                        void* stream) {
-  if (n <= 0) return 0;
-  if (cursor && !loss_slot) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return (int)hipErrorInvalidValue;
-  dct::AdamArgs a = flat_step_args(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, step_counter,
-                                   cursor, loss_slot, loss_out, loss_cap);
-  hipLaunchKernelGGL(dct::adam_flat_kernel<false>, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), a);
-  return (int)hipGetLastError();
+  return dct_adam_flat_step_lr(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, step_counter,
+                               cursor, loss_slot, loss_out, loss_cap, nullptr, 0.f, nullptr, stream);
 }
 
 int dct_grad_clip_workspace_floats(void) { return dct::CLIP_MAX_GRID; }
@@ -165,10 +159,20 @@ int dct_adam_flat_step_clipped(float* p, const float* g, float* m, float* v, uin
                                float b1, float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
                                const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
                                int loss_cap, const float* clip_coef, float clip_value, void* stream) {
-  if (!(clip_value >= 0.f)) return (int)hipErrorInvalidValue;
-  if (!clip_coef && clip_value == 0.f)  // no clipping: the unclipped kernel, bit for bit
-    return dct_adam_flat_step(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, step_counter,
-                              cursor, loss_slot, loss_out, loss_cap, stream);
+  return dct_adam_flat_step_lr(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, t, grad_scale, decoupled, step_counter,
+                               cursor, loss_slot, loss_out, loss_cap, clip_coef, clip_value, nullptr, stream);
+}
+
+// a rate table is read at the device step count, and its header as one aligned 8-byte word
+static bool lr_tab_ok(const float* lr_tab, const int* step_counter) {
+  return !lr_tab || (step_counter && !((uintptr_t)lr_tab & 15));
+}
+
+int dct_adam_flat_step_lr(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr, float b1,
+                          float b2, float eps, float wd, int64_t t, float grad_scale, int decoupled,
+                          const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
+                          const float* clip_coef, float clip_value, const float* lr_tab, void* stream) {
+  if (!(clip_value >= 0.f) || !lr_tab_ok(lr_tab, step_counter)) return (int)hipErrorInvalidValue;
   if (n <= 0) return 0;
   if (cursor && !loss_slot) return (int)hipErrorInvalidValue;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return (int)hipErrorInvalidValue;
@@ -176,9 +180,12 @@ int dct_adam_flat_step_clipped(float* p, const float* g, float* m, float* v, uin
                                    cursor, loss_slot, loss_out, loss_cap);
   a.clip_coef = clip_coef;
   a.clip_value = clip_value;
+  a.lr_tab = lr_tab;
   const dim3 grid(grid_for((n + 3) / 4, 256));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (clip_value > 0.f) hipLaunchKernelGGL(dct::adam_flat_clip_kernel<2>, grid, dim3(256), 0, st, a);
+  if (!clip_coef && clip_value == 0.f)  // no clipping: the unclipped kernel
+    hipLaunchKernelGGL(dct::adam_flat_kernel<false>, grid, dim3(256), 0, st, a);
+  else if (clip_value > 0.f) hipLaunchKernelGGL(dct::adam_flat_clip_kernel<2>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(dct::adam_flat_clip_kernel<1>, grid, dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
@@ -188,8 +195,19 @@ int dct_adam_flat_step_parts(float* p, const float* g, float* m, float* v, uint1
                              const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
                              int loss_cap, int nparts, const int64_t* part_off, const int64_t* part_n,
                              const float* const* part, const int* part_splits, void* stream) {
+  return dct_adam_flat_step_parts_lr(p, g, m, v, p_bf16, n, lr, b1, b2, eps, wd, grad_scale, decoupled, step_counter,
+                                     cursor, loss_slot, loss_out, loss_cap, nparts, part_off, part_n, part, part_splits,
+                                     nullptr, stream);
+}
+
+int dct_adam_flat_step_parts_lr(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, int64_t n, float lr,
+                                float b1, float b2, float eps, float wd, float grad_scale, int decoupled,
+                                const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
+                                int loss_cap, int nparts, const int64_t* part_off, const int64_t* part_n,
+                                const float* const* part, const int* part_splits, const float* lr_tab, void* stream) {
   if (n <= 0) return 0;
-  if (!step_counter || (cursor && !loss_slot) || nparts < 0 || nparts > 3) return (int)hipErrorInvalidValue;
+  if (!step_counter || (cursor && !loss_slot) || nparts < 0 || nparts > 3 || !lr_tab_ok(lr_tab, step_counter))
+    return (int)hipErrorInvalidValue;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return (int)hipErrorInvalidValue;
   dct::AdamArgs a{};
   a.p = p; a.g = g; a.m = m; a.v = v; a.p_bf16 = p_bf16; a.n = n;
@@ -197,6 +215,7 @@ int dct_adam_flat_step_parts(float* p, const float* g, float* m, float* v, uint1
   a.grad_scale = grad_scale;
   a.decoupled = decoupled;
   a.step_counter = step_counter;
+  a.lr_tab = lr_tab;
   a.cursor = cursor;
   a.loss_slot = loss_slot;
   a.loss_out = loss_out;

@@ -27,6 +27,7 @@
 
 #include "dct_common.h"
 #include "kernels.h"
+#include "lr_table.h"
 
 namespace dct {
 
@@ -45,6 +46,7 @@ struct XgAdamArgs {
   unsigned* status;
   int world, rank;
   long long timeout_ticks;    // s_memrealtime (100 MHz)
+  const float* lr_tab;        // optional rate table (lr_table.h): the rate of the step after t - 1 steps
 };
 
 __device__ __forceinline__ void xa_adam(float& p, float g, float& m, float& v, const XgAdamArgs& a, float step_size,
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(256) void xg_allreduce_adam_kernel(XgAdamArgs a) {
   a.g[e0] = r0;
   if (e1 < a.n) a.g[e1] = r1;
   const float tf = (float)t;
-  const float step_size = a.lr / (1.f - pow_t(log2f(a.b1), tf));
+  const float step_size = lr_for(a.lr_tab, a.lr, (int)t - 1) / (1.f - pow_t(log2f(a.b1), tf));
   const float rbc2 = rsqrtf(1.f - pow_t(log2f(a.b2), tf));
   if (e0 < a.P) {
     xa_adam(p0, r0, m0, w0, a, step_size, rbc2);
@@ -157,7 +159,15 @@ int64_t dct_xg_adam_buffer_bytes(int64_t n, int world) { return 2 * (int64_t)wor
 int dct_xg_allreduce_adam(float* g, float* p, float* m, float* v, int64_t n, int64_t P, const int* step_counter,
                           float lr, float b1, float b2, float eps, float wd, void* recv, void* const* peers,
                           unsigned* status, int world, int rank, long long timeout_ticks, void* stream) {
-  if (world < 1 || world > dct::XA_MAXW || rank < 0 || rank >= world || !g || !p || !m || !v || !step_counter ||
+  return dct_xg_allreduce_adam_lr(g, p, m, v, n, P, step_counter, lr, b1, b2, eps, wd, recv, peers, status, world, rank,
+                                  timeout_ticks, nullptr, stream);
+}
+
+int dct_xg_allreduce_adam_lr(float* g, float* p, float* m, float* v, int64_t n, int64_t P, const int* step_counter,
+                             float lr, float b1, float b2, float eps, float wd, void* recv, void* const* peers,
+                             unsigned* status, int world, int rank, long long timeout_ticks, const float* lr_tab,
+                             void* stream) {
+  if (((uintptr_t)lr_tab & 15) || world < 1 || world > dct::XA_MAXW || rank < 0 || rank >= world || !g || !p || !m || !v || !step_counter ||
       !recv || !peers || !status || n < 1 || P < 1 || P > n || dct_xg_adam_buffer_bytes(n, world) > INT32_MAX)
     return (int)hipErrorInvalidValue;
   dct::XgAdamArgs a;
@@ -173,6 +183,7 @@ int dct_xg_allreduce_adam(float* g, float* p, float* m, float* v, int64_t n, int
   a.b2 = b2;
   a.eps = eps;
   a.wd = wd;
+  a.lr_tab = lr_tab;
   a.recv = reinterpret_cast<char*>(recv);
   a.peers = reinterpret_cast<char* const*>(peers);
   a.status = status;

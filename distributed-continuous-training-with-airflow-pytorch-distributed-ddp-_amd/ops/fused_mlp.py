@@ -112,6 +112,15 @@ def wave_supported(dims: Sequence[int], batch: int) -> bool:
     return bool(native().mlp_wave_supported([int(d) for d in dims], int(batch)))
 
 
+def _table_ptr(lr_tab: Optional[torch.Tensor]) -> int:
+    """Device pointer of a rate table (0: none), checked: cuda fp32, 4 header words and at least one rate."""
+    if lr_tab is None:
+        return 0
+    if not (lr_tab.is_cuda and lr_tab.dtype == torch.float32 and lr_tab.is_contiguous() and lr_tab.numel() >= 5):
+        raise ValueError("lr_tab must be a contiguous cuda fp32 rate table (4 header words + >= 1 rate)")
+    return lr_tab.data_ptr()
+
+
 class FusedMLPKernel:
     def __init__(self, dims: Sequence[int], bmax: int):
         if bmax not in (4, 16, TILE_BMAX):
@@ -202,8 +211,12 @@ class FusedMLPKernel:
               loss: str = "ce", grad_out: Optional[torch.Tensor] = None, step_counter: Optional[torch.Tensor] = None,
               cursor: Optional[torch.Tensor] = None, prof: Optional[torch.Tensor] = None,
               pending: Optional[torch.Tensor] = None, stage: Optional[torch.Tensor] = None,
-              stream: Optional[int] = None, xg=None, xg_timeout_s: float = 2.0):
+              stream: Optional[int] = None, xg=None, xg_timeout_s: float = 2.0,
+              lr_tab: Optional[torch.Tensor] = None):
         """Run ``steps`` fused optimizer steps (mode 0) or one gradient step (grad_out given).
+
+        ``lr_tab``: a device rate table (csrc/lr_table.h, trainer/lr_schedule.py) - every step takes its rate from the
+        table's entry for the steps taken before it (t0 + s, or the device step counter's) instead of ``lr``.
 
         ``xg``: a native ``PeerExchange`` -> data-parallel steps with the gradient all-reduce done
         inside the kernel over peer-mapped receive buffers (see ``parallel.xgmi``)."""
@@ -247,14 +260,14 @@ class FusedMLPKernel:
             int(seed) & 0xFFFFFFFF, int(step_base) & 0xFFFFFFFF, ptr(loss_out), mode, LOSS_KINDS[loss],
             ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending), ptr(stage),
             stream if stream is not None else stream_handle(),
-            **xg_args, **self._tile_args(p.device),
+            **xg_args, **self._tile_args(p.device), lr_tab=_table_ptr(lr_tab),
         )
 
     def prepare_train(self, p, m, v, X, Y, idx, n_items: int, batch: int, lr: float, betas=(0.9, 0.999),
                       eps: float = 1e-8, weight_decay: float = 0.0, dropout: float = 0.0, seed: int = 0,
                       loss_out: Optional[torch.Tensor] = None, loss: str = "ce",
                       step_counter: Optional[torch.Tensor] = None, xg=None, xg_timeout_s: float = 2.0,
-                      xg_ticks: Optional[torch.Tensor] = None) -> "BoundTrain":
+                      xg_ticks: Optional[torch.Tensor] = None, lr_tab: Optional[torch.Tensor] = None) -> "BoundTrain":
         """Validate the operands of persistent train-mode launches ONCE and bind them natively.
 
         ``BoundTrain.run(first_step, steps)`` then launches steps [first_step, first_step+steps)
@@ -288,8 +301,8 @@ class FusedMLPKernel:
             ptr(p), ptr(m), ptr(v), ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), int(batch), float(lr),
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, ptr(loss_out), 0 if loss_out is None else loss_out.numel(), LOSS_KINDS[loss],
-            ptr(step_counter), **xg_args, **self._tile_args(p.device))
-        return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws),
+            ptr(step_counter), **xg_args, **self._tile_args(p.device), lr_tab=_table_ptr(lr_tab))
+        return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws, lr_tab),
                           p.device.index or 0)
 
     # ------------------------------------------------------------ in-kernel all-reduce

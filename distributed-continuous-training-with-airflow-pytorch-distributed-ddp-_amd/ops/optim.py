@@ -63,10 +63,12 @@ def adam_flat_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
                betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
                decoupled: bool = False, p_bf16: Optional[torch.Tensor] = None,
                step_counter: Optional[torch.Tensor] = None, clip_coef: Optional[torch.Tensor] = None,
-               clip_value: float = 0.0):
+               clip_value: float = 0.0, lr_tab: Optional[torch.Tensor] = None):
     """In-place Adam on flat fp32 buffers; ``step`` is the 1-based step count after this update.  ``clip_coef`` (a
     one-element fp32 tensor on p's device, grad_clip_coef_'s ws[1:2]) is multiplied into ``grad_scale``;
-    ``clip_value`` > 0 clamps the scaled gradient to [-clip_value, clip_value].  ``g`` is not rewritten."""
+    ``clip_value`` > 0 clamps the scaled gradient to [-clip_value, clip_value].  ``g`` is not rewritten.
+    ``lr_tab`` (GPU, with ``step_counter``): a device rate table (csrc/lr_table.h, trainer/lr_schedule.py) - the step's
+    rate is its entry for ``*step_counter - 1`` steps taken instead of ``lr``."""
     n = p.numel()
     for t in (g, m, v):
         if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous() or t.device != p.device:
@@ -76,16 +78,22 @@ def adam_flat_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
             raise ValueError("p_bf16 must be a bf16 buffer of the same size")
         if step_counter is not None and not (step_counter.is_cuda and step_counter.dtype == torch.int32):
             raise ValueError("step_counter must be a cuda int32 tensor")
+        if lr_tab is not None and (step_counter is None or not lr_tab.is_cuda or lr_tab.dtype != torch.float32
+                                   or lr_tab.numel() < 5):
+            raise ValueError("lr_tab must be a cuda fp32 rate table (4 header words + >= 1 rate) used with step_counter")
         if clip_coef is not None or clip_value:
             native().adam_flat_step_clipped(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_bf16), n, float(lr),
                                             float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                                             max(1, int(step)), float(grad_scale), int(decoupled), ptr(step_counter),
-                                            0, 0, 0, 0, ptr(clip_coef), float(clip_value), stream_handle(p.device))
+                                            0, 0, 0, 0, ptr(clip_coef), float(clip_value), stream_handle(p.device),
+                                            ptr(lr_tab))
             return
         native().adam_flat(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p_bf16), n, float(lr), float(betas[0]),
                            float(betas[1]), float(eps), float(weight_decay), max(1, int(step)), float(grad_scale),
-                           int(decoupled), ptr(step_counter), stream_handle(p.device))
+                           int(decoupled), ptr(step_counter), stream_handle(p.device), ptr(lr_tab))
         return
+    if lr_tab is not None:
+        raise ValueError("adam_flat_: a rate table is read on the GPU; on the CPU pass the step's rate as lr")
     b1, b2 = betas
     gg = g * grad_scale if grad_scale != 1.0 else g
     if clip_coef is not None:
@@ -123,7 +131,8 @@ class FlatAdam:
 
     def __init__(self, flat_param: torch.Tensor, flat_grad: torch.Tensor, param_shapes: Sequence[torch.Size],
                  lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 amsgrad: bool = False, clip_val: Optional[float] = None, clip_algorithm: str = "norm"):
+                 amsgrad: bool = False, clip_val: Optional[float] = None, clip_algorithm: str = "norm",
+                 lr_schedule=None):
         if amsgrad:
             raise NotImplementedError("amsgrad is not supported")
         self.clip_val, self.clip_algorithm = check_clip_args(clip_val, clip_algorithm)
@@ -142,6 +151,10 @@ class FlatAdam:
         self.param_groups = [group]
         self.step_count = 0
         self.p_bf16: Optional[torch.Tensor] = None
+        # trainer/lr_schedule.py LrSchedule (or None: the constant param-group rate).  On the GPU the kernels read the
+        # step's rate from its device table at the device step count (a captured step follows the schedule); on the
+        # CPU the step gets that same rate as the scalar.
+        self.lr_schedule = lr_schedule
 
     @property
     def lr(self):
@@ -160,6 +173,12 @@ class FlatAdam:
             counter = self._device_counter()
             if bump_counter:
                 counter.add_(1)
+        lr, lr_tab = g["lr"], None
+        if self.lr_schedule is not None:
+            if self.p.is_cuda:
+                lr_tab = self.lr_schedule.device_table(self.p.device)
+            else:
+                lr = self.lr_schedule.rate_for(self.step_count - 1)
         clip_coef, clip_value = None, 0.0
         if self.clip_val is not None:
             # the gradient is clipped inside Adam (flat_g keeps the unclipped values): by norm, one kernel leaves the
@@ -172,23 +191,24 @@ class FlatAdam:
             cursor, loss, loss_out = epilogue
             b1, b2 = g["betas"]
             native().adam_flat_step_clipped(ptr(self.p), ptr(self.g), ptr(self.m), ptr(self.v), ptr(self.p_bf16),
-                                            self.p.numel(), float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                                            self.p.numel(), float(lr), float(b1), float(b2), float(g["eps"]),
                                             float(g["weight_decay"]), max(1, self.step_count), float(grad_scale), 0,
                                             ptr(counter), ptr(cursor), ptr(loss), ptr(loss_out), loss_out.numel(),
-                                            ptr(clip_coef), float(clip_value), stream_handle(self.p.device))
+                                            ptr(clip_coef), float(clip_value), stream_handle(self.p.device),
+                                            ptr(lr_tab))
             return
         if epilogue is not None:
             cursor, loss, loss_out = epilogue
             b1, b2 = g["betas"]
             native().adam_flat_step(ptr(self.p), ptr(self.g), ptr(self.m), ptr(self.v), ptr(self.p_bf16),
-                                    self.p.numel(), float(g["lr"]), float(b1), float(b2), float(g["eps"]),
+                                    self.p.numel(), float(lr), float(b1), float(b2), float(g["eps"]),
                                     float(g["weight_decay"]), max(1, self.step_count), float(grad_scale), 0,
                                     ptr(counter), ptr(cursor), ptr(loss), ptr(loss_out), loss_out.numel(),
-                                    stream_handle(self.p.device))
+                                    stream_handle(self.p.device), ptr(lr_tab))
             return
-        adam_flat_(self.p, self.g, self.m, self.v, self.step_count, g["lr"], g["betas"], g["eps"],
+        adam_flat_(self.p, self.g, self.m, self.v, self.step_count, lr, g["betas"], g["eps"],
                    g["weight_decay"], grad_scale=grad_scale, p_bf16=self.p_bf16, step_counter=counter,
-                   clip_coef=clip_coef, clip_value=clip_value)
+                   clip_coef=clip_coef, clip_value=clip_value, lr_tab=lr_tab)
 
     def clip_stats(self):
         """(norm, coef) of the last step's clipping by norm as Python floats (synchronises: tests and logging);

@@ -150,13 +150,14 @@ def _open_exchange(ctx: DistContext, supported: bool, nbytes, what: str, strict:
 
 
 def allreduce_adam_(xg, g, p, m, v, n_params: int, step_counter, lr: float, betas, eps: float,
-                    weight_decay: float, timeout: Optional[float] = None):
+                    weight_decay: float, timeout: Optional[float] = None, lr_tab=None):
     """Enqueue the fused peer all-reduce + Adam step (csrc/xg_adam.hip) on the current stream.
 
     ``g`` (fp32, the gradients then optionally the local loss) is replaced by the rank average -
     summed in rank order, so bit-identical on every rank - and Adam (L2 weight decay, step
     t = ``*step_counter``) updates ``p/m/v[:n_params]``.  Collective: every rank enqueues it once
-    per step, after the kernel that advanced the step counter."""
+    per step, after the kernel that advanced the step counter.  ``lr_tab``: a device rate table (csrc/lr_table.h) -
+    the step's rate is its entry for ``*step_counter - 1`` steps taken instead of ``lr``."""
     import torch
 
     from ..ops._native import native
@@ -171,7 +172,8 @@ def allreduce_adam_(xg, g, p, m, v, n_params: int, step_counter, lr: float, beta
     native().xg_allreduce_adam(g.data_ptr(), p.data_ptr(), m.data_ptr(), v.data_ptr(), g.numel(), n_params,
                                step_counter.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(eps),
                                float(weight_decay), xg, timeout_s() if timeout is None else float(timeout),
-                               torch.cuda.current_stream(p.device).cuda_stream)
+                               torch.cuda.current_stream(p.device).cuda_stream,
+                               0 if lr_tab is None else lr_tab.data_ptr())
 
 
 def device_barrier(xg, stream: int, timeout: Optional[float] = None):

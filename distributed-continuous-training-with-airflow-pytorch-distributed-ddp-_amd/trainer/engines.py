@@ -17,6 +17,10 @@
 * ``AutogradEngine`` (any TrainModule; CPU/gloo plumbing path and the large-model GPU path):
   ``training_step`` + autograd, parameters/gradients as views of flat buffers, the bucketed
   reducer hooked on ``post_accumulate_grad`` (overlap with backward), flat Adam.
+
+A learning-rate scheduler returned by ``configure_optimizers()`` (trainer/lr_schedule.py) is followed by the autograd
+all three engines (the graph engine: trainer/graph_engine.py): every launch that applies Adam reads the step's rate
+from a device table at the device step count, so persistent launches and captured graphs follow a per-step schedule.
 """
 from __future__ import annotations
 
@@ -38,17 +42,21 @@ from ..parallel.reducer import NativeBucketReducer, TorchBucketReducer, plan_buc
 from ..utils.debug import assert_reducer_complete, check_device
 from ..utils.debug import enabled as debug_enabled
 from ..utils.debug import reducer_timing_enabled
+from .lr_schedule import LrSchedule, parse_configure_optimizers
 
 
 def adam_hparams_from(optimizer) -> Optional[Dict]:
-    """Extract Adam hyper-parameters from a configure_optimizers() result (None if not Adam)."""
-    opt = optimizer
-    if isinstance(opt, (list, tuple)):
-        if len(opt) != 1:
-            return None
-        opt = opt[0]
-    if isinstance(opt, dict):
-        opt = opt.get("optimizer")
+    """Extract Adam hyper-parameters from a configure_optimizers() result (None if not Adam).  ``lr`` is the rate the
+    optimizer holds now; a returned lr scheduler is read by parse_configure_optimizers (trainer/lr_schedule.py)."""
+    try:
+        opt, _ = parse_configure_optimizers(optimizer)
+    except ValueError:
+        return None
+    return adam_hparams_of(opt)
+
+
+def adam_hparams_of(opt) -> Optional[Dict]:
+    """Adam hyper-parameters of one optimizer (what parse_configure_optimizers returned), None if it is not Adam."""
     if type(opt) is not torch.optim.Adam:
         return None
     g = opt.param_groups[0]
@@ -93,8 +101,12 @@ class FusedMLPEngine(_EngineBase):
         return FusedMLPKernel.supported(spec["dims"], batch_size)
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,
-                 steps_per_launch: int = 0, use_graph: Optional[bool] = None):
+                 steps_per_launch: int = 0, use_graph: Optional[bool] = None, lr_schedule=None):
         super().__init__(model, ctx, batch_size, seed)
+        # trainer/lr_schedule.py LrSchedule or None: every launch that applies Adam - the persistent trainers (with
+        # and without the in-kernel exchange), the update-then-grad kernel, flat Adam and the peer all-reduce + Adam
+        # of the DDP step path - reads the step's rate from its device table at the device step count
+        self.lr_schedule = lr_schedule
         spec = model.fused_spec()
         self.dims = spec["dims"]
         self.dropout = float(spec["dropout"])
@@ -268,10 +280,15 @@ class FusedMLPEngine(_EngineBase):
         return rows.numel()
 
     # ------------------------------------------------------------------ train
+    def _lr_tab(self) -> Optional[torch.Tensor]:
+        """The schedule's device table (bound from here on: a fixed address), or None."""
+        return self.lr_schedule.device_table(self.device) if self.lr_schedule is not None else None
+
     def _bound_launch(self, n_items: int, loss_out: torch.Tensor):
         """The persistent train launch bound to (index list, loss buffer, exchange): validated once,
         then every run_steps call is one short native call (ops/fused_mlp.py BoundTrain)."""
-        key = (n_items, loss_out.data_ptr(), loss_out.numel())
+        tab = self._lr_tab()
+        key = (n_items, loss_out.data_ptr(), loss_out.numel(), 0 if tab is None else tab.data_ptr())
         bl = getattr(self, "_bound", None)
         if bl is None or self._bound_key != key:
             a = self.adam
@@ -280,7 +297,8 @@ class FusedMLPEngine(_EngineBase):
                                            weight_decay=a["weight_decay"], dropout=self.dropout, seed=self.rank_seed,
                                            loss_out=loss_out, loss=self.loss, step_counter=self.step_counter,
                                            xg=self.xg, xg_timeout_s=getattr(self, "xg_timeout_s", 20.0),
-                                           xg_ticks=getattr(self, "xg_ticks", None) if self.xg is not None else None)
+                                           xg_ticks=getattr(self, "xg_ticks", None) if self.xg is not None else None,
+                                           lr_tab=tab)
             self._bound, self._bound_key = bl, key
         return bl
 
@@ -337,7 +355,7 @@ class FusedMLPEngine(_EngineBase):
         if self.fused_update:  # the last step's update is still pending: apply it
             a = self.adam
             adam_flat_(self.p, self.gbuf[: self.P], self.m, self.v, 1, a["lr"], a["betas"], a["eps"],
-                       a["weight_decay"], step_counter=self.step_counter)
+                       a["weight_decay"], step_counter=self.step_counter, lr_tab=self._lr_tab())
             self.pending.zero_()
         # the last step's reduced loss is flushed by the next kernel; flush it here instead
         last = first_step + steps - 1
@@ -358,7 +376,8 @@ class FusedMLPEngine(_EngineBase):
                               steps=1, t0=0, lr=a["lr"], betas=a["betas"], eps=a["eps"],
                               weight_decay=a["weight_decay"], dropout=self.dropout, seed=self.rank_seed,
                               loss=self.loss, grad_out=self.gbuf, step_counter=self.step_counter,
-                              cursor=self.cursor, loss_out=loss_out, pending=self.pending, stage=self.stage)
+                              cursor=self.cursor, loss_out=loss_out, pending=self.pending, stage=self.stage,
+                              lr_tab=self._lr_tab())
             self.comm.allreduce(self.gbuf.data_ptr(), self.P + 1, nat.DT_F32, nat.OP_AVG, stream)
             return
         self.kernel.train(self.p, None, None, self.X, self.Y, self.idx, n_items=n_items, batch=self.B, steps=1,
@@ -369,11 +388,11 @@ class FusedMLPEngine(_EngineBase):
             from ..parallel.xgmi import allreduce_adam_
 
             allreduce_adam_(self.gx, self.gbuf, self.p, self.m, self.v, self.P, self.step_counter, a["lr"],
-                            a["betas"], a["eps"], a["weight_decay"], timeout=self.xg_timeout_s)
+                            a["betas"], a["eps"], a["weight_decay"], timeout=self.xg_timeout_s, lr_tab=self._lr_tab())
             return
         self.comm.allreduce(self.gbuf.data_ptr(), self.P + 1, nat.DT_F32, nat.OP_AVG, stream)
         adam_flat_(self.p, self.gbuf[: self.P], self.m, self.v, 1, a["lr"], a["betas"], a["eps"],
-                   a["weight_decay"], step_counter=self.step_counter)
+                   a["weight_decay"], step_counter=self.step_counter, lr_tab=self._lr_tab())
 
     def _get_graph(self, n_items: int, C: int, loss_out: torch.Tensor):
         key = (n_items, C, loss_out.data_ptr())
@@ -458,7 +477,7 @@ class FusedMLPEngine(_EngineBase):
                               steps=k, t0=0, lr=a["lr"], betas=a["betas"], eps=a["eps"],
                               weight_decay=a["weight_decay"], dropout=self.dropout, seed=self.rank_seed,
                               loss_out=loss_out, loss=self.loss, step_counter=self.step_counter, xg=self.xg,
-                              xg_timeout_s=probe_timeout_s())
+                              xg_timeout_s=probe_timeout_s(), lr_tab=self._lr_tab())
         else:
             full, self.xg_timeout_s = self.xg_timeout_s, probe_timeout_s()
             try:
@@ -544,7 +563,9 @@ class AutogradEngine(_EngineBase):
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, bucket_cap_bytes: int = 8 << 20,
                  first_bucket_bytes: int = 1 << 20, gradient_clip_val: Optional[float] = None,
-                 gradient_clip_algorithm: str = "norm"):
+                 gradient_clip_algorithm: str = "norm", optimizers=None):
+        """``optimizers``: the model's configure_optimizers() result when the caller already has it (the Trainer, so
+        that optimizer and lr scheduler are created once); None calls it here."""
         super().__init__(model, ctx, batch_size, seed)
         # gradient clipping (Trainer(gradient_clip_val, gradient_clip_algorithm)): after the all-reduce, on the
         # averaged gradient, inside the flat Adam - p.grad keeps the unclipped gradient (ops/optim.py)
@@ -616,15 +637,22 @@ class AutogradEngine(_EngineBase):
             from ..utils.tracing import DevicePhaseTimer
 
             self.phase_timer = DevicePhaseTimer(["fwd", "bwd", "allreduce", "opt"], dev)
-        opt = model.configure_optimizers()
-        hp = adam_hparams_from(opt)
+        opt = model.configure_optimizers() if optimizers is None else optimizers
+        torch_opt, sched_cfg = parse_configure_optimizers(opt)  # (parsed once: ValueError for what is not supported)
+        hp = adam_hparams_of(torch_opt)
+        # a returned lr scheduler (trainer/lr_schedule.py): with flat Adam its rates reach the kernel through the
+        # device table (eager and captured steps) or as the step's scalar (CPU); with another torch optimizer the
+        # real scheduler is stepped in Python beside it (live)
+        self.lr_schedule = None
+        if sched_cfg is not None:
+            self.lr_schedule = LrSchedule.from_config(torch_opt, sched_cfg, live=hp is None)
         if hp is not None:
             self.optimizer = FlatAdam(self.flat_p, self.flat_g, [p.shape for p in params], clip_val=self.clip_val,
-                                      clip_algorithm=self.clip_algorithm, **hp)
+                                      clip_algorithm=self.clip_algorithm, lr_schedule=self.lr_schedule, **hp)
             self.torch_optimizer = None
         else:
             self.optimizer = None
-            self.torch_optimizer = opt[0] if isinstance(opt, (list, tuple)) else opt
+            self.torch_optimizer = torch_opt
         # native-op fast paths (ops/nn.py bound_params): weight-gradient accumulation straight into
         # the flat bucket buffer, and bf16 shadow weights maintained by the fused Adam
         self._shadows = None
@@ -726,7 +754,11 @@ class AutogradEngine(_EngineBase):
                     self._torch_clip_stats = (norm, torch.clamp(self.clip_val / (norm + 1e-6), max=1.0))
                 else:
                     torch.nn.utils.clip_grad_value_(self.params, self.clip_val)
+            if self.lr_schedule is not None:
+                self.lr_schedule.before_step()
             self.torch_optimizer.step()
+            if self.lr_schedule is not None:
+                self.lr_schedule.after_step(batch_idx)
         self._pm(4)
         return loss
 

@@ -77,7 +77,7 @@ class GraphMLPEngine:
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,
                  bucket_cap_bytes: int = 8 << 20, first_bucket_bytes: int = 1 << 20, use_graph: Optional[bool] = None,
-                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm"):
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm", lr_schedule=None):
         native().reload_knobs()  # bind time: the native launchers' DCT_* knobs
         # gradient clipping: the executor then keeps every dW in g (no split-K slices handed to Adam, no riding Adam,
         # as under DCT_DW_INTO_ADAM=0), takes the norm of g[:P] after the all-reduce and runs one clipped flat Adam
@@ -93,6 +93,9 @@ class GraphMLPEngine:
         self.dims = list(spec["dims"])
         self.loss = spec["loss"]
         self.adam = adam
+        # trainer/lr_schedule.py LrSchedule or None: every Adam launch of the step (riding ranges, adam_range, the flat
+        # launches) reads its rate from the schedule's device table at the device step count
+        self.lr_schedule = lr_schedule
         self.device = dev = ctx.device
         if use_graph is None:
             use_graph = False  # (the eager C++ enqueue beats the replays; use_graph=True for A/Bs)
@@ -278,6 +281,8 @@ class GraphMLPEngine:
         if first_step + steps > math.ceil(n_items / self.B) or loss_out.numel() < first_step + steps:
             raise ValueError("step range exceeds the epoch's batches / loss buffer")
         self.cursor.fill_(first_step)
+        if self.lr_schedule is not None:
+            self.exe.set_lr_table(self.lr_schedule.device_table(self.device).data_ptr())
         full_steps = max(0, min(first_step + steps, n_full) - first_step)
         g = self._get_graph(n_items, loss_out) if (self.use_graph and full_steps > 0) else None
         for _ in range(full_steps):

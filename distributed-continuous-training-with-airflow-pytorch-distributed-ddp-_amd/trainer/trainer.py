@@ -25,14 +25,15 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..ckpt.callbacks import ModelCheckpoint
+from ..ckpt.callbacks import LearningRateMonitor, ModelCheckpoint
 from ..ckpt.lightning_io import build_checkpoint, load_checkpoint, save_checkpoint
 from ..data.dataset import dataset_tensors
 from ..data.sampler import distributed_indices
 from ..ops.optim import check_clip_args
 from ..parallel.dist import DistContext, init_distributed, shutdown
-from .engines import AutogradEngine, FusedMLPEngine, adam_hparams_from
+from .engines import AutogradEngine, FusedMLPEngine, adam_hparams_of
 from .graph_engine import GraphMLPEngine
+from .lr_schedule import LrSchedule, parse_configure_optimizers
 from ..utils.debug import assert_reducer_ordering
 from ..utils.tracing import PhaseTimer, trace_range
 
@@ -119,6 +120,11 @@ class Trainer:
     @property
     def is_global_zero(self) -> bool:
         return self.global_rank == 0
+
+    @property
+    def lr_schedule(self) -> Optional[LrSchedule]:
+        """The lr scheduler of the fit (configure_optimizers()'s "lr_scheduler") as the engine runs it, or None."""
+        return getattr(self.engine, "lr_schedule", None)
 
     @property
     def checkpoint_callback(self) -> Optional[ModelCheckpoint]:
@@ -229,7 +235,9 @@ class Trainer:
         choice = self.engine_choice
         if choice == "auto":
             choice = os.environ.get("DCT_ENGINE", "auto")
-        adam = adam_hparams_from(model.configure_optimizers())
+        optimizers = model.configure_optimizers()
+        torch_opt, sched_cfg = parse_configure_optimizers(optimizers)  # (ValueError: > 1 optimizer / scheduler)
+        adam = adam_hparams_of(torch_opt)
         clip = dict(gradient_clip_val=self.gradient_clip_val, gradient_clip_algorithm=self.gradient_clip_algorithm)
         if self.gradient_clip_val is not None and choice == "fused":
             raise RuntimeError("engine='fused' cannot clip gradients: the persistent small-MLP kernels apply Adam "
@@ -240,17 +248,21 @@ class Trainer:
         if choice == "auto" and fused_ok and batch_size > 16 and GraphMLPEngine.applicable(model, ctx.device, batch_size):
             fused_ok = False  # batch > 16: the graph engine keeps the models it takes; the batch-tiled trainer the rest
         if choice in ("auto", "fused") and fused_ok:
-            return FusedMLPEngine(model, ctx, batch_size, seed, adam, steps_per_launch=self.steps_per_launch)
+            sched = dict(lr_schedule=LrSchedule.from_config(torch_opt, sched_cfg)) if sched_cfg is not None else {}
+            return FusedMLPEngine(model, ctx, batch_size, seed, adam, steps_per_launch=self.steps_per_launch, **sched)
         if choice == "fused":
             raise RuntimeError("engine='fused' requested but the model/device/batch is not supported by it")
         if choice in ("auto", "graph") and adam is not None and GraphMLPEngine.applicable(model, ctx.device, batch_size):
+            sched = dict(lr_schedule=LrSchedule.from_config(torch_opt, sched_cfg)) if sched_cfg is not None else {}
             return GraphMLPEngine(model, ctx, batch_size, seed, adam, self.strategy.bucket_cap_bytes,
-                                  self.strategy.first_bucket_bytes, **clip)
+                                  self.strategy.first_bucket_bytes, **clip, **sched)
         if choice == "graph":
             raise RuntimeError("engine='graph' requested but the model/device is not supported by it")
         model.to(ctx.device)
+        # (with a scheduler the engine takes this call's optimizer and scheduler: they belong together)
+        opts = dict(optimizers=optimizers) if sched_cfg is not None else {}
         return AutogradEngine(model, ctx, batch_size, seed, self.strategy.bucket_cap_bytes,
-                              self.strategy.first_bucket_bytes, **clip)
+                              self.strategy.first_bucket_bytes, **clip, **opts)
 
     # ------------------------------------------------------------------ checkpoints
     def _checkpoint_dict(self, batches_in_epoch: int = 0, val_batches: int = 0) -> Dict[str, Any]:
@@ -261,10 +273,15 @@ class Trainer:
             if isinstance(cb, ModelCheckpoint):
                 callbacks[cb.state_key] = cb.state_dict()
         hp = dict(model.hparams) if getattr(model, "hparams", None) else None
+        opt_state = self.engine.optimizer_state_dict()
+        sched = self.lr_schedule
+        if sched is not None:  # the current rate and initial_lr, as torch's optimizer would save them
+            opt_state["param_groups"][0].update(sched.param_group_overlay())
         ckpt = build_checkpoint(model.state_dict(), epoch=self.current_epoch, global_step=self.global_step,
-                                optimizer_states=[self.engine.optimizer_state_dict()], callbacks=callbacks,
+                                optimizer_states=[opt_state], callbacks=callbacks,
                                 hyper_parameters=hp, hparams_name=getattr(model, "_hparams_name", "kwargs"),
-                                batches_in_epoch=batches_in_epoch, val_batches=val_batches)
+                                batches_in_epoch=batches_in_epoch, val_batches=val_batches,
+                                lr_schedulers=[sched.state_dict()] if sched is not None else None)
         model.on_save_checkpoint(ckpt)
         return ckpt
 
@@ -281,6 +298,9 @@ class Trainer:
         self.engine.load_from_model()
         if ckpt.get("optimizer_states"):
             self.engine.load_optimizer_state(ckpt["optimizer_states"][0], int(ckpt.get("global_step", 0)))
+        if self.lr_schedule is not None and ckpt.get("lr_schedulers"):
+            groups = (ckpt.get("optimizer_states") or [{}])[0].get("param_groups") or [None]
+            self.lr_schedule.load_state(ckpt["lr_schedulers"][0], groups[0])
         for cb in self.callbacks:
             if isinstance(cb, ModelCheckpoint) and cb.state_key in ckpt.get("callbacks", {}):
                 cb.load_state_dict(ckpt["callbacks"][cb.state_key])
@@ -333,6 +353,8 @@ class Trainer:
                 self.epoch_times.append(epoch_t)
                 samples = len(train_rows)
                 self.callback_metrics.update(val_metrics)
+                if self.lr_schedule is not None:  # interval "epoch": stepped after validation (the monitored metric
+                    self.lr_schedule.end_epoch(epoch, self.callback_metrics)  # is the cross-rank mean: same on all)
                 if val_metrics:
                     self._log_metrics(val_metrics, self.global_step)
                 extra = {"epoch_time_s": epoch_t, "train_time_s": train_t,
@@ -409,7 +431,10 @@ class Trainer:
     def _train_epoch(self, epoch: int, B: int, shuffle: bool) -> int:
         self._stage = "train"
         eng = self.engine
+        sched = self.lr_schedule
         if getattr(eng, "epoch_engine", False):
+            if sched is not None:
+                sched.begin_epoch(self.global_step, eng.steps_per_epoch(), device=eng.device)
             losses = eng.train_epoch(epoch, shuffle)
             n = losses.numel()
             first = self.global_step
@@ -422,10 +447,16 @@ class Trainer:
             self._log_series("train_loss", [(first + k - 1, lv[k - 1]) for k in range(k0, n + 1, ev)])
             if n:
                 self.callback_metrics["train_loss"] = lv[-1]
+            self._log_learning_rates(first, n)
             return n
         local = eng.epoch_local_indices(len(eng.train_rows), epoch, shuffle)
         rows_all = eng.train_rows[local]
         n_steps = math.ceil(len(rows_all) / B)
+        first = self.global_step
+        if sched is not None:
+            # (max_steps ends the epoch early: a step-interval scheduler is advanced by the steps that run)
+            n_fill = n_steps if self.max_steps <= 0 else max(1, min(n_steps, self.max_steps - first))
+            sched.begin_epoch(first, n_fill, device=eng.device)
         for bi in range(n_steps):
             rows = rows_all[bi * B: (bi + 1) * B]
             self._cur_batch_size = len(rows)
@@ -451,7 +482,18 @@ class Trainer:
                 self.callback_metrics.update(m)
             if 0 < self.max_steps <= self.global_step:
                 break
+        self._log_learning_rates(first, self.global_step - first)
         return n_steps
+
+    def _log_learning_rates(self, first: int, n: int):
+        """LearningRateMonitor callbacks: the rates of the epoch's n steps (global steps first ..) from the schedule's
+        host copy - nothing is read back from the device."""
+        sched = self.lr_schedule
+        if sched is None or n <= 0:
+            return
+        for cb in self.callbacks:
+            if isinstance(cb, LearningRateMonitor):
+                self._log_series(sched.name, cb.points(sched, first, n, self.log_every_n_steps))
 
     @torch.no_grad()
     def _validate(self, VB: int, limit_batches: Optional[int] = None, sanity: bool = False) -> Dict[str, float]:
