@@ -937,6 +937,40 @@ PYBIND11_MODULE(_dct_native, m) {
   m.def("mlp_tile_ws_floats", [](const std::vector<int>& dims, int B) {
     return (int64_t)dct_mlp_tile_ws_floats(dims.data(), (int)dims.size() - 1, B);
   });
+  // batch-tiled inference (mlp_infer.hip): the shape check and workspace size need no device
+  m.def("mlp_infer_supported", [](const std::vector<int>& dims) {
+    return dims.size() >= 2 && dct_mlp_infer_ws_bytes(dims.data(), (int)dims.size() - 1, 1) != 0;
+  }, py::arg("dims"));
+  m.def("mlp_infer_ws_bytes", [](const std::vector<int>& dims, int64_t n) {
+    return dims.size() >= 2 ? (int64_t)dct_mlp_infer_ws_bytes(dims.data(), (int)dims.size() - 1, n) : (int64_t)0;
+  }, py::arg("dims"), py::arg("n"));
+  m.def("mlp_infer",
+        [](const std::vector<int>& dims, uintptr_t p, uintptr_t X, int ldx, uintptr_t idx, uintptr_t Y, int64_t n,
+           uintptr_t norm_mean, uintptr_t norm_std, int loss_kind, uintptr_t logits_out, uintptr_t probs_out,
+           uintptr_t pred_out, uintptr_t ws, int64_t ws_bytes, uintptr_t stats, int grid, uintptr_t stream) {
+          if (dims.size() < 2) throw std::invalid_argument("mlp_infer: dims");
+          dct::MlpInferArgs a{};
+          a.p = P<const float>(p);
+          a.X = P<const float>(X);
+          a.ldx = ldx;
+          a.idx = P<const int>(idx);
+          a.Y = P<const int>(Y);
+          a.n = n;
+          a.norm_mean = P<const float>(norm_mean);
+          a.norm_std = P<const float>(norm_std);
+          a.loss_kind = loss_kind;
+          a.logits_out = P<float>(logits_out);
+          a.probs_out = P<float>(probs_out);
+          a.pred_out = P<int>(pred_out);
+          a.ws = P<void>(ws);
+          a.ws_bytes = ws_bytes;
+          a.stats = P<void>(stats);
+          check(dct_mlp_infer(dims.data(), (int)dims.size() - 1, &a, grid, reinterpret_cast<void*>(stream)),
+                "mlp_infer");
+        },
+        py::arg("dims"), py::arg("p"), py::arg("X"), py::arg("ldx"), py::arg("idx"), py::arg("Y"), py::arg("n"),
+        py::arg("norm_mean"), py::arg("norm_std"), py::arg("loss_kind"), py::arg("logits_out"), py::arg("probs_out"),
+        py::arg("pred_out"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stats"), py::arg("grid"), py::arg("stream"));
   m.def("mlp_xg_slab_granules", [](const std::vector<int>& dims) {
     return (int64_t)dct_mlp_xg_slab_granules(dims.data(), (int)dims.size() - 1);
   });

@@ -132,6 +132,28 @@ struct MlpArgs {
 
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
 
+// One launch of the batch-tiled inference kernel (mlp_infer.hip): forward only, rows 0 .. n - 1 of the index
+// list (or of X itself), per-row outputs and - with labels - order-independent statistics.
+struct MlpInferArgs {
+  const float* p;  // flat params (torch state_dict order), 16-byte aligned
+  const float* X;
+  int ldx;          // row stride of X (floats)
+  const int* idx;   // optional [n] rows of X; null: rows 0 .. n - 1
+  const int* Y;     // optional labels, indexed like X's rows; null: no statistics
+  long long n;
+  const float* norm_mean;  // optional [D0], both or neither: the gather computes (x - mean) / std in fp32
+  const float* norm_std;   // (a std of 0 is replaced by 1 on the host)
+  int loss_kind;           // 0 = CE, 1 = MSE vs one-hot
+  float* logits_out;       // optional [n][C]
+  float* probs_out;        // optional [n][C], softmax with the row maximum subtracted
+  int* pred_out;           // optional [n], argmax (lowest index on ties)
+  // with Y: slot workspace of dct_mlp_infer_ws_bytes(dims, L, n) bytes and the statistics, 2 + C * C words of
+  // 8 bytes: [0] the loss sum (fp64), [1] the correct count (int64), [2 + y * C + pred] the confusion matrix (int64)
+  void* ws;
+  long long ws_bytes;
+  void* stats;
+};
+
 // fills *sh for dims[0 .. L] and plans of up to bmax rows per step (mlp_block = -1: auto, until the plan stamps
 // its knob copy); -1 when L is outside 2 .. MLP_MAXL, else 0 with sh->supported set
 int mlp_make_shape(MlpShape* sh, const int* dims, int L, int bmax);
@@ -169,4 +191,7 @@ size_t dct_mlp_xg_slab_granules(const int* dims, int L);
 int dct_mlp_tile_supported(const int* dims, int L);
 long long dct_mlp_tile_ws_floats(const int* dims, int L, int B);
 int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream);
+// batch-tiled forward-only inference for the shapes dct_mlp_tile_supported takes (mlp_infer.hip); grid <= 0: default
+int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, void* stream);
+long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n);
 }

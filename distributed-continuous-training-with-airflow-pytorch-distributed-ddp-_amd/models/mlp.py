@@ -65,6 +65,15 @@ class MLPClassifier(TrainModule):
         self.log("val_acc", acc, sync_dist=True, prog_bar=True)
         return loss
 
+    def test_step(self, batch, batch_idx):
+        x, y = batch
+        logits = self(x)
+        loss = self.compute_loss(logits, y)
+        acc = (torch.argmax(logits, dim=1) == y).float().mean()
+        self.log("test_loss", loss, sync_dist=True, prog_bar=True)
+        self.log("test_acc", acc, sync_dist=True, prog_bar=True)
+        return loss
+
     def configure_optimizers(self):
         return torch.optim.Adam(self.parameters(), lr=self.lr)
 

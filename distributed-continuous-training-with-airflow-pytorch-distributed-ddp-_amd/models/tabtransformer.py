@@ -117,6 +117,15 @@ class TabTransformer(TrainModule):
         self.log("val_acc", acc, sync_dist=True, prog_bar=True)
         return loss
 
+    def test_step(self, batch, batch_idx):
+        x, y = batch
+        logits = self(x)
+        loss = F.cross_entropy(logits, y)
+        acc = (logits.argmax(1) == y).float().mean()
+        self.log("test_loss", loss, sync_dist=True, prog_bar=True)
+        self.log("test_acc", acc, sync_dist=True, prog_bar=True)
+        return loss
+
     def ddp_block_groups(self):
         """Blocks grouped for data-parallel gradient buckets, in backward order: the upper half of
         the blocks (with the head / final LayerNorm, whose gradients come first), then the rest

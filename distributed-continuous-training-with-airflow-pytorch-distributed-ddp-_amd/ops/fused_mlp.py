@@ -132,6 +132,7 @@ class FusedMLPKernel:
         self._plan = None
         self._eval_plan = None
         self._tile_ws = None  # slot workspace of the batch-tiled trainer (csrc/mlp_tile.hip)
+        self._infer_ws_buf = None  # slot workspace of the inference kernel's statistics (csrc/mlp_infer.hip)
 
     def _tile_args(self, device) -> dict:
         """The batch-tiled trainer's slot workspace (partial gradients per tile + the fold's arrival
@@ -348,6 +349,81 @@ class FusedMLPKernel:
         g = grid or max(1, min(chunks, 256))
         plan.eval(ptr(p), ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), LOSS_KINDS[loss],
                   ptr(acc_out), ptr(logits_out), int(g), stream if stream is not None else stream_handle())
+
+    # ------------------------------------------------------------ batch-tiled inference
+    @staticmethod
+    def infer_supported(dims: Sequence[int]) -> bool:
+        """The batch-tiled inference kernel (csrc/mlp_infer.hip) takes this architecture: 2 or 3 linear layers,
+        D0 1..32, hidden widths multiples of 16 in 16..128, 2..4 classes.  No GPU needed."""
+        return bool(native().mlp_infer_supported([int(d) for d in dims]))
+
+    def _infer_ws(self, device, n: int) -> torch.Tensor:
+        """The statistics' slot workspace (at most 4096 slots), allocated once and grown on demand."""
+        need = int(native().mlp_infer_ws_bytes(self.dims, int(n))) // 8
+        ws = self._infer_ws_buf
+        if ws is None or ws.device != device or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.int64, device=device)
+            self._infer_ws_buf = ws
+        return ws
+
+    def infer(self, p, X, n: int, idx: Optional[torch.Tensor] = None, Y: Optional[torch.Tensor] = None,
+              loss: str = "ce", logits_out: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
+              pred_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, norm=None,
+              grid: Optional[int] = None, stream: Optional[int] = None):
+        """One forward-only launch over rows ``idx[0 .. n)`` of ``X`` (``idx=None``: rows ``0 .. n - 1``).
+
+        Per-row outputs, each optional: ``logits_out`` / ``probs_out`` fp32 [n, C], ``pred_out`` int32 [n] (argmax,
+        lowest index on ties).  ``norm=(mean, std)``: cuda fp32 [D0] each, the gather computes ``(x - mean) / std``
+        (the caller replaces a zero std by 1).  With labels ``Y`` (int32, indexed like X's rows) the launch also
+        writes ``stats_out``, ONE cuda int64 buffer of ``2 + C * C`` words: word 0 holds the bits of the fp64 loss sum
+        (``stats_out[:1].view(torch.float64)``), word 1 the correct count, words ``2 + y * C + pred`` the confusion
+        matrix (rows = label, columns = prediction); ``infer_stats`` unpacks it.  The statistics depend on the inputs
+        and ``n`` only - not on ``grid``, not on the run.  Without ``Y`` nothing is written to ``stats_out``."""
+        if not self.infer_supported(self.dims):
+            raise ValueError(f"the inference kernel does not take the architecture {self.dims}")
+        self._check_params(p)
+        if p.data_ptr() % 16:
+            raise ValueError("the flat parameter buffer must lie on a 16-byte boundary")
+        n = int(n)
+        C = self.dims[-1]
+        if n < 1:
+            raise ValueError("n must be >= 1")
+        if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.stride(1) == 1):
+            raise ValueError("X must be a cuda fp32 [N, D] row-major tensor")
+        if X.shape[1] < self.dims[0]:
+            raise ValueError(f"X has {X.shape[1]} features, model expects {self.dims[0]}")
+        if idx is None:
+            if n > X.shape[0]:
+                raise ValueError(f"n = {n} rows asked of a table of {X.shape[0]}")
+        elif not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() >= n):
+            raise ValueError("idx must be cuda int32 with at least n entries")
+        if Y is not None:
+            if not (Y.is_cuda and Y.dtype == torch.int32 and Y.is_contiguous() and Y.numel() == X.shape[0]):
+                raise ValueError("Y must be cuda int32 [N]")
+            if stats_out is None or not (stats_out.is_cuda and stats_out.dtype == torch.int64
+                                         and stats_out.is_contiguous() and stats_out.numel() >= 2 + C * C):
+                raise ValueError(f"stats_out must be a contiguous cuda int64 buffer of >= {2 + C * C} words")
+        for name, t, dt, cnt in (("logits_out", logits_out, torch.float32, n * C),
+                                 ("probs_out", probs_out, torch.float32, n * C), ("pred_out", pred_out, torch.int32, n)):
+            if t is not None and not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= cnt):
+                raise ValueError(f"{name} must be a contiguous cuda {dt} buffer of >= {cnt} entries")
+        mean = std = None
+        if norm is not None:
+            mean, std = norm
+            for t in (mean, std):
+                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self.dims[0]):
+                    raise ValueError(f"norm = (mean, std) must be contiguous cuda fp32 [{self.dims[0]}] each")
+        ws = self._infer_ws(p.device, n) if Y is not None else None
+        native().mlp_infer(self.dims, ptr(p), ptr(X), X.stride(0), ptr(idx), ptr(Y), n, ptr(mean), ptr(std),
+                           LOSS_KINDS[loss], ptr(logits_out), ptr(probs_out), ptr(pred_out), ptr(ws),
+                           0 if ws is None else ws.numel() * 8, ptr(stats_out) if Y is not None else 0,
+                           int(grid or 0), stream if stream is not None else stream_handle())
+
+    def infer_stats(self, stats_out: torch.Tensor):
+        """(loss sum: float, correct: int, confusion: int64 [C, C] on the CPU) of an ``infer`` launch (one sync)."""
+        C = self.dims[-1]
+        host = stats_out[: 2 + C * C].cpu()
+        return float(host[:1].view(torch.float64)[0]), int(host[1]), host[2:].reshape(C, C).clone()
 
 
 # the current stream's raw handle without building a torch.cuda.Stream object (one C call); the

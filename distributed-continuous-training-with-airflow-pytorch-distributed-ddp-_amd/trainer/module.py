@@ -95,6 +95,12 @@ class TrainModule(nn.Module):
     def validation_step(self, batch, batch_idx):
         return None
 
+    def test_step(self, batch, batch_idx):
+        return None
+
+    def predict_step(self, batch, batch_idx):
+        return self(batch[0] if isinstance(batch, (list, tuple)) else batch)
+
     def configure_optimizers(self):
         return torch.optim.Adam(self.parameters(), lr=1e-3)
 

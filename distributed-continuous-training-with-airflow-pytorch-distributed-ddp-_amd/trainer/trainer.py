@@ -107,6 +107,13 @@ class Trainer:
         self._epoch_logs: Dict[str, List] = {}
         self._cur_batch_size = 1
         self.should_stop = False
+        # validate / test / predict (trainer/evaluate.py): the confusion matrix of the last native validate / test
+        # (int64 [C, C], rows = label, summed over ranks; None on the generic path), and an optional (mean, std) of
+        # fp32 [D0] tensors that makes those calls score (x - mean) / std
+        self.last_confusion_matrix: Optional[torch.Tensor] = None
+        self.input_norm = None
+        self._model = None
+        self._fit_loaders = (None, None)
 
     # ------------------------------------------------------------------ properties
     @property
@@ -147,7 +154,7 @@ class Trainer:
                 bs = batch_size or self._cur_batch_size
                 acc[0] += float(v) * bs
                 acc[1] += bs
-        elif self._stage in ("val", "sanity"):
+        elif self._stage in ("val", "sanity", "test"):
             bs = batch_size or self._cur_batch_size
             acc = self._epoch_logs.setdefault(name, [0.0, 0, sync_dist, prog_bar])
             acc[0] += float(v) * bs
@@ -312,6 +319,7 @@ class Trainer:
     # ------------------------------------------------------------------ fit
     def fit(self, model, train_dataloaders=None, val_dataloaders=None, ckpt_path: Optional[str] = None):
         self._model = model
+        self._fit_loaders = (train_dataloaders, val_dataloaders)  # validate() without a loader takes the fit's
         self._graph_step_logs = None
         self.ctx = init_distributed(self.accelerator, self.strategy.backend, self.strategy.timeout_s)
         object.__setattr__(model, "_trainer", self)
@@ -398,6 +406,27 @@ class Trainer:
                 except Exception as e:  # noqa: BLE001
                     print(f"[dct] logger finalize failed: {e!r}", file=sys.stderr)
         return self
+
+    # ------------------------------------------------------------------ validate / test / predict
+    def validate(self, model=None, dataloaders=None, ckpt_path: Optional[str] = None) -> List[Dict[str, float]]:
+        """``[{"val_loss": .., "val_acc": ..}]`` over one dataloader (the fit's validation loader when none is
+        given); trainer/evaluate.py has the paths, the DDP semantics and ``ckpt_path``."""
+        from .evaluate import run_eval
+
+        return run_eval(self, "val", model, dataloaders, ckpt_path)
+
+    def test(self, model=None, dataloaders=None, ckpt_path: Optional[str] = None) -> List[Dict[str, float]]:
+        """``[{"test_loss": .., "test_acc": ..}]`` over one dataloader (``test_step``)."""
+        from .evaluate import run_eval
+
+        return run_eval(self, "test", model, dataloaders, ckpt_path)
+
+    def predict(self, model=None, dataloaders=None, ckpt_path: Optional[str] = None,
+                return_predictions: bool = True):
+        """The list of per-batch ``predict_step`` outputs in loader order (each rank its own shard)."""
+        from .evaluate import run_predict
+
+        return run_predict(self, model, dataloaders, ckpt_path, return_predictions)
 
     def teardown(self):
         if self.ctx is not None:
