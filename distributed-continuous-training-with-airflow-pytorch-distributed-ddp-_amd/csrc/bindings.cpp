@@ -937,9 +937,10 @@ PYBIND11_MODULE(_dct_native, m) {
   m.def("mlp_tile_ws_floats", [](const std::vector<int>& dims, int B) {
     return (int64_t)dct_mlp_tile_ws_floats(dims.data(), (int)dims.size() - 1, B);
   });
-  // batch-tiled inference (mlp_infer.hip): the shape check and workspace size need no device
+  // batch-tiled inference (mlp_infer.hip): the batch-tiled trainer's shape check (mlp_tile_fwd.h make_plan) under
+  // its own name; it and the workspace size need no device
   m.def("mlp_infer_supported", [](const std::vector<int>& dims) {
-    return dims.size() >= 2 && dct_mlp_infer_ws_bytes(dims.data(), (int)dims.size() - 1, 1) != 0;
+    return dims.size() >= 2 && dct_mlp_tile_supported(dims.data(), (int)dims.size() - 1) != 0;
   }, py::arg("dims"));
   m.def("mlp_infer_ws_bytes", [](const std::vector<int>& dims, int64_t n) {
     return dims.size() >= 2 ? (int64_t)dct_mlp_infer_ws_bytes(dims.data(), (int)dims.size() - 1, n) : (int64_t)0;

@@ -191,7 +191,8 @@ size_t dct_mlp_xg_slab_granules(const int* dims, int L);
 int dct_mlp_tile_supported(const int* dims, int L);
 long long dct_mlp_tile_ws_floats(const int* dims, int L, int B);
 int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream);
-// batch-tiled forward-only inference for the shapes dct_mlp_tile_supported takes (mlp_infer.hip); grid <= 0: default
+// batch-tiled forward-only inference (mlp_infer.hip); grid <= 0: default.  It and dct_mlp_tile_train share one
+// forward and one host check (mlp_tile_fwd.h): the shapes of dct_mlp_tile_supported, p on a 16-byte boundary
 int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, void* stream);
 long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n);
 }

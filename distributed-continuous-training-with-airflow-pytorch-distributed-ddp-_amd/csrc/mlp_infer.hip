@@ -1,11 +1,12 @@
-// mlp_infer: batch-tiled forward-only fp32 inference for the weather MLPs - the forward half of
-// mlp_tile.hip's step kernel, without dropout, with per-row outputs and order-independent statistics.
+// mlp_infer: batch-tiled forward-only fp32 inference for the weather MLPs - the tile forward of mlp_tile_fwd.h
+// (the one mlp_tile.hip's step kernel trains through: same shape rule, staging, layers and head), without dropout,
+// with per-row outputs and order-independent statistics.  Here: the once-per-workgroup staging, the normalising
+// gather, the tile walk, the outputs, the loss and the statistics.
 //
 //   infer kernel (grid G): every workgroup stages W0, the head weights and the biases in LDS ONCE and keeps
 //     its W1 fragments of the MFMA in registers, then walks tiles of R = 32 rows: gather rows X[idx[..]]
 //     (optionally (x - mean) / std, the scoring script's "raw" contract) -> layer 0 on the VALU (D0 <= 32) ->
-//     hidden x hidden forward on v_mfma_f32_16x16x4_f32 (exact fp32; two M = 16 row blocks per column block,
-//     k permuted identically on both operands, as in mlp_tile_step_kernel) -> head (C <= 4) on the VALU ->
+//     hidden x hidden forward on v_mfma_f32_16x16x4_f32 (exact fp32) -> head (C <= 4) on the VALU ->
 //     logits / softmax probabilities / argmax, each written only when its pointer is given.
 //   statistics (labels given): loss sum (CE or MSE), correct count, C x C confusion matrix (rows = label,
 //     columns = prediction).  The T = ceil(n / 32) tiles are cut into at most 4096 slots of S = ceil(T / 4096)
@@ -17,57 +18,23 @@
 //     order, so the fp64 loss sum is bit-identical from run to run and from grid to grid.
 //   The kernel boundary is the only synchronisation: no atomics, no workgroup waits on another one.
 //
-// Shapes: those of dct_mlp_tile_supported - 2 or 3 linear layers, D0 1..32, hidden widths multiples of 16 in
-// 16..128, C 2..4.  LDS: 57.5 KB for the 3-layer nets, 40.6 KB for the 2-layer ones.  Rows >= n of the last tile
-// are gathered as zeros and write nothing.
+// Shapes: those of dct_mlp_tile_supported (tile::make_plan), parameters on a 16-byte boundary.  LDS: 57.5 KB for
+// the 3-layer nets, 40.6 KB for the 2-layer ones.  Rows >= n of the last tile are gathered as zeros and write nothing.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "mlp_fused.h"
+#include "mlp_tile_fwd.h"
 
 namespace dct {
 namespace infer {
 
-constexpr int R = 32;     // rows per tile
-constexpr int NT = 256;   // 4 waves
-constexpr int LDH = 132;  // LDS row stride of the hidden activations (128 + 4)
-constexpr int LDX = 33;   // LDS row stride of the input tile and of W0
+using namespace tile;  // R, NT, LDH, LDX, Plan and the forward pieces
+
 constexpr int MAX_SLOTS = 4096;
 constexpr int SLOT_WORDS = 18;  // 8-byte words per slot: loss (fp64), correct, 16 confusion cells
 constexpr int FOLD_NT = 64;
 constexpr int MAX_GRID = 65536;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct Plan {
-  int L;        // 2 or 3 linear layers
-  int D0, H1, H2, C;  // H2 = 0 when L == 2
-  int K;        // width feeding the head (H2, or H1 when L == 2)
-  int woff[3], boff[3];  // torch flat offsets (layer 2 unused when L == 2; the head is layer L - 1)
-};
-
-static bool make_plan(Plan* tp, const int* dims, int L) {
-  if (L != 2 && L != 3) return false;
-  const int D0 = dims[0], C = dims[L];
-  if (D0 < 1 || D0 > 32 || C < 2 || C > 4) return false;
-  for (int l = 1; l < L; ++l)
-    if (dims[l] < 16 || dims[l] > 128 || dims[l] % 16 != 0) return false;
-  *tp = Plan{};
-  tp->L = L;
-  tp->D0 = D0;
-  tp->H1 = dims[1];
-  tp->H2 = (L == 3) ? dims[2] : 0;
-  tp->C = C;
-  tp->K = dims[L - 1];
-  int flat = 0;
-  for (int l = 0; l < L; ++l) {
-    tp->woff[l] = flat;
-    flat += dims[l] * dims[l + 1];
-    tp->boff[l] = flat;
-    flat += dims[l + 1];
-  }
-  return true;
-}
 
 // tiles, tiles per slot and slots of n rows
 struct Slots {
@@ -101,10 +68,6 @@ __host__ __device__ inline Lds lds_layout(int L) {
   return o;
 }
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ float pick4(const float (&v)[4], int i) {
   return i == 0 ? v[0] : (i == 1 ? v[1] : (i == 2 ? v[2] : v[3]));
 }
@@ -136,24 +99,12 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
   float4 wf[2][8];
   float b1v[2] = {0.f, 0.f};
   if (L == 3) {
+    load_w1_frags(wf, a.p + tp.woff[1], H1, H2, wave, j, q);
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int cb = wave + 4 * c;
-      const float* wrow = a.p + tp.woff[1] + (size_t)(cb * 16 + j) * H1 + 4 * q;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        wf[c][i] = (cb * 16 < H2 && i * 16 < H1) ? *reinterpret_cast<const float4*>(wrow + i * 16)
-                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
-      if (cb * 16 < H2) b1v[c] = a.p[tp.boff[1] + cb * 16 + j];
-    }
+    for (int c = 0; c < 2; ++c)
+      if ((wave + 4 * c) * 16 < H2) b1v[c] = a.p[tp.boff[1] + (wave + 4 * c) * 16 + j];
   }
-  for (int e = tid; e < H1 * D0; e += NT) {
-    const int o = e / D0, k = e - o * D0;
-    W0s[o * LDX + k] = a.p[tp.woff[0] + e];
-  }
-  for (int e = tid; e < C * K; e += NT) Wl[e] = a.p[tp.woff[L - 1] + e];
-  if (tid < C) Wl[4 * 128 + tid] = a.p[tp.boff[L - 1] + tid];
-  if (tid < H1) W0s[tid * LDX + 32] = a.p[tp.boff[0] + tid];
+  stage_weights(W0s, Wl, a.p, tp, L, tid);
   if (tid < D0) {
     nm[tid] = norm ? a.norm_mean[tid] : 0.f;
     ns[tid] = norm ? a.norm_std[tid] : 1.f;
@@ -188,77 +139,31 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
       }
       __syncthreads();
 
-      // ---- layer 0 (VALU): A1 = relu(X0 W0^T + b0)
-      for (int e = tid; e < R * H1; e += NT) {
-        const int r = e / H1, o = e - r * H1;
-        float z = W0s[o * LDX + 32];  // b0, staged in the pad column
-        for (int k = 0; k < D0; ++k) z = fmaf(W0s[o * LDX + k], X0[r * LDX + k], z);
-        A1[r * LDH + o] = fmaxf(z, 0.f);
-      }
+      // ---- layer 0: A1 = relu(X0 W0^T + b0)
+      layer0(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
       __syncthreads();
 
-      // ---- layer 1 (MFMA): A2 = relu(A1 W1^T + b1); a wave owns column blocks wave, wave + 4
+      // ---- layer 1: A2 = relu(A1 W1^T + b1); a wave owns column blocks wave, wave + 4
       if (L == 3) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int cb = wave + 4 * c;
           if (cb * 16 >= H2) break;
-          f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-          const float* ar0 = A1 + j * LDH + 4 * q;
-          const float* ar1 = ar0 + 16 * LDH;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            if (i * 16 >= H1) break;
-            // k of MFMA t, lane group q: 16 i + 4 q + t (the same permutation on both operands)
-            const float4 wv = wf[c][i];
-            const float4 a0 = *reinterpret_cast<const float4*>(ar0 + i * 16);
-            const float4 a1 = *reinterpret_cast<const float4*>(ar1 + i * 16);
-            acc0 = mfma4(a0.x, wv.x, acc0);
-            acc1 = mfma4(a1.x, wv.x, acc1);
-            acc0 = mfma4(a0.y, wv.y, acc0);
-            acc1 = mfma4(a1.y, wv.y, acc1);
-            acc0 = mfma4(a0.z, wv.z, acc0);
-            acc1 = mfma4(a1.z, wv.z, acc1);
-            acc0 = mfma4(a0.w, wv.w, acc0);
-            acc1 = mfma4(a1.w, wv.w, acc1);
-          }
-          const int o = cb * 16 + j;
-          const float bv = b1v[c];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int r0 = 4 * q + i, r1 = r0 + 16;
-            A2[r0 * LDH + o] = fmaxf(acc0[i] + bv, 0.f);
-            A2[r1 * LDH + o] = fmaxf(acc1[i] + bv, 0.f);
-          }
+          layer1_block(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
         }
         __syncthreads();
       }
 
-      // ---- head (VALU, 8 lanes per row; after the xor tree all 8 hold the row's logits) + outputs + row loss
+      // ---- head (all 8 lanes of a row hold its logits) + outputs + row loss
       {
-        const float* Ah = (L == 3) ? A2 : A1;
         const int r = tid >> 3, part = tid & 7;
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int k = part; k < K; k += 8) {
-          const float av = Ah[r * LDH + k];
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            if (c < C) acc[c] = fmaf(Wl[c * K + k], av, acc[c]);
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          acc[c] += __shfl_xor(acc[c], 1);
-          acc[c] += __shfl_xor(acc[c], 2);
-          acc[c] += __shfl_xor(acc[c], 4);
-        }
         float z[4], ex[4];
+        head_logits(z, (L == 3) ? A2 : A1, Wl, C, K, tid);
         float mx = -3.402823466e+38f;
         int am = 0;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          z[c] = (c < C) ? acc[c] + Wl[4 * 128 + c] : 0.f;
+        for (int c = 0; c < 4; ++c)
           if (c < C && z[c] > mx) { mx = z[c]; am = c; }
-        }
         float se = 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -367,16 +272,15 @@ extern "C" {
 
 // bytes of the slot workspace of a launch over n rows with labels: at most 4096 slots, whatever n is
 long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n) {
-  dct::infer::Plan tp;
-  if (!dct::infer::make_plan(&tp, dims, L) || n < 1) return 0;
+  dct::tile::Plan tp;
+  if (!dct::tile::make_plan(&tp, dims, L) || n < 1) return 0;
   return (long long)dct::infer::slots_of(n).nslots * dct::infer::SLOT_WORDS * 8;
 }
 
 int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, void* stream) {
-  dct::infer::Plan tp;
-  if (!dct::infer::make_plan(&tp, dims, L)) return (int)hipErrorInvalidValue;
-  if (a->n < 1 || !a->p || !a->X || a->ldx < tp.D0) return (int)hipErrorInvalidValue;
-  if (reinterpret_cast<uintptr_t>(a->p) % 16 != 0) return (int)hipErrorInvalidValue;  // W1 is read as float4
+  dct::tile::Plan tp;
+  if (!dct::tile::plan_launch(&tp, dims, L, a->p)) return (int)hipErrorInvalidValue;
+  if (a->n < 1 || !a->X || a->ldx < tp.D0) return (int)hipErrorInvalidValue;
   if ((a->norm_mean == nullptr) != (a->norm_std == nullptr)) return (int)hipErrorInvalidValue;
   if (a->loss_kind != 0 && a->loss_kind != 1) return (int)hipErrorInvalidValue;
   if (grid > dct::infer::MAX_GRID) return (int)hipErrorInvalidValue;

@@ -18,9 +18,12 @@
 //     counters are advanced by the fold's last-arriving workgroup (an arrival counter that it
 //     leaves at zero, so a captured launch pair replays).
 //
-// Weights are read straight from the flat parameter buffer (L2 resident, <= 85 KB); activations
-// and dZ of the tile live in LDS with the two narrow layers' weights (91.5 KB for the 3-layer nets, 57.7 KB for the 2-layer ones).  No LDS-DMA loads.
-// Shapes: 2 or 3 linear layers, D0 1..32, hidden widths multiples of 16 in 16..128, C 2..4.
+// Weights are read straight from the flat parameter buffer (L2 resident, <= 85 KB, on a 16-byte boundary: W1
+// is read as float4); activations and dZ of the tile live in LDS with the two narrow layers' weights (91.5 KB
+// for the 3-layer nets, 57.7 KB for the 2-layer ones).  No LDS-DMA loads.
+// The forward pieces (W1 fragment load, weight staging, layers 0 and 1, head logits), the shape rule (make_plan)
+// and the launch check are mlp_tile_fwd.h's, shared with the inference kernel (mlp_infer.hip); the gather, the
+// loss, the whole backward, the slots and the fold are here.
 // Dropout key: mix_hash(seed + (b >> 6) * 0x9E3779B9, gstep, (LI * 64 + (b & 63)) * 65536 + o),
 // b = row within the batch: rows < 64 draw the LDS kernel's mask (ops/fused_mlp.py
 // dropout_keep_mask is the host mirror).
@@ -29,51 +32,13 @@
 
 #include "mlp_fused_impl.h"
 #include "mlp_select.h"
+#include "mlp_tile_fwd.h"
 
 namespace dct {
 namespace tile {
 
-constexpr int R = 32;     // rows per workgroup
-constexpr int NT = 256;   // 4 waves
-constexpr int LDH = 132;  // LDS row stride of the hidden activations / dZ (128 + 4)
-constexpr int LDX = 33;   // LDS row stride of the input tile and of W0
 constexpr int BMAX = 1024;
 constexpr int FOLD_NT = 256;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct Plan {
-  int L;        // 2 or 3 linear layers
-  int D0, H1, H2, C;  // H2 = 0 when L == 2
-  int K;        // width feeding the head (H2, or H1 when L == 2)
-  int woff[3], boff[3];  // torch flat offsets (layer 2 unused when L == 2; the head is layer L - 1)
-  int P, Pp;    // parameters, slot stride (floats)
-};
-
-static bool make_plan(Plan* tp, const int* dims, int L) {
-  if (L != 2 && L != 3) return false;
-  const int D0 = dims[0], C = dims[L];
-  if (D0 < 1 || D0 > 32 || C < 2 || C > 4) return false;
-  for (int l = 1; l < L; ++l)
-    if (dims[l] < 16 || dims[l] > 128 || dims[l] % 16 != 0) return false;
-  *tp = Plan{};
-  tp->L = L;
-  tp->D0 = D0;
-  tp->H1 = dims[1];
-  tp->H2 = (L == 3) ? dims[2] : 0;
-  tp->C = C;
-  tp->K = dims[L - 1];
-  int flat = 0;
-  for (int l = 0; l < L; ++l) {
-    tp->woff[l] = flat;
-    flat += dims[l] * dims[l + 1];
-    tp->boff[l] = flat;
-    flat += dims[l + 1];
-  }
-  tp->P = flat;
-  tp->Pp = (flat + 1 + 3) & ~3;
-  return true;
-}
 
 // LDS carve (floats)
 struct Lds {
@@ -101,10 +66,6 @@ __device__ __forceinline__ float drop_apply(float z, uint32_t seed, uint32_t gst
   const uint32_t h = mix_hash(seed + (uint32_t)(b >> 6) * 0x9E3779B9u, gstep,
                               (uint32_t)((LI * 64 + (b & 63)) * 65536 + o));
   return (u01(h) < p) ? 0.f : z * scale;
-}
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
 template <int L>
@@ -139,22 +100,17 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
   int* lab = reinterpret_cast<int*>(lds + lo.lab);
   float* slot = a.tile_ws + (size_t)blockIdx.x * tp.Pp;
 
-  // ---- this wave's W1 fragments of the forward MFMA (column blocks wave, wave + 4): issued first, so
-  // their L2 round trips overlap the gather and layer 0 instead of chaining inside the k loop
-  float4 wf[2][8];
-  if (L == 3) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int cb = wave + 4 * c;
-      const float* wrow = a.p + tp.woff[1] + (size_t)(cb * 16 + j) * H1 + 4 * q;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        wf[c][i] = (cb * 16 < H2 && i * 16 < H1) ? *reinterpret_cast<const float4*>(wrow + i * 16)
-                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
+  // the epilogue of the hidden layers: dropout keyed by the row within the batch
+  const auto drop = [&](int LI, int r, int o, float z) {
+    return dropping ? drop_apply(z, a.seed, gstep, LI, row0 + r, o, a.dropout, dscale) : z;
+  };
 
-  // ---- gather the tile's rows and labels; stage W0
+  // ---- this wave's W1 fragments of the forward MFMA: issued first, so their L2 round trips overlap the
+  // gather and layer 0 instead of chaining inside the k loop
+  float4 wf[2][8];
+  if (L == 3) load_w1_frags(wf, a.p + tp.woff[1], H1, H2, wave, j, q);
+
+  // ---- gather the tile's rows and labels; stage W0 and the head
   for (int e = tid; e < R * D0; e += NT) {
     const int r = e / D0, k = e - r * D0;
     const int gb = row0 + r;
@@ -166,64 +122,20 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
     const int gb = row0 + tid;
     lab[tid] = (gb < bs) ? a.Y[a.idx[(size_t)cur * B + gb]] : 0;
   }
-  for (int e = tid; e < H1 * D0; e += NT) {
-    const int o = e / D0, k = e - o * D0;
-    W0s[o * LDX + k] = a.p[tp.woff[0] + e];
-  }
-  for (int e = tid; e < C * K; e += NT) Wl[e] = a.p[tp.woff[L - 1] + e];
-  if (tid < C) Wl[4 * 128 + tid] = a.p[tp.boff[L - 1] + tid];
-  if (tid < H1) W0s[tid * LDX + 32] = a.p[tp.boff[0] + tid];
+  stage_weights(W0s, Wl, a.p, tp, L, tid);
   __syncthreads();
 
-  // ---- layer 0 (VALU): A1 = dropout(relu(X0 W0^T + b0))
-  for (int e = tid; e < R * H1; e += NT) {
-    const int r = e / H1, o = e - r * H1;
-    float z = W0s[o * LDX + 32];  // b0, staged in the pad column
-    for (int k = 0; k < D0; ++k) z = fmaf(W0s[o * LDX + k], X0[r * LDX + k], z);
-    z = fmaxf(z, 0.f);
-    if (dropping) z = drop_apply(z, a.seed, gstep, 0, row0 + r, o, a.dropout, dscale);
-    A1[r * LDH + o] = z;
-  }
+  // ---- layer 0: A1 = dropout(relu(X0 W0^T + b0))
+  layer0(A1, W0s, X0, D0, H1, tid, drop);
   __syncthreads();
 
-  // ---- layer 1 (MFMA): A2 = dropout(relu(A1 W1^T + b1)); a wave owns column blocks wave, wave + 4
+  // ---- layer 1: A2 = dropout(relu(A1 W1^T + b1)); a wave owns column blocks wave, wave + 4
   if (L == 3) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const int cb = wave + 4 * c;
       if (cb * 16 >= H2) break;
-      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-      const float* ar0 = A1 + j * LDH + 4 * q;
-      const float* ar1 = ar0 + 16 * LDH;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        if (i * 16 >= H1) break;
-        // k of MFMA t, lane group q: 16 i + 4 q + t (the same permutation on both operands)
-        const float4 wv = wf[c][i];
-        const float4 a0 = *reinterpret_cast<const float4*>(ar0 + i * 16);
-        const float4 a1 = *reinterpret_cast<const float4*>(ar1 + i * 16);
-        acc0 = mfma4(a0.x, wv.x, acc0);
-        acc1 = mfma4(a1.x, wv.x, acc1);
-        acc0 = mfma4(a0.y, wv.y, acc0);
-        acc1 = mfma4(a1.y, wv.y, acc1);
-        acc0 = mfma4(a0.z, wv.z, acc0);
-        acc1 = mfma4(a1.z, wv.z, acc1);
-        acc0 = mfma4(a0.w, wv.w, acc0);
-        acc1 = mfma4(a1.w, wv.w, acc1);
-      }
-      const int o = cb * 16 + j;
-      const float bv = a.p[tp.boff[1] + o];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r0 = 4 * q + i, r1 = r0 + 16;
-        float z0 = fmaxf(acc0[i] + bv, 0.f), z1 = fmaxf(acc1[i] + bv, 0.f);
-        if (dropping) {
-          z0 = drop_apply(z0, a.seed, gstep, 1, row0 + r0, o, a.dropout, dscale);
-          z1 = drop_apply(z1, a.seed, gstep, 1, row0 + r1, o, a.dropout, dscale);
-        }
-        A2[r0 * LDH + o] = z0;
-        A2[r1 * LDH + o] = z1;
-      }
+      layer1_block(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, drop);
     }
     __syncthreads();
   }
@@ -247,24 +159,10 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
   const float* Ah = (L == 3) ? A2 : A1;
   float* dZh = (L == 3) ? dZ2 : dZ1;
   {
-    const int r = tid >> 3, part = tid & 7;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = part; k < K; k += 8) {
-      const float av = Ah[r * LDH + k];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < C) acc[c] = fmaf(Wl[c * K + k], av, acc[c]);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      acc[c] += __shfl_xor(acc[c], 1);
-      acc[c] += __shfl_xor(acc[c], 2);
-      acc[c] += __shfl_xor(acc[c], 4);
-    }
-    if (part == 0) {
-      float z[4], dz[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) z[c] = (c < C) ? acc[c] + Wl[4 * 128 + c] : 0.f;
+    const int r = tid >> 3;
+    float z[4], dz[4] = {0.f, 0.f, 0.f, 0.f};
+    head_logits(z, Ah, Wl, C, K, tid);
+    if ((tid & 7) == 0) {
       const bool live = (row0 + r) < bs;
       const float inv = 1.0f / (float)(bs > 0 ? bs : 1);
       const LossAcc rl = row_loss4(z, C, lab[r], a.loss_kind, live ? inv : 0.f, dz);
@@ -469,7 +367,7 @@ long long dct_mlp_tile_ws_floats(const int* dims, int L, int B) {
 
 int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream) {
   dct::tile::Plan tp;
-  if (!dct::tile::make_plan(&tp, dims, L)) return (int)hipErrorInvalidValue;
+  if (!dct::tile::plan_launch(&tp, dims, L, a->p)) return (int)hipErrorInvalidValue;
   if (a->B < 1 || a->B > dct::tile::BMAX || a->steps < 1 || a->n_items < 1) return (int)hipErrorInvalidValue;
   if (a->mode == 1 && a->steps != 1) return (int)hipErrorInvalidValue;
   if (!a->cursor && (long long)(a->steps - 1) * a->B >= a->n_items) return (int)hipErrorInvalidValue;

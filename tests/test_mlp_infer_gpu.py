@@ -143,6 +143,37 @@ def test_statistics_over_many_slots_per_workgroup_and_tiles_per_slot(cuda):
     assert correct == int((pred == y).sum()) and torch.equal(conf, ic.confusion(y, pred, 2).cpu())
 
 
+@pytest.mark.parametrize("dims", [[5, 128, 128, 2], [5, 64, 2]])
+def test_launcher_refuses_a_parameter_pointer_off_the_16_byte_boundary(dims, cuda):
+    """The host check the launcher shares with the batch-tiled trainer (csrc/mlp_tile_fwd.h): W1 is read as float4.
+    One float into an aligned allocation is refused with nothing written; the aligned view goes through."""
+    nat, n, C, P = native(), 33, dims[-1], ic.num_params(dims)
+    g = torch.Generator().manual_seed(7)
+    buf = torch.zeros(P + 1, device=cuda)
+    assert buf.data_ptr() % 16 == 0
+    X = torch.randn(n, dims[0], generator=g).to(cuda)
+    Y = torch.randint(0, C, (n,), generator=g, dtype=torch.int32).to(cuda)
+    ws = torch.full((nat.mlp_infer_ws_bytes(dims, n) // 8,), -1, dtype=torch.int64, device=cuda)
+    stats = torch.full((2 + C * C,), -1, dtype=torch.int64, device=cuda)
+    logits, probs = torch.full((n, C), POISON, device=cuda), torch.full((n, C), POISON, device=cuda)
+    pred = torch.full((n,), -7, dtype=torch.int32, device=cuda)
+
+    def run(p):
+        p.copy_((torch.rand(P, generator=g) * 2 - 1) * 0.5)
+        nat.mlp_infer(dims, ptr(p), ptr(X), X.stride(0), 0, ptr(Y), n, 0, 0, 0, ptr(logits), ptr(probs), ptr(pred),
+                      ptr(ws), ws.numel() * 8, ptr(stats), 0, stream_handle())
+        torch.cuda.synchronize()
+
+    with pytest.raises(RuntimeError, match="invalid"):
+        run(buf[1:P + 1])
+    torch.cuda.synchronize()
+    assert bool((logits == POISON).all()) and bool((probs == POISON).all()) and bool((pred == -7).all())
+    assert bool((ws == -1).all()) and bool((stats == -1).all())
+    run(buf[:P])
+    assert bool(torch.isfinite(logits).all()) and bool((logits != POISON).all())
+    assert torch.equal(pred.long(), logits.argmax(1)) and int(stats[2:].sum()) == n
+
+
 def test_launcher_refuses_an_unsupported_shape_and_a_short_workspace(cuda):
     nat = native()
     p = torch.zeros(4096, device=cuda)

@@ -15,7 +15,7 @@ import dct_amd  # noqa: F401
 from dct_amd.data.dataset import TensorPairDataset
 from dct_amd.data.synthetic import weather_tensors
 from dct_amd.models.mlp import MLPClassifier, WeatherClassifier
-from dct_amd.ops._native import native
+from dct_amd.ops._native import native, ptr, stream_handle
 from dct_amd.ops.fused_mlp import FusedMLPKernel, dropout_keep_mask, mlp_num_params
 from dct_amd.trainer import Trainer, seed_everything
 
@@ -272,6 +272,40 @@ def test_tile_dropout_above_row_63_matches_host_mask(cuda):
         return lins[-1](h)
 
     _check_against_torch(p, m, v, losses, net, *_torch_adam(net, X, Y, idx, B, 7, "ce", forward=forward))
+
+
+@pytest.mark.parametrize("dims", [[5, 128, 128, 2], [5, 64, 2]])
+def test_tile_train_refuses_a_parameter_pointer_off_the_16_byte_boundary(dims, cuda):
+    """W1 is read as float4 at p + woff[1]: a contiguous view one float into an aligned allocation passes the Python
+    checks, and both tiled launchers (one host check, csrc/mlp_tile_fwd.h) refuse it before any launch - nothing is
+    written.  The aligned view of the same allocation goes through."""
+    B, poison = 33, 12345.0
+    X, Y, idx, net, dev = _problem(dims, B, 9, cuda)
+    P = mlp_num_params(dims)
+    k = FusedMLPKernel(dims, bmax=1024)
+    assert k.plan.trainer(B) == "tile"
+    buf = torch.zeros(P + 1, device=cuda)
+    assert buf.data_ptr() % 16 == 0
+    m, v = torch.full((P,), poison, device=cuda), torch.full((P,), poison, device=cuda)
+    losses = torch.full((1,), poison, device=cuda)
+    logits = torch.full((B, dims[-1]), poison, device=cuda)
+    p = buf[1:P + 1]
+    p.copy_(_flat(net))
+    with pytest.raises(RuntimeError, match="invalid"):
+        _tile_train(k, p, m, v, dev, B, B, ((0, 1),), losses)
+    with pytest.raises(RuntimeError, match="invalid"):
+        native().mlp_infer(dims, ptr(p), ptr(dev[0]), dev[0].stride(0), 0, 0, B, 0, 0, 0, ptr(logits), 0, 0, 0, 0, 0, 0,
+                           stream_handle())
+    torch.cuda.synchronize()
+    assert torch.equal(p.cpu(), _flat(net))
+    for t in (m, v, losses, logits):
+        assert bool((t == poison).all())
+    p = buf[:P]
+    p.copy_(_flat(net))
+    m.zero_(), v.zero_()
+    _tile_train(k, p, m, v, dev, B, B, ((0, 1),), losses)
+    assert math.isfinite(losses.item()) and losses.item() != poison
+    assert bool(torch.isfinite(p).all()) and not torch.equal(p.cpu(), _flat(net))
 
 
 def _loaders(n=2000, bs=64):
