@@ -48,6 +48,10 @@ class ModelConfig:
     num_classes: int = 2  # :61
     dropout: float = 0.2  # :60
     loss: str = "ce"  # ce (reference :69) | mse (BASELINE.json north star)
+    # cross-entropy only (torch's CrossEntropyLoss(weight=, label_smoothing=)): None, "balanced"
+    # (n / (C * count_c) over the training split) or one strictly positive weight per class; smoothing in [0, 1)
+    class_weight: Any = None
+    label_smoothing: float = 0.0
     # TabTransformer-only knobs
     d_model: int = 64
     n_heads: int = 4
@@ -201,6 +205,36 @@ class PipelineConfig:
             else:
                 d = yaml.safe_load(f)
         return cls.from_dict(d)
+
+
+def parse_class_weight(text) -> Any:
+    """``--class-weight`` / ``model.class_weight``: None or "" -> None, "balanced" -> "balanced", "w0,w1,..." (or a
+    sequence of numbers) -> a list of floats.  The model validates the numbers (models/mlp.py)."""
+    if text is None or isinstance(text, str) and text.strip() == "":
+        return None
+    if isinstance(text, str):
+        if text.strip().lower() == "balanced":
+            return "balanced"
+        try:
+            return [float(t) for t in text.split(",")]
+        except ValueError:
+            raise ValueError(f"class weights must be 'balanced' or comma-separated numbers, got {text!r}") from None
+    return [float(t) for t in text]
+
+
+def balanced_class_weight(labels, num_classes: int) -> List[float]:
+    """sklearn's "balanced" heuristic, ``n / (C * count_c)``, over a label vector (the training split's: the same
+    numbers on every rank).  A class without a single row has no finite weight: ValueError."""
+    import torch
+
+    y = torch.as_tensor(labels).reshape(-1).to(torch.int64)
+    if y.numel() == 0 or int(y.min()) < 0 or int(y.max()) >= int(num_classes):
+        raise ValueError(f"balanced class weights need labels in 0..{int(num_classes) - 1}")
+    counts = torch.bincount(y, minlength=int(num_classes))
+    missing = [c for c in range(int(num_classes)) if int(counts[c]) == 0]
+    if missing:
+        raise ValueError(f"balanced class weights: no training row of class(es) {missing}")
+    return [y.numel() / (int(num_classes) * int(c)) for c in counts.tolist()]
 
 
 def default_config(env: Optional[Dict[str, str]] = None) -> PipelineConfig:

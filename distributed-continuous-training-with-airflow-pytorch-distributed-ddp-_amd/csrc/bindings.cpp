@@ -73,7 +73,7 @@ struct MlpPlan {
 // The key of a described launch (MlpPlan.trainer): what mlp_launch_key would derive from its arguments,
 // with every buffer the description implies bound.
 static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, int rank, int loss_kind, bool prof,
-                                   bool cursor, bool stage, bool pending, bool aligned) {
+                                   bool cursor, bool stage, bool pending, bool aligned, bool weighted) {
   dct::MlpLaunchKey k{};
   k.B = batch; k.mode = mode; k.steps = steps; k.loss_kind = loss_kind;
   k.xg_world = world; k.xg_rank = rank;
@@ -82,6 +82,7 @@ static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, in
   k.moments = mode == 0 || pending;
   k.xg_bufs = world > 1;
   k.p_aligned = k.mv_aligned = aligned;
+  k.weighted = weighted;
   return k;
 }
 
@@ -92,7 +93,8 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
                                     uint32_t seed, uint32_t step_base, uintptr_t loss_out, int mode, int loss_kind,
                                     uintptr_t step_counter, uintptr_t cursor, uintptr_t prof, uintptr_t pending,
                                     uintptr_t stage, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
-                                    uintptr_t xg_status, int64_t xg_timeout, int xg_poll) {
+                                    uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t class_w = 0,
+                                    float label_smooth = 0.f) {
   if (!plan.supported) throw std::runtime_error("MLP too large for the fused kernel");
   if (steps < 1 || n_items < 1 || B < 1) throw std::invalid_argument("empty launch");
   if (!cursor && (int64_t)(steps - 1) * B >= n_items) throw std::invalid_argument("more steps than batches");
@@ -135,6 +137,11 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
   a.xg_status = P<unsigned int>(xg_status);
   a.xg_timeout = xg_timeout;
   a.xg_poll = xg_poll;
+  if (!(label_smooth >= 0.f && label_smooth < 1.f)) throw std::invalid_argument("label_smoothing outside [0, 1)");
+  if ((class_w || label_smooth != 0.f) && loss_kind != 0)
+    throw std::invalid_argument("class weights / label smoothing: cross-entropy only");
+  a.class_w = P<const float>(class_w);
+  a.label_smooth = label_smooth;
   // a request no trainer of this plan serves is an invalid argument; a chosen trainer's own refusal of
   // the arguments surfaces in launch_train
   const dct::MlpChoice c = plan.select(dct::mlp_launch_key(a));
@@ -271,21 +278,24 @@ PYBIND11_MODULE(_dct_native, m) {
       })
       .def_property_readonly("mlp_block", [](const MlpPlan& p) { return p.sh()->mlp_block; })
       // the trainer a launch of this description reaches: "wave_single", "wave_rows", "block5", "block5_b8",
-      // "block3", "lds", "tile" or "none".  `aligned`: the flat buffers lie on 16-byte boundaries.  No device needed.
+      // "block3", "lds", "tile" or "none".  `aligned`: the flat buffers lie on 16-byte boundaries; `weighted`: class
+      // weights or label smoothing are on (the batch-tiled trainer's plan only).  No device needed.
 #define MLP_QUERY_ARGS                                                                                              \
   py::arg("batch"), py::arg("mode") = 0, py::arg("steps") = 1, py::arg("world") = 1, py::arg("rank") = 0,           \
       py::arg("loss_kind") = 0, py::arg("prof") = false, py::arg("cursor") = false, py::arg("stage") = false,       \
-      py::arg("pending") = false, py::arg("aligned") = true
+      py::arg("pending") = false, py::arg("aligned") = true, py::arg("weighted") = false
       .def("trainer", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
-                         bool prof, bool cursor, bool stage, bool pending, bool aligned) {
+                         bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted) {
         return std::string(dct::mlp_trainer_name(
-            plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned))
+            plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
+                                  weighted))
                 .trainer));
       }, MLP_QUERY_ARGS)
       // whether that launch reads its staged-batch buffer (the wave kernels and mlp_block5's grad mode do)
       .def("uses_stage", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
-                            bool prof, bool cursor, bool stage, bool pending, bool aligned) {
-        return plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned))
+                            bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted) {
+        return plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
+                                     weighted))
             .use_stage;
       }, MLP_QUERY_ARGS)
 #undef MLP_QUERY_ARGS
@@ -297,12 +307,13 @@ PYBIND11_MODULE(_dct_native, m) {
              int loss_kind, uintptr_t step_counter, uintptr_t cursor, uintptr_t prof, uintptr_t pending,
              uintptr_t stage, uintptr_t stream, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
              uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t tile_ws, int64_t tile_ws_floats,
-             uintptr_t lr_tab) {
+             uintptr_t lr_tab, uintptr_t class_w, float label_smooth) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             dct::MlpArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
                                                    b1, b2, eps, wd, dropout, seed, step_base, loss_out, mode,
                                                    loss_kind, step_counter, cursor, prof, pending, stage, xg_recv,
-                                                   xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll);
+                                                   xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll,
+                                                   class_w, label_smooth);
             a.tile_ws = P<float>(tile_ws);
             a.tile_ws_floats = tile_ws_floats;
             a.lr_tab = P<const float>(lr_tab);
@@ -315,7 +326,8 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("cursor"), py::arg("prof") = 0, py::arg("pending") = 0, py::arg("stage") = 0,
           py::arg("stream") = 0, py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL, py::arg("xg_poll") = 0,
-          py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0, py::arg("lr_tab") = (uintptr_t)0)
+          py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0, py::arg("lr_tab") = (uintptr_t)0,
+          py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f)
       .def(
           "prepare_train",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t X, int ldx, uintptr_t Y,
@@ -323,12 +335,13 @@ PYBIND11_MODULE(_dct_native, m) {
              uint32_t seed, uintptr_t loss_out, int64_t loss_len, int loss_kind, uintptr_t step_counter,
              uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank, uintptr_t xg_status,
              int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks, uintptr_t tile_ws, int64_t tile_ws_floats,
-             uintptr_t lr_tab) {
+             uintptr_t lr_tab, uintptr_t class_w, float label_smooth) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             auto l = std::make_unique<MlpLaunch>(MlpLaunch{plan});
             l->base = make_train_args(plan, p, mo, vo, 0, X, ldx, Y, idx, n_items, B, 1, 0, lr, b1, b2, eps, wd,
                                       dropout, seed, 0, loss_out, 0, loss_kind, step_counter, 0, 0, 0, 0, xg_recv,
-                                      xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll);
+                                      xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll, class_w,
+                                      label_smooth);
             l->base.xg_ticks = P<unsigned long long>(xg_ticks);
             l->base.tile_ws = P<float>(tile_ws);
             l->base.tile_ws_floats = tile_ws_floats;
@@ -343,7 +356,7 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("step_counter"), py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL,
           py::arg("xg_poll") = 0, py::arg("xg_ticks") = 0, py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0,
-          py::arg("lr_tab") = (uintptr_t)0)
+          py::arg("lr_tab") = (uintptr_t)0, py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f)
       .def(
           "eval",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items,
@@ -948,7 +961,8 @@ PYBIND11_MODULE(_dct_native, m) {
   m.def("mlp_infer",
         [](const std::vector<int>& dims, uintptr_t p, uintptr_t X, int ldx, uintptr_t idx, uintptr_t Y, int64_t n,
            uintptr_t norm_mean, uintptr_t norm_std, int loss_kind, uintptr_t logits_out, uintptr_t probs_out,
-           uintptr_t pred_out, uintptr_t ws, int64_t ws_bytes, uintptr_t stats, int grid, uintptr_t stream) {
+           uintptr_t pred_out, uintptr_t ws, int64_t ws_bytes, uintptr_t stats, int grid, uintptr_t stream,
+           uintptr_t class_w, float label_smooth) {
           if (dims.size() < 2) throw std::invalid_argument("mlp_infer: dims");
           dct::MlpInferArgs a{};
           a.p = P<const float>(p);
@@ -966,12 +980,15 @@ PYBIND11_MODULE(_dct_native, m) {
           a.ws = P<void>(ws);
           a.ws_bytes = ws_bytes;
           a.stats = P<void>(stats);
+          a.class_w = P<const float>(class_w);
+          a.label_smooth = label_smooth;
           check(dct_mlp_infer(dims.data(), (int)dims.size() - 1, &a, grid, reinterpret_cast<void*>(stream)),
                 "mlp_infer");
         },
         py::arg("dims"), py::arg("p"), py::arg("X"), py::arg("ldx"), py::arg("idx"), py::arg("Y"), py::arg("n"),
         py::arg("norm_mean"), py::arg("norm_std"), py::arg("loss_kind"), py::arg("logits_out"), py::arg("probs_out"),
-        py::arg("pred_out"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stats"), py::arg("grid"), py::arg("stream"));
+        py::arg("pred_out"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stats"), py::arg("grid"), py::arg("stream"),
+        py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f);
   m.def("mlp_xg_slab_granules", [](const std::vector<int>& dims) {
     return (int64_t)dct_mlp_xg_slab_granules(dims.data(), (int)dims.size() - 1);
   });

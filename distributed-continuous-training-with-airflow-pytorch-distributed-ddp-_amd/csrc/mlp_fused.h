@@ -119,8 +119,8 @@ struct MlpArgs {
   float k_l2b1, k_l2b2;  // log2(b1), log2(b2) (Adam bias corrections as one exp2 each)
   float k_rc1, k_rc2;  // 1 / (1 - b1), 1 / (1 - b2) (scaled-moment Adam)
   float k_sqc2;        // sqrt(1 - b2)
-  // batch-tiled trainer (mlp_tile.hip): slot workspace [ceil(B / 32)][Pp] partial gradients + loss of a step,
-  // the fold kernel's arrival counter in its last four floats
+  // batch-tiled trainer (mlp_tile.hip): slot workspace [ceil(B / 32)][Pp] partial gradients + loss (and, weighted,
+  // the sum of w[y]) of a step, the fold kernel's arrival counter in its last four floats
   float* tile_ws;
   long long tile_ws_floats;
   // optional learning-rate table (lr_table.h; last, so every other field keeps its kernel-argument offset): train
@@ -128,6 +128,12 @@ struct MlpArgs {
   // of lr.  Grad-mode launches apply no Adam and ignore it, except the single-wave kernel's update-then-grad, whose
   // pending update is the step after *step_counter - 1.
   const float* lr_tab;
+  // optional class-weighted / label-smoothed cross-entropy (batch-tiled trainer only; appended, so every other field
+  // keeps its offset): class_w device [C] strictly positive weights (null: all 1), label_smooth in [0, 1).  With
+  // either set the loss is sum_i num_i / W, W = sum_i w[y_i] over the live rows (torch's weighted mean); both off:
+  // the plain CE / MSE with the 1 / bs normaliser.  mlp_select.h refuses such a launch on every other trainer.
+  const float* class_w;
+  float label_smooth;
 };
 
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
@@ -152,6 +158,11 @@ struct MlpInferArgs {
   void* ws;
   long long ws_bytes;
   void* stats;
+  // optional class-weighted / label-smoothed cross-entropy (loss_kind 0 only): class_w device [C] (null: all 1),
+  // label_smooth in [0, 1).  With either set statistic word 0 is sum_i num_i, the numerator of the weighted mean;
+  // its denominator W = sum_c w[c] * (row sum c of the confusion matrix) is the host's to compute.
+  const float* class_w;
+  float label_smooth;
 };
 
 // fills *sh for dims[0 .. L] and plans of up to bmax rows per step (mlp_block = -1: auto, until the plan stamps

@@ -121,6 +121,41 @@ __device__ __forceinline__ LossAcc row_loss4(const float (&z)[4], int C, int y, 
   return r;
 }
 
+// Class-weighted, label-smoothed CE of one row of logits z[0..C) (C <= 4) with label y, torch's
+// F.cross_entropy(weight=w, label_smoothing=eps) before its normaliser: the target mass
+// t[c] = (1 - eps) w[y] [c == y] + (eps / C) w[c], num = -sum_c t[c] log_softmax(z)[c] (returned) and
+// dz[c] = softmax(z)[c] sum_c t[c] - t[c]; *wy = w[y], the row's share of the normaliser W = sum_i w[y_i].
+// The caller divides by W.  Full-precision exp / log / division: 32 lanes of a tile come here once per step.
+__device__ __forceinline__ float row_loss4_weighted(const float (&z)[4], int C, int y, const float (&w)[4], float eps,
+                                                    float* dz, float* wy) {
+  float mx = -3.402823466e+38f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (c < C && z[c] > mx) mx = z[c];
+  float e[4], t[4], s = 0.f, wl = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    e[c] = (c < C) ? expf(z[c] - mx) : 0.f;
+    s += e[c];
+    if (c == y) wl = w[c];
+  }
+  const float lse = mx + logf(s);
+  const float on = (1.f - eps) * wl, sm = eps / (float)C;
+  float st = 0.f, num = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    t[c] = (c < C) ? fmaf(sm, w[c], (c == y) ? on : 0.f) : 0.f;
+    st += t[c];
+    if (c < C) num = fmaf(t[c], lse - z[c], num);
+  }
+  const float rs = st / s;
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (c < C) dz[c] = fmaf(e[c], rs, -t[c]);
+  *wy = wl;
+  return num;
+}
+
 // ----------------------------------------------------------------------------------------
 // forward of layer LI: Out[b][o] = act(sum_k W[o][k] A[b][k] + bias[o]).
 // items = (rows4/4 output groups) << ksl k-splits (KS adjacent lanes per group).

@@ -8,7 +8,9 @@
 //     (optionally (x - mean) / std, the scoring script's "raw" contract) -> layer 0 on the VALU (D0 <= 32) ->
 //     hidden x hidden forward on v_mfma_f32_16x16x4_f32 (exact fp32) -> head (C <= 4) on the VALU ->
 //     logits / softmax probabilities / argmax, each written only when its pointer is given.
-//   statistics (labels given): loss sum (CE or MSE), correct count, C x C confusion matrix (rows = label,
+//   statistics (labels given): loss sum (CE or MSE; with MlpInferArgs::class_w / label_smooth the sum of the
+//     weighted, smoothed CE numerators of row_loss4_weighted, whose normaliser W the host takes from the confusion
+//     matrix's row sums), correct count, C x C confusion matrix (rows = label,
 //     columns = prediction).  The T = ceil(n / 32) tiles are cut into at most 4096 slots of S = ceil(T / 4096)
 //     consecutive tiles.  A workgroup owns whole slots (slot s, s + G, ...), accumulates a slot's tiles in
 //     ascending order - the loss in fp64, the counts as 64-bit integers - and writes the slot with plain vector
@@ -23,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mlp_fused.h"
+#include "mlp_fused_impl.h"
 #include "mlp_tile_fwd.h"
 
 namespace dct {
@@ -72,7 +74,9 @@ __device__ __forceinline__ float pick4(const float (&v)[4], int i) {
   return i == 0 ? v[0] : (i == 1 ? v[1] : (i == 2 ? v[2] : v[3]));
 }
 
-template <int L>
+// WL: the class-weighted / label-smoothed loss, chosen on the host from the launch arguments - the plain
+// instantiation is the kernel as it was
+template <int L, bool WL>
 __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, long long T, long long S, int nslots) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds lo = lds_layout(L);
@@ -82,6 +86,14 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
   const int D0 = tp.D0, H1 = tp.H1, H2 = tp.H2, C = tp.C, K = tp.K;
   const bool stats = a.Y != nullptr;
   const bool norm = a.norm_mean != nullptr;
+  // class-weighted / label-smoothed CE: the weights in (scalar) registers
+  constexpr bool wloss = WL;
+  float cw[4] = {1.f, 1.f, 1.f, 1.f};
+  if (WL && a.class_w) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < C) cw[c] = a.class_w[c];
+  }
 
   float* X0 = lds + lo.x0;
   float* W0s = lds + lo.w0;
@@ -181,7 +193,13 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
         if (stats && part == 0) {
           const int y = lab[r];
           float loss = 0.f;
-          if (a.loss_kind == 0) {
+          if (wloss) {
+            // the trainer's row loss (mlp_fused_impl.h): the numerator of the weighted mean; labels outside 0 .. C - 1
+            // carry no weight and add nothing
+            float dz[4], wy;
+            loss = row_loss4_weighted(z, C, y, cw, a.label_smooth, dz, &wy);
+            if (y < 0 || y >= C) loss = 0.f;
+          } else if (a.loss_kind == 0) {
             float zy = 0.f;
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -252,10 +270,10 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_infer_fold_kernel(const long long
   }
 }
 
-template <int L>
+template <int L, bool WL>
 static hipError_t launch(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
   const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
-  auto fn = mlp_infer_kernel<L>;
+  auto fn = mlp_infer_kernel<L, WL>;
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), bytes, st, tp, a, sl.T, sl.S, sl.nslots);
@@ -283,6 +301,8 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, 
   if (a->n < 1 || !a->X || a->ldx < tp.D0) return (int)hipErrorInvalidValue;
   if ((a->norm_mean == nullptr) != (a->norm_std == nullptr)) return (int)hipErrorInvalidValue;
   if (a->loss_kind != 0 && a->loss_kind != 1) return (int)hipErrorInvalidValue;
+  if (!(a->label_smooth >= 0.f && a->label_smooth < 1.f)) return (int)hipErrorInvalidValue;
+  if ((a->class_w || a->label_smooth != 0.f) && a->loss_kind != 0) return (int)hipErrorInvalidValue;  // CE only
   if (grid > dct::infer::MAX_GRID) return (int)hipErrorInvalidValue;
   const dct::infer::Slots sl = dct::infer::slots_of(a->n);
   if (a->Y) {
@@ -292,7 +312,11 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, 
   }
   if (grid <= 0) grid = sl.nslots < 1024 ? sl.nslots : 1024;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return (int)(L == 2 ? dct::infer::launch<2>(tp, *a, sl, grid, st) : dct::infer::launch<3>(tp, *a, sl, grid, st));
+  if (a->class_w || a->label_smooth != 0.f)
+    return (int)(L == 2 ? dct::infer::launch<2, true>(tp, *a, sl, grid, st)
+                        : dct::infer::launch<3, true>(tp, *a, sl, grid, st));
+  return (int)(L == 2 ? dct::infer::launch<2, false>(tp, *a, sl, grid, st)
+                      : dct::infer::launch<3, false>(tp, *a, sl, grid, st));
 }
 
 }  // extern "C"

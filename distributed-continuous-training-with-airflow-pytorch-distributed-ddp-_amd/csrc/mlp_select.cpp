@@ -33,6 +33,7 @@ MlpLaunchKey mlp_launch_key(const MlpArgs& a) {
   k.xg_bufs = a.xg_recv != nullptr && a.xg_peers != nullptr && a.xg_status != nullptr;
   k.p_aligned = ((uintptr_t)a.p & 15) == 0;
   k.mv_aligned = (((uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0;
+  k.weighted = a.class_w != nullptr || a.label_smooth != 0.f;
   return k;
 }
 
@@ -48,6 +49,8 @@ MlpChoice mlp_select_trainer(const MlpShape& sh, bool use_wave, bool use_tile, c
     if (!mlp_tile_batch_ok(k.B)) return none("batch outside the batch-tiled trainer's range", false);
     return take(MLP_TILE);
   }
+  if (k.weighted)
+    return none("class weights / label smoothing need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.pending && !use_wave) return none("update-then-grad needs the single-wave kernel", true);
   // 2. the wave kernels, where the plan is a wave plan and they take this batch
   if (use_wave && dct_mlp_wave_supported(sh.dims, sh.L, k.B)) {

@@ -28,6 +28,7 @@ struct MlpLaunchKey {
   bool xg_bufs;     // xg_recv, xg_peers and xg_status bound
   bool p_aligned;   // p on a 16-byte boundary
   bool mv_aligned;  // m and v on 16-byte boundaries (unbound counts as aligned)
+  bool weighted;    // class_w bound or label_smooth != 0: only the batch-tiled trainer computes that loss
 };
 MlpLaunchKey mlp_launch_key(const MlpArgs& a);  // the only place pointers become bools
 

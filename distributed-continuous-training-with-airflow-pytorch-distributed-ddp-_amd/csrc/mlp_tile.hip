@@ -10,11 +10,14 @@
 //     and dlogits / bs on the VALU -> dX and dW of the hidden x hidden layer on the MFMA, the
 //     narrow layers on the VALU -> the tile's partial gradients [P] and partial loss sum go to its
 //     own slot of the workspace [T][Pp] with plain vector stores.  Rows >= bs contribute zeros, a
-//     tile without a live row writes a zero slot.
+//     tile without a live row writes a zero slot.  With class weights / label smoothing (MlpArgs::class_w,
+//     label_smooth; CE only) the row loss is row_loss4_weighted's numerator and un-normalised dlogits, and the
+//     tile also writes the sum of w[y] over its live rows to slot word P + 1.
 //   fold kernel (grid ceil((P + 1) / 256)): sums the T slots in ascending tile index (bit-identical
 //     whatever order the tiles finished in), then Adam (adam_elem, train mode) or grad_out (grad
-//     mode), the batch loss, and the device step counter / batch cursor.  The kernel boundary is
-//     what makes the slots visible across XCDs; no workgroup ever waits on another one.  The
+//     mode), the batch loss, and the device step counter / batch cursor.  Weighted: it first sums the tiles' w[y]
+//     words in the same order into W and divides the folded gradient and loss by it (torch's weighted mean).
+//     The kernel boundary is what makes the slots visible across XCDs; no workgroup ever waits on another one.  The
 //     counters are advanced by the fold's last-arriving workgroup (an arrival counter that it
 //     leaves at zero, so a captured launch pair replays).
 //
@@ -68,7 +71,9 @@ __device__ __forceinline__ float drop_apply(float z, uint32_t seed, uint32_t gst
   return (u01(h) < p) ? 0.f : z * scale;
 }
 
-template <int L>
+// WL: the class-weighted / label-smoothed loss (class_w bound or label_smooth != 0), chosen on the host from the
+// launch arguments - the plain instantiation is the kernel as it was
+template <int L, bool WL>
 __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds lo = lds_layout(L);
@@ -87,6 +92,14 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
   const int row0 = blockIdx.x * R;
   const bool dropping = a.dropout > 0.f;
   const float dscale = dropping ? a.k_drop_scale : 1.0f;
+  // class-weighted / label-smoothed CE: the weights in (scalar) registers
+  constexpr bool wloss = WL;
+  float cw[4] = {1.f, 1.f, 1.f, 1.f};
+  if (WL && a.class_w) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < C) cw[c] = a.class_w[c];
+  }
 
   float* X0 = lds + lo.x0;
   float* W0s = lds + lo.w0;
@@ -164,11 +177,21 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
     head_logits(z, Ah, Wl, C, K, tid);
     if ((tid & 7) == 0) {
       const bool live = (row0 + r) < bs;
-      const float inv = 1.0f / (float)(bs > 0 ? bs : 1);
-      const LossAcc rl = row_loss4(z, C, lab[r], a.loss_kind, live ? inv : 0.f, dz);
+      if (wloss) {
+        // un-normalised: the fold divides the folded gradient and loss by W = sum of w[y] over the batch's live rows
+        float wy;
+        const float num = row_loss4_weighted(z, C, lab[r], cw, a.label_smooth, dz, &wy);
 #pragma unroll
-      for (int c = 0; c < 4; ++c) dZL[r * 4 + c] = (c < C) ? dz[c] : 0.f;
-      lossr[r] = live ? rl.loss : 0.f;
+        for (int c = 0; c < 4; ++c) dZL[r * 4 + c] = (c < C && live) ? dz[c] : 0.f;
+        lossr[r] = live ? num : 0.f;
+        lab[r] = __float_as_int(live ? wy : 0.f);  // w[y] where the label was (read above, by this thread only)
+      } else {
+        const float inv = 1.0f / (float)(bs > 0 ? bs : 1);
+        const LossAcc rl = row_loss4(z, C, lab[r], a.loss_kind, live ? inv : 0.f, dz);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) dZL[r * 4 + c] = (c < C) ? dz[c] : 0.f;
+        lossr[r] = live ? rl.loss : 0.f;
+      }
     }
   }
   __syncthreads();
@@ -198,6 +221,11 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
     float s = 0.f;
     for (int r = 0; r < R; ++r) s += lossr[r];
     slot[tp.P] = s;
+    if (wloss) {  // the tile's share of W, rows in ascending order
+      float sw = 0.f;
+      for (int r = 0; r < R; ++r) sw += __int_as_float(lab[r]);
+      slot[tp.P + 1] = sw;
+    }
   }
   __syncthreads();
 
@@ -270,6 +298,7 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
 }
 
 // Sum the T slots in ascending tile index; Adam (train mode) or grad_out (grad mode); loss and counters.
+template <bool WL>
 __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs a, int T, unsigned int* done) {
   __shared__ int s_cnt[2];
   const int tid = threadIdx.x;
@@ -286,6 +315,16 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
     float g = 0.f;
 #pragma unroll 8
     for (int t = 0; t < T; ++t) g += w[(size_t)t * tp.Pp];
+    constexpr bool wloss = WL;
+    if (wloss) {
+      // weighted loss: the slots hold un-normalised sums; W = the tiles' sums of w[y] in ascending tile index - the
+      // same value in every thread, for every parameter and for the loss (0 only for a batch without a live row)
+      const float* ww = a.tile_ws + tp.P + 1;
+      float W = 0.f;
+#pragma unroll 8
+      for (int t = 0; t < T; ++t) W += ww[(size_t)t * tp.Pp];
+      g = W > 0.f ? g / W : 0.f;
+    }
     if (e < tp.P) {
       if (adam) {
         const int t = tcur + 1;
@@ -303,7 +342,7 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
       }
     } else {
       const int bs = max(0, min(a.B, a.n_items - cur * a.B));
-      const float bl = bs > 0 ? g / (float)bs : 0.f;
+      const float bl = wloss ? g : (bs > 0 ? g / (float)bs : 0.f);
       if (a.cursor && cur > 0 && a.loss_out) a.loss_out[cur - 1] = a.grad_out[tp.P];
       if (a.loss_out && !a.cursor) a.loss_out[0] = bl;
       if (!adam) a.grad_out[tp.P] = bl;
@@ -322,11 +361,11 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
   }
 }
 
-template <int L>
+template <int L, bool WL>
 static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* done, hipStream_t st) {
   const int T = (a0.B + R - 1) / R;
   const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
-  auto fn = mlp_tile_step_kernel<L>;
+  auto fn = mlp_tile_step_kernel<L, WL>;
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
   const int fold_grid = (tp.P + 1 + FOLD_NT - 1) / FOLD_NT;
@@ -339,7 +378,7 @@ static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* 
     a.step_base = a0.step_base + (uint32_t)s;
     if (a0.loss_out && !a0.cursor) a.loss_out = a0.loss_out + s;
     hipLaunchKernelGGL(fn, dim3(T), dim3(NT), bytes, st, tp, a);
-    hipLaunchKernelGGL(mlp_tile_fold_kernel, dim3(fold_grid), dim3(FOLD_NT), 0, st, tp, a, T, done);
+    hipLaunchKernelGGL(mlp_tile_fold_kernel<WL>, dim3(fold_grid), dim3(FOLD_NT), 0, st, tp, a, T, done);
   }
   return hipGetLastError();
 }
@@ -372,10 +411,16 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stre
   if (a->mode == 1 && a->steps != 1) return (int)hipErrorInvalidValue;
   if (!a->cursor && (long long)(a->steps - 1) * a->B >= a->n_items) return (int)hipErrorInvalidValue;
   if (a->xg_world > 1 || a->pending) return (int)hipErrorInvalidValue;
+  if (!(a->label_smooth >= 0.f && a->label_smooth < 1.f)) return (int)hipErrorInvalidValue;
+  if ((a->class_w || a->label_smooth != 0.f) && a->loss_kind != 0) return (int)hipErrorInvalidValue;  // CE only
   if (!a->tile_ws || a->tile_ws_floats < dct_mlp_tile_ws_floats(dims, L, a->B)) return (int)hipErrorInvalidValue;
   unsigned int* done = reinterpret_cast<unsigned int*>(a->tile_ws + (a->tile_ws_floats - 4));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return (int)(L == 2 ? dct::tile::launch_steps<2>(tp, *a, done, st) : dct::tile::launch_steps<3>(tp, *a, done, st));
+  if (a->class_w || a->label_smooth != 0.f)
+    return (int)(L == 2 ? dct::tile::launch_steps<2, true>(tp, *a, done, st)
+                        : dct::tile::launch_steps<3, true>(tp, *a, done, st));
+  return (int)(L == 2 ? dct::tile::launch_steps<2, false>(tp, *a, done, st)
+                      : dct::tile::launch_steps<3, false>(tp, *a, done, st));
 }
 
 }  // extern "C"

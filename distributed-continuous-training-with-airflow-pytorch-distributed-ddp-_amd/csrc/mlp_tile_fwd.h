@@ -48,7 +48,7 @@ static inline bool make_plan(Plan* tp, const int* dims, int L) {
     flat += dims[l + 1];
   }
   tp->P = flat;
-  tp->Pp = (flat + 1 + 3) & ~3;
+  tp->Pp = (flat + 2 + 3) & ~3;  // [P] gradients, the loss sum, the weighted loss's sum of w[y]
   return true;
 }
 

@@ -20,16 +20,35 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops.fused_mlp import check_class_weight, check_label_smoothing
 from ..trainer.module import TrainModule
 
 
 class MLPClassifier(TrainModule):
     def __init__(self, input_dim: int, hidden: Sequence[int] = (64,), num_classes: int = 2, dropout: float = 0.2,
-                 loss: str = "ce", lr: float = 0.01):
+                 loss: str = "ce", lr: float = 0.01, class_weight: Optional[Sequence[float]] = None,
+                 label_smoothing: float = 0.0):
         super().__init__()
         self.save_hyperparameters()
         if loss not in ("ce", "mse"):
             raise ValueError("loss must be 'ce' or 'mse'")
+        # torch's CrossEntropyLoss(weight=, label_smoothing=): exactly num_classes finite, strictly positive weights,
+        # smoothing in [0, 1); cross-entropy only
+        w = check_class_weight(class_weight, num_classes)
+        self.label_smoothing = check_label_smoothing(label_smoothing)
+        if loss != "ce" and (w is not None or self.label_smoothing != 0.0):
+            raise ValueError("class_weight / label_smoothing apply to loss='ce' only")
+        # recorded hyper-parameters: plain Python numbers (checkpoints, YAML), and only when set - a model without
+        # the two options records what it always did
+        for key, on, val in (("class_weight", w is not None, None if w is None else [float(x) for x in w.tolist()]),
+                             ("label_smoothing", self.label_smoothing != 0.0, self.label_smoothing)):
+            if key in self.hparams:
+                if on:
+                    self.hparams[key] = val
+                else:
+                    del self.hparams[key]
+        # a buffer follows .to(device); non-persistent: the state_dict keys stay net.<i>.weight / bias
+        self.register_buffer("class_weight", w, persistent=False)
         dims = [int(input_dim)] + [int(h) for h in hidden] + [int(num_classes)]
         layers: List[nn.Module] = []
         for i in range(len(dims) - 1):
@@ -47,7 +66,7 @@ class MLPClassifier(TrainModule):
 
     def compute_loss(self, logits, y):
         if self.loss_kind == "ce":
-            return F.cross_entropy(logits, y)
+            return F.cross_entropy(logits, y, weight=self.class_weight, label_smoothing=self.label_smoothing)
         return F.mse_loss(logits, F.one_hot(y, logits.shape[-1]).to(logits.dtype))
 
     def training_step(self, batch, batch_idx):
@@ -79,7 +98,13 @@ class MLPClassifier(TrainModule):
 
     # ---- fused-engine contract
     def fused_spec(self):
-        return {"dims": list(self.dims), "dropout": self.dropout_p, "loss": self.loss_kind}
+        spec = {"dims": list(self.dims), "dropout": self.dropout_p, "loss": self.loss_kind}
+        # only when set: a spec without them is the plain loss every engine and kernel takes
+        if self.class_weight is not None:
+            spec["class_weight"] = self.class_weight.detach().float().cpu()
+        if self.label_smoothing != 0.0:
+            spec["label_smoothing"] = self.label_smoothing
+        return spec
 
     def linear_layers(self) -> List[nn.Linear]:
         return [m for m in self.net if isinstance(m, nn.Linear)]
@@ -88,16 +113,24 @@ class MLPClassifier(TrainModule):
 class WeatherClassifier(MLPClassifier):
     """Reference model: Linear(D,64)-ReLU-Dropout(0.2)-Linear(64,2), CE, Adam(lr=0.01)."""
 
-    def __init__(self, input_dim: int):
-        super().__init__(input_dim=input_dim, hidden=(64,), num_classes=2, dropout=0.2, loss="ce", lr=0.01)
-        # the reference records exactly {"input_dim": D} (save_hyperparameters at :53)
-        self._set_hparams({"input_dim": int(input_dim)})
+    def __init__(self, input_dim: int, class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0):
+        super().__init__(input_dim=input_dim, hidden=(64,), num_classes=2, dropout=0.2, loss="ce", lr=0.01,
+                         class_weight=class_weight, label_smoothing=label_smoothing)
+        # the reference records exactly {"input_dim": D} (save_hyperparameters at :53); the two loss options join
+        # it only when set
+        hp = {"input_dim": int(input_dim)}
+        if self.class_weight is not None:
+            hp["class_weight"] = [float(x) for x in self.class_weight.tolist()]
+        if self.label_smoothing != 0.0:
+            hp["label_smoothing"] = self.label_smoothing
+        self._set_hparams(hp)
 
 
 def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None, num_classes: int = 2,
-              dropout: float = 0.2, loss: str = "ce", lr: float = 0.01) -> MLPClassifier:
+              dropout: float = 0.2, loss: str = "ce", lr: float = 0.01,
+              class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0) -> MLPClassifier:
     if name == "weather":
-        return WeatherClassifier(input_dim)
+        return WeatherClassifier(input_dim, class_weight=class_weight, label_smoothing=label_smoothing)
     # name -> (hidden widths, dropout, loss, lr); BASELINE.json configs 1-4
     presets = {
         "weather-mlp-3x128": ((128, 128), 0.2, "ce", 0.01),
@@ -105,4 +138,5 @@ def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None,
     }
     if name in presets and hidden is None:
         hidden, dropout, loss, lr = presets[name]
-    return MLPClassifier(input_dim, hidden=hidden or (64,), num_classes=num_classes, dropout=dropout, loss=loss, lr=lr)
+    return MLPClassifier(input_dim, hidden=hidden or (64,), num_classes=num_classes, dropout=dropout, loss=loss, lr=lr,
+                         class_weight=class_weight, label_smoothing=label_smoothing)

@@ -121,6 +121,44 @@ def _table_ptr(lr_tab: Optional[torch.Tensor]) -> int:
     return lr_tab.data_ptr()
 
 
+def check_label_smoothing(label_smoothing) -> float:
+    """``label_smoothing`` as a float in [0, 1) (torch's range without 1: a fully smoothed target has no label)."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing!r}")
+    return eps
+
+
+def check_class_weight(class_weight, num_classes: int) -> Optional[torch.Tensor]:
+    """``class_weight`` (None, a sequence or a tensor) as a CPU fp32 [C] tensor: exactly ``num_classes`` finite,
+    strictly positive weights - so that a batch with a live row always has a positive normaliser."""
+    if class_weight is None:
+        return None
+    w = torch.as_tensor(class_weight).detach().to("cpu", torch.float32).reshape(-1)
+    if w.numel() != int(num_classes):
+        raise ValueError(f"class_weight needs exactly {int(num_classes)} weights, got {w.numel()}")
+    if not bool(torch.isfinite(w).all()) or not bool((w > 0).all()):
+        raise ValueError("class_weight must be finite and strictly positive")
+    return w
+
+
+def confusion_weight_sum(confusion: torch.Tensor, class_weight=None) -> float:
+    """``W = sum_i w[y_i]`` of the rows an ``infer`` launch counted, from its int64 confusion matrix (rows = label):
+    ``sum_c w[c] * (row sum c)`` in fp64 - exact for fp32 weights (``class_weight=None``: the row count)."""
+    rows = confusion.sum(1).to(torch.float64)
+    w = torch.ones_like(rows) if class_weight is None else torch.as_tensor(class_weight).detach().cpu().double()
+    return float((w.reshape(-1) * rows).sum())
+
+
+def weighted_infer_stats(loss_sum: float, correct: int, confusion: torch.Tensor, class_weight=None):
+    """(weighted loss mean, correct, confusion) of an ``infer`` launch that ran with class weights / label smoothing.
+
+    There statistic word 0 is the numerator ``sum_i num_i``; the normaliser needs no accumulator of its own, it is
+    ``confusion_weight_sum``'s (``class_weight=None``: smoothing alone).  nan for a launch without a labelled row."""
+    W = confusion_weight_sum(confusion, class_weight)
+    return (loss_sum / W if W > 0 else float("nan")), correct, confusion
+
+
 class FusedMLPKernel:
     def __init__(self, dims: Sequence[int], bmax: int):
         if bmax not in (4, 16, TILE_BMAX):
@@ -205,6 +243,28 @@ class FusedMLPKernel:
         if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() >= n_items):
             raise ValueError("idx must be cuda int32 with at least n_items entries")
 
+    def _check_wloss(self, class_weight, label_smoothing, loss: str, device) -> dict:
+        """The native arguments of a class-weighted / label-smoothed launch ({} when both are off)."""
+        eps = check_label_smoothing(label_smoothing)
+        if class_weight is None and eps == 0.0:
+            return {}
+        if loss != "ce":
+            raise ValueError("class_weight / label_smoothing apply to the cross-entropy loss only")
+        if class_weight is not None:
+            C = self.dims[-1]
+            if not (isinstance(class_weight, torch.Tensor) and class_weight.is_cuda and class_weight.device == device
+                    and class_weight.dtype == torch.float32 and class_weight.is_contiguous()
+                    and class_weight.numel() == C):
+                raise ValueError(f"class_weight must be a contiguous cuda fp32 [{C}] tensor on the parameters' device")
+        return dict(class_w=ptr(class_weight), label_smooth=eps)
+
+    def _check_wloss_train(self, class_weight, label_smoothing, loss: str, device, batch: int) -> dict:
+        args = self._check_wloss(class_weight, label_smoothing, loss, device)
+        if args and self.plan.trainer(int(batch), weighted=True) != "tile":
+            raise ValueError("class_weight / label_smoothing need the batch-tiled trainer: a plan of bmax 1024 "
+                             "(any batch 1..1024) for an architecture it takes")
+        return args
+
     # ------------------------------------------------------------------ launches
     def train(self, p, m, v, X, Y, idx, n_items: int, batch: int, steps: int, t0: int, lr: float,
               betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, dropout: float = 0.0,
@@ -213,8 +273,13 @@ class FusedMLPKernel:
               cursor: Optional[torch.Tensor] = None, prof: Optional[torch.Tensor] = None,
               pending: Optional[torch.Tensor] = None, stage: Optional[torch.Tensor] = None,
               stream: Optional[int] = None, xg=None, xg_timeout_s: float = 2.0,
-              lr_tab: Optional[torch.Tensor] = None):
+              lr_tab: Optional[torch.Tensor] = None, class_weight: Optional[torch.Tensor] = None,
+              label_smoothing: float = 0.0):
         """Run ``steps`` fused optimizer steps (mode 0) or one gradient step (grad_out given).
+
+        ``class_weight`` (cuda fp32 [C], strictly positive) / ``label_smoothing`` (in [0, 1)): torch's
+        ``F.cross_entropy(weight=, label_smoothing=)`` with its weighted-mean normaliser ``sum_i w[y_i]``; CE only,
+        and only on the batch-tiled trainer's plan (``bmax=TILE_BMAX``, any batch 1..1024).
 
         ``lr_tab``: a device rate table (csrc/lr_table.h, trainer/lr_schedule.py) - every step takes its rate from the
         table's entry for the steps taken before it (t0 + s, or the device step counter's) instead of ``lr``.
@@ -229,6 +294,7 @@ class FusedMLPKernel:
         self._check_data(X, Y, idx, n_items)
         if batch > self.bmax:
             raise ValueError(f"batch {batch} > kernel bmax {self.bmax}")
+        wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         if steps < 1 or (cursor is None and (steps - 1) * batch >= n_items):
             raise ValueError("steps do not match the index list")
         if cursor is not None and (mode != 1 or not (cursor.is_cuda and cursor.dtype == torch.int32)):
@@ -261,14 +327,15 @@ class FusedMLPKernel:
             int(seed) & 0xFFFFFFFF, int(step_base) & 0xFFFFFFFF, ptr(loss_out), mode, LOSS_KINDS[loss],
             ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending), ptr(stage),
             stream if stream is not None else stream_handle(),
-            **xg_args, **self._tile_args(p.device), lr_tab=_table_ptr(lr_tab),
+            **xg_args, **self._tile_args(p.device), lr_tab=_table_ptr(lr_tab), **wl_args,
         )
 
     def prepare_train(self, p, m, v, X, Y, idx, n_items: int, batch: int, lr: float, betas=(0.9, 0.999),
                       eps: float = 1e-8, weight_decay: float = 0.0, dropout: float = 0.0, seed: int = 0,
                       loss_out: Optional[torch.Tensor] = None, loss: str = "ce",
                       step_counter: Optional[torch.Tensor] = None, xg=None, xg_timeout_s: float = 2.0,
-                      xg_ticks: Optional[torch.Tensor] = None, lr_tab: Optional[torch.Tensor] = None) -> "BoundTrain":
+                      xg_ticks: Optional[torch.Tensor] = None, lr_tab: Optional[torch.Tensor] = None,
+                      class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0) -> "BoundTrain":
         """Validate the operands of persistent train-mode launches ONCE and bind them natively.
 
         ``BoundTrain.run(first_step, steps)`` then launches steps [first_step, first_step+steps)
@@ -279,6 +346,7 @@ class FusedMLPKernel:
         self._check_data(X, Y, idx, n_items)
         if not 1 <= batch <= self.bmax:
             raise ValueError(f"batch {batch} outside 1..{self.bmax}")
+        wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         if step_counter is None or not (step_counter.is_cuda and step_counter.dtype == torch.int32):
             raise ValueError("step_counter must be a cuda int32 scalar tensor (launches are step-relative)")
         if loss_out is not None and not (loss_out.is_cuda and loss_out.dtype == torch.float32
@@ -302,8 +370,9 @@ class FusedMLPKernel:
             ptr(p), ptr(m), ptr(v), ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), int(batch), float(lr),
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, ptr(loss_out), 0 if loss_out is None else loss_out.numel(), LOSS_KINDS[loss],
-            ptr(step_counter), **xg_args, **self._tile_args(p.device), lr_tab=_table_ptr(lr_tab))
-        return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws, lr_tab),
+            ptr(step_counter), **xg_args, **self._tile_args(p.device), lr_tab=_table_ptr(lr_tab), **wl_args)
+        return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws, lr_tab,
+                                   class_weight),
                           p.device.index or 0)
 
     # ------------------------------------------------------------ in-kernel all-reduce
@@ -369,7 +438,8 @@ class FusedMLPKernel:
     def infer(self, p, X, n: int, idx: Optional[torch.Tensor] = None, Y: Optional[torch.Tensor] = None,
               loss: str = "ce", logits_out: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
               pred_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, norm=None,
-              grid: Optional[int] = None, stream: Optional[int] = None):
+              grid: Optional[int] = None, stream: Optional[int] = None,
+              class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0):
         """One forward-only launch over rows ``idx[0 .. n)`` of ``X`` (``idx=None``: rows ``0 .. n - 1``).
 
         Per-row outputs, each optional: ``logits_out`` / ``probs_out`` fp32 [n, C], ``pred_out`` int32 [n] (argmax,
@@ -378,7 +448,10 @@ class FusedMLPKernel:
         writes ``stats_out``, ONE cuda int64 buffer of ``2 + C * C`` words: word 0 holds the bits of the fp64 loss sum
         (``stats_out[:1].view(torch.float64)``), word 1 the correct count, words ``2 + y * C + pred`` the confusion
         matrix (rows = label, columns = prediction); ``infer_stats`` unpacks it.  The statistics depend on the inputs
-        and ``n`` only - not on ``grid``, not on the run.  Without ``Y`` nothing is written to ``stats_out``."""
+        and ``n`` only - not on ``grid``, not on the run.  Without ``Y`` nothing is written to ``stats_out``.
+
+        ``class_weight`` (cuda fp32 [C]) / ``label_smoothing`` as in ``train`` (CE only): word 0 is then the numerator
+        ``sum_i num_i`` of torch's weighted mean; ``weighted_infer_stats`` divides it by ``W``."""
         if not self.infer_supported(self.dims):
             raise ValueError(f"the inference kernel does not take the architecture {self.dims}")
         self._check_params(p)
@@ -413,11 +486,12 @@ class FusedMLPKernel:
             for t in (mean, std):
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self.dims[0]):
                     raise ValueError(f"norm = (mean, std) must be contiguous cuda fp32 [{self.dims[0]}] each")
+        wl_args = self._check_wloss(class_weight, label_smoothing, loss, p.device)
         ws = self._infer_ws(p.device, n) if Y is not None else None
         native().mlp_infer(self.dims, ptr(p), ptr(X), X.stride(0), ptr(idx), ptr(Y), n, ptr(mean), ptr(std),
                            LOSS_KINDS[loss], ptr(logits_out), ptr(probs_out), ptr(pred_out), ptr(ws),
                            0 if ws is None else ws.numel() * 8, ptr(stats_out) if Y is not None else 0,
-                           int(grid or 0), stream if stream is not None else stream_handle())
+                           int(grid or 0), stream if stream is not None else stream_handle(), **wl_args)
 
     def infer_stats(self, stats_out: torch.Tensor):
         """(loss sum: float, correct: int, confusion: int64 [C, C] on the CPU) of an ``infer`` launch (one sync)."""

@@ -34,7 +34,7 @@ import torch
 
 from ..data.sampler import distributed_indices
 from ..ops._native import reload_knobs
-from ..ops.fused_mlp import FusedMLPKernel, mlp_num_params
+from ..ops.fused_mlp import TILE_BMAX, FusedMLPKernel, mlp_num_params, tile_supported, weighted_infer_stats
 from ..ops.nn import BatchGather, bound_params, fold_batch_gather, join_side_work, unit_loss_seed
 from ..ops.optim import FlatAdam, adam_flat_, check_clip_args
 from ..parallel.dist import DistContext, init_native_comm
@@ -64,6 +64,11 @@ def adam_hparams_of(opt) -> Optional[Dict]:
         return None
     return dict(lr=float(g["lr"]), betas=tuple(float(b) for b in g["betas"]), eps=float(g["eps"]),
                 weight_decay=float(g["weight_decay"]))
+
+
+def spec_weighted(spec: Dict) -> bool:
+    """A fused_spec() that asks for class weights or label smoothing (models/mlp.py carries the keys only when set)."""
+    return spec.get("class_weight") is not None or float(spec.get("label_smoothing", 0.0)) != 0.0
 
 
 class _EngineBase:
@@ -98,6 +103,9 @@ class FusedMLPEngine(_EngineBase):
         if device.type != "cuda" or not hasattr(model, "fused_spec"):
             return False
         spec = model.fused_spec()
+        if spec_weighted(spec):
+            # class weights / label smoothing: only the batch-tiled trainer computes that loss, at any batch it takes
+            return spec["loss"] == "ce" and tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
         return FusedMLPKernel.supported(spec["dims"], batch_size)
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,
@@ -112,10 +120,19 @@ class FusedMLPEngine(_EngineBase):
         self.dropout = float(spec["dropout"])
         self.loss = spec["loss"]
         self.adam = adam
-        self.kernel = FusedMLPKernel(self.dims, bmax=4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
+        # class-weighted / label-smoothed CE (models/mlp.py): the batch-tiled trainer's plan whatever the batch, and
+        # the two arguments on every train launch; validation through the tiled inference kernel
+        self.weighted = spec_weighted(spec)
+        bmax = TILE_BMAX if self.weighted else (4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
+        self.kernel = FusedMLPKernel(self.dims, bmax=bmax)
         self.P = mlp_num_params(self.dims)
         dev = ctx.device
         self.device = dev
+        cw = spec.get("class_weight")
+        self.class_weight = None if cw is None else torch.as_tensor(cw, dtype=torch.float32).contiguous().to(dev)
+        self.wloss = {}
+        if self.weighted:
+            self.wloss = dict(class_weight=self.class_weight, label_smoothing=float(spec.get("label_smoothing", 0.0)))
         self.p = self._flat_from_model().to(dev)
         self.m = torch.zeros_like(self.p)
         self.v = torch.zeros_like(self.p)
@@ -298,7 +315,7 @@ class FusedMLPEngine(_EngineBase):
                                            loss_out=loss_out, loss=self.loss, step_counter=self.step_counter,
                                            xg=self.xg, xg_timeout_s=getattr(self, "xg_timeout_s", 20.0),
                                            xg_ticks=getattr(self, "xg_ticks", None) if self.xg is not None else None,
-                                           lr_tab=tab)
+                                           lr_tab=tab, **self.wloss)
             self._bound, self._bound_key = bl, key
         return bl
 
@@ -377,13 +394,13 @@ class FusedMLPEngine(_EngineBase):
                               weight_decay=a["weight_decay"], dropout=self.dropout, seed=self.rank_seed,
                               loss=self.loss, grad_out=self.gbuf, step_counter=self.step_counter,
                               cursor=self.cursor, loss_out=loss_out, pending=self.pending, stage=self.stage,
-                              lr_tab=self._lr_tab())
+                              lr_tab=self._lr_tab(), **self.wloss)
             self.comm.allreduce(self.gbuf.data_ptr(), self.P + 1, nat.DT_F32, nat.OP_AVG, stream)
             return
         self.kernel.train(self.p, None, None, self.X, self.Y, self.idx, n_items=n_items, batch=self.B, steps=1,
                           t0=0, lr=a["lr"], dropout=self.dropout, seed=self.rank_seed, loss=self.loss,
                           grad_out=self.gbuf, step_counter=self.step_counter, cursor=self.cursor,
-                          loss_out=loss_out)
+                          loss_out=loss_out, **self.wloss)
         if self.gx is not None:
             from ..parallel.xgmi import allreduce_adam_
 
@@ -477,7 +494,7 @@ class FusedMLPEngine(_EngineBase):
                               steps=k, t0=0, lr=a["lr"], betas=a["betas"], eps=a["eps"],
                               weight_decay=a["weight_decay"], dropout=self.dropout, seed=self.rank_seed,
                               loss_out=loss_out, loss=self.loss, step_counter=self.step_counter, xg=self.xg,
-                              xg_timeout_s=probe_timeout_s(), lr_tab=self._lr_tab())
+                              xg_timeout_s=probe_timeout_s(), lr_tab=self._lr_tab(), **self.wloss)
         else:
             full, self.xg_timeout_s = self.xg_timeout_s, probe_timeout_s()
             try:
@@ -549,6 +566,18 @@ class FusedMLPEngine(_EngineBase):
         if r.numel() > self.val_idx.numel():
             self.val_idx = torch.zeros(r.numel(), dtype=torch.int32, device=self.device)
         self.val_idx[: r.numel()].copy_(r)
+        if self.weighted:
+            # mlp_eval_kernel knows no weights: one launch of the tiled inference kernel over the shard, the weighted
+            # mean sum_i num_i / sum_i w[y_i] of the whole shard, then the cross-rank mean as below
+            stats = getattr(self, "_infer_stats", None)
+            if stats is None:
+                C = self.dims[-1]
+                stats = self._infer_stats = torch.zeros(2 + C * C, dtype=torch.int64, device=self.device)
+            self.kernel.infer(self.p, self.X, r.numel(), idx=self.val_idx, Y=self.Y, loss=self.loss, stats_out=stats,
+                              **self.wloss)
+            vl, correct, _ = weighted_infer_stats(*self.kernel.infer_stats(stats), self.class_weight)
+            vals = self.ctx.all_reduce_mean(torch.tensor([vl, correct / r.numel()], dtype=torch.float64)).tolist()
+            return vals[0], vals[1]
         self.eval_acc.zero_()
         self.kernel.evaluate(self.p, self.X, self.Y, self.val_idx, r.numel(), self.eval_acc, loss=self.loss)
         stats = self.eval_acc / float(r.numel())

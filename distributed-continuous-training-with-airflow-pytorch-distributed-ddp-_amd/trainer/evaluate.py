@@ -8,7 +8,8 @@ ckpt_path="best")``, ``trainer.predict(model, loader)``) on two paths:
     step the call would run (``validation_step`` / ``test_step`` / ``predict_step``, and ``forward``) is the library's
     own, not a user override.  The table is uploaded once and ONE launch covers the rank's whole shard;
     ``validate`` / ``test`` read the launch's statistics (fp64 loss sum, integer counts - the same bits whatever the
-    grid), ``predict`` returns views of one ``[n, C]`` logits tensor split by the loader's batch size, and
+    grid; a class-weighted / label-smoothed model reports the weighted mean ``sum num_i / sum w[y_i]`` over the
+    rank's whole shard), ``predict`` returns views of one ``[n, C]`` logits tensor split by the loader's batch size, and
     ``trainer.last_confusion_matrix`` holds the int64 ``[C, C]`` confusion matrix (rows = label, columns =
     prediction) summed over ranks.
   * generic: every other model (the wide-MLP and TabTransformer engines' models included) and the CPU -
@@ -33,7 +34,7 @@ import torch
 from ..ckpt.lightning_io import load_checkpoint
 from ..data.dataset import dataset_tensors
 from ..data.sampler import distributed_indices
-from ..ops.fused_mlp import TILE_BMAX, FusedMLPKernel
+from ..ops.fused_mlp import TILE_BMAX, FusedMLPKernel, weighted_infer_stats
 from ..parallel.dist import init_distributed
 
 _STEP = {"val": "validation_step", "test": "test_step", "predict": "predict_step"}
@@ -134,7 +135,7 @@ def _flat_params(model, device) -> torch.Tensor:
 
 
 def _native_launch(trainer, model, X, Y, local, want_logits: bool):
-    """One ``infer`` launch over the rank's shard: (logits or None, (loss sum, correct, confusion) or None)."""
+    """One ``infer`` launch over the rank's shard: (logits or None, (loss mean, correct, confusion) or None)."""
     dev = trainer.ctx.device
     spec = model.fused_spec()
     kern = FusedMLPKernel(spec["dims"], bmax=TILE_BMAX)
@@ -145,9 +146,23 @@ def _native_launch(trainer, model, X, Y, local, want_logits: bool):
     idx = None if trainer.world_size == 1 else local.to(dev, torch.int32)
     logits = torch.empty(n, C, dtype=torch.float32, device=dev) if want_logits else None
     stats = torch.zeros(2 + C * C, dtype=torch.int64, device=dev) if Yd is not None else None
+    # a class-weighted / label-smoothed model (models/mlp.py): the launch sums the weighted numerators, and the mean
+    # is sum_i num_i / sum_i w[y_i] over the shard
+    cw = spec.get("class_weight")
+    eps = float(spec.get("label_smoothing", 0.0))
+    weighted = Yd is not None and (cw is not None or eps != 0.0)
+    wl = {}
+    if weighted:
+        wl = dict(class_weight=None if cw is None else torch.as_tensor(cw, dtype=torch.float32).contiguous().to(dev),
+                  label_smoothing=eps)
     kern.infer(_flat_params(model, dev), Xd, n, idx=idx, Y=Yd, loss=spec["loss"], logits_out=logits,
-               stats_out=stats, norm=_norm_on(trainer, dev))
-    return logits, (kern.infer_stats(stats) if stats is not None else None)
+               stats_out=stats, norm=_norm_on(trainer, dev), **wl)
+    if stats is None:
+        return logits, None
+    loss_sum, correct, conf = kern.infer_stats(stats)
+    if weighted:
+        return logits, weighted_infer_stats(loss_sum, correct, conf, cw)
+    return logits, (loss_sum / max(1, n), correct, conf)
 
 
 def _batches(trainer, model, X, Y, local, B: int):
@@ -175,9 +190,9 @@ def run_eval(trainer, stage: str, model=None, dataloaders=None, ckpt_path: Optio
     local = _local_rows(trainer, len(X))
     trainer.last_confusion_matrix = None
     if native_path(model, ctx.device, stage):
-        _, (loss_sum, correct, conf) = _native_launch(trainer, model, X, Y, local, want_logits=False)
+        _, (loss_mean, correct, conf) = _native_launch(trainer, model, X, Y, local, want_logits=False)
         n = max(1, len(local))
-        vals = ctx.all_reduce_mean(torch.tensor([loss_sum / n, correct / n], dtype=torch.float64)).tolist()
+        vals = ctx.all_reduce_mean(torch.tensor([loss_mean, correct / n], dtype=torch.float64)).tolist()
         conf = conf.to(ctx.device) if ctx.backend == "nccl" else conf
         trainer.last_confusion_matrix = ctx.all_reduce_sum_(conf).cpu()
         out = {f"{stage}_loss": vals[0], f"{stage}_acc": vals[1]}

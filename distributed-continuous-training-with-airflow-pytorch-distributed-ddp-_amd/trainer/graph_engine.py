@@ -73,6 +73,8 @@ class GraphMLPEngine:
         if device.type != "cuda" or not hasattr(model, "fused_spec"):
             return False
         spec = model.fused_spec()
+        if spec.get("class_weight") is not None or float(spec.get("label_smoothing", 0.0)) != 0.0:
+            return False  # the step kernels' loss knows no class weights / label smoothing: the autograd engine's does
         return spec["dropout"] == 0.0 and spec["dims"][0] % 8 == 0 and batch_size >= 1
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,

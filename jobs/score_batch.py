@@ -43,7 +43,7 @@ def model_from_checkpoint(path: str) -> MLPClassifier:
     if "input_dim" not in hp:
         raise ValueError(f"{path}: not an MLP-family checkpoint (hyper_parameters {sorted(hp)}): "
                          "score_batch scores the MLP family only")
-    kw = {k: hp[k] for k in ("hidden", "num_classes", "dropout", "loss") if k in hp}
+    kw = {k: hp[k] for k in ("hidden", "num_classes", "dropout", "loss", "class_weight", "label_smoothing") if k in hp}
     return MLPClassifier(int(hp["input_dim"]), **kw)
 
 

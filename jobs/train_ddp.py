@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import dct_amd  # noqa: E402
 from dct_amd.ckpt import ModelCheckpoint, resume_checkpoint  # noqa: E402
-from dct_amd.config import default_config  # noqa: E402
+from dct_amd.config import balanced_class_weight, default_config, parse_class_weight  # noqa: E402
 from dct_amd.data.dataset import TensorPairDataset, WeatherDataset  # noqa: E402
 from dct_amd.models import build_model  # noqa: E402
 from dct_amd.tracking import MLFlowLogger  # noqa: E402
@@ -41,6 +41,11 @@ def parse_args(argv=None):
     p.add_argument("--gradient-clip-algorithm", default=cfg.optim.gradient_clip_algorithm, choices=("norm", "value"),
                    help="norm: global L2 norm (clip_grad_norm_); value: element-wise (clip_grad_value_)")
     p.add_argument("--model", default=cfg.model.name)
+    p.add_argument("--class-weight", default=cfg.model.class_weight,
+                   help="cross-entropy class weights: 'balanced' (n / (C * count_c) over the training split) or "
+                        "w0,w1,... (MLP family; default: none)")
+    p.add_argument("--label-smoothing", type=float, default=cfg.model.label_smoothing,
+                   help="cross-entropy label smoothing in [0, 1) (MLP family; default 0)")
     p.add_argument("--tracking-uri", default=cfg.tracking.tracking_uri)
     p.add_argument("--experiment", default=cfg.tracking.experiment_name)
     p.add_argument("--accelerator", default=cfg.train.accelerator)
@@ -86,7 +91,17 @@ def main(argv=None) -> int:
     val_loader = DataLoader(val_set, batch_size=a.batch_size, shuffle=False, num_workers=0)
 
     input_dim = full_dataset.features.shape[1]
-    model = build_model(a.model, input_dim, lr=a.lr)
+    loss_kw = {}
+    class_weight = parse_class_weight(a.class_weight)
+    if class_weight == "balanced":
+        # the split is seeded (seed_everything above): every rank counts the same labels
+        labels = full_dataset.labels[torch.as_tensor(train_set.indices)]
+        class_weight = balanced_class_weight(labels, default_config().model.num_classes)
+    if class_weight is not None:
+        loss_kw["class_weight"] = class_weight
+    if a.label_smoothing:
+        loss_kw["label_smoothing"] = a.label_smoothing
+    model = build_model(a.model, input_dim, lr=a.lr, **loss_kw)
 
     world_size = int(os.environ.get("WORLD_SIZE", 1))
     trainer = Trainer(
