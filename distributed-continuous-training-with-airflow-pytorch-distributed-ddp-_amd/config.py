@@ -68,6 +68,7 @@ class OptimConfig:
     weight_decay: float = 0.0
     gradient_clip_val: Optional[float] = None  # Trainer(gradient_clip_val): None or 0 = no clipping
     gradient_clip_algorithm: str = "norm"  # norm (global L2 norm, clip_grad_norm_) | value (clip_grad_value_)
+    accumulate_grad_batches: int = 1  # Trainer(accumulate_grad_batches): micro-batches per optimizer step
 
 
 @dataclass

@@ -73,7 +73,8 @@ struct MlpPlan {
 // The key of a described launch (MlpPlan.trainer): what mlp_launch_key would derive from its arguments,
 // with every buffer the description implies bound.
 static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, int rank, int loss_kind, bool prof,
-                                   bool cursor, bool stage, bool pending, bool aligned, bool weighted) {
+                                   bool cursor, bool stage, bool pending, bool aligned, bool weighted,
+                                   int accumulate) {
   dct::MlpLaunchKey k{};
   k.B = batch; k.mode = mode; k.steps = steps; k.loss_kind = loss_kind;
   k.xg_world = world; k.xg_rank = rank;
@@ -83,6 +84,7 @@ static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, in
   k.xg_bufs = world > 1;
   k.p_aligned = k.mv_aligned = aligned;
   k.weighted = weighted;
+  k.accum = accumulate > 1 ? accumulate : 0;
   return k;
 }
 
@@ -94,11 +96,14 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
                                     uintptr_t step_counter, uintptr_t cursor, uintptr_t prof, uintptr_t pending,
                                     uintptr_t stage, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
                                     uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t class_w = 0,
-                                    float label_smooth = 0.f) {
+                                    float label_smooth = 0.f, int accum = 1) {
   if (!plan.supported) throw std::runtime_error("MLP too large for the fused kernel");
   if (steps < 1 || n_items < 1 || B < 1) throw std::invalid_argument("empty launch");
-  if (!cursor && (int64_t)(steps - 1) * B >= n_items) throw std::invalid_argument("more steps than batches");
+  if (accum < 1) throw std::invalid_argument("accumulate must be >= 1");
+  // (with accumulation a step is a window of accum batches)
+  if (!cursor && (int64_t)(steps - 1) * B * accum >= n_items) throw std::invalid_argument("more steps than batches");
   dct::MlpArgs a{};
+  a.accum = accum;
   a.p = P<float>(p);
   a.m = P<float>(mo);
   a.v = P<float>(vo);
@@ -195,8 +200,9 @@ struct MlpLaunch {
   int64_t loss_len = 0;  // loss slots bound at base.loss_out (0 = none)
   void run(int first_step, int steps, uintptr_t stream) const {
     if (first_step < 0 || steps < 1) throw std::invalid_argument("MlpLaunch.run: bad step range");
-    const int64_t off = (int64_t)first_step * base.B;
-    if (off + (int64_t)(steps - 1) * base.B >= n_items) throw std::invalid_argument("MlpLaunch.run: past the index list");
+    const int64_t rows = (int64_t)base.B * (base.accum > 1 ? base.accum : 1);  // index entries per optimizer step
+    const int64_t off = (int64_t)first_step * rows;
+    if (off + (int64_t)(steps - 1) * rows >= n_items) throw std::invalid_argument("MlpLaunch.run: past the index list");
     if (base.loss_out && first_step + steps > loss_len) throw std::invalid_argument("MlpLaunch.run: past the loss buffer");
     dct::MlpArgs a = base;
     a.idx = base.idx + off;
@@ -279,25 +285,44 @@ PYBIND11_MODULE(_dct_native, m) {
       .def_property_readonly("mlp_block", [](const MlpPlan& p) { return p.sh()->mlp_block; })
       // the trainer a launch of this description reaches: "wave_single", "wave_rows", "block5", "block5_b8",
       // "block3", "lds", "tile" or "none".  `aligned`: the flat buffers lie on 16-byte boundaries; `weighted`: class
-      // weights or label smoothing are on (the batch-tiled trainer's plan only).  No device needed.
+      // weights or label smoothing are on (the batch-tiled trainer's plan only); `accumulate`: micro-batches per
+      // optimizer step (> 1: the batch-tiled trainer's plan only, within its slot cap).  No device needed.
 #define MLP_QUERY_ARGS                                                                                              \
   py::arg("batch"), py::arg("mode") = 0, py::arg("steps") = 1, py::arg("world") = 1, py::arg("rank") = 0,           \
       py::arg("loss_kind") = 0, py::arg("prof") = false, py::arg("cursor") = false, py::arg("stage") = false,       \
-      py::arg("pending") = false, py::arg("aligned") = true, py::arg("weighted") = false
+      py::arg("pending") = false, py::arg("aligned") = true, py::arg("weighted") = false,                           \
+      py::arg("accumulate") = 1
       .def("trainer", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
-                         bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted) {
+                         bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted,
+                         int accumulate) {
         return std::string(dct::mlp_trainer_name(
             plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
-                                  weighted))
+                                  weighted, accumulate))
                 .trainer));
       }, MLP_QUERY_ARGS)
       // whether that launch reads its staged-batch buffer (the wave kernels and mlp_block5's grad mode do)
       .def("uses_stage", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
-                            bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted) {
+                            bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted,
+                            int accumulate) {
         return plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
-                                     weighted))
+                                     weighted, accumulate))
             .use_stage;
       }, MLP_QUERY_ARGS)
+      // one trainer's own predicate on that launch, whatever the selector would choose first (tests): "block5",
+      // "block5_xg", "block3", "wave_rows", "wave_xg"
+      .def("takes", [](const MlpPlan& plan, const std::string& which, int batch, int mode, int steps, int world,
+                       int rank, int loss_kind, bool prof, bool cursor, bool stage, bool pending, bool aligned,
+                       bool weighted, int accumulate) {
+        const dct::MlpLaunchKey k = query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending,
+                                              aligned, weighted, accumulate);
+        const dct::MlpShape& sh = *plan.sh();
+        if (which == "block5") return dct::mlp_block5_takes(sh, k);
+        if (which == "block5_xg") return dct::mlp_block5_xg_shape_ok(sh, k);
+        if (which == "block3") return dct::mlp_block3_takes(sh, k);
+        if (which == "wave_rows") return dct::mlp_wave_rows_takes(sh.L, k);
+        if (which == "wave_xg") return dct::mlp_wave_xg_takes(sh.L, k);
+        throw std::invalid_argument("MlpPlan.takes: unknown trainer predicate " + which);
+      }, py::arg("which"), MLP_QUERY_ARGS)
 #undef MLP_QUERY_ARGS
       .def(
           "train",
@@ -307,13 +332,13 @@ PYBIND11_MODULE(_dct_native, m) {
              int loss_kind, uintptr_t step_counter, uintptr_t cursor, uintptr_t prof, uintptr_t pending,
              uintptr_t stage, uintptr_t stream, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
              uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t tile_ws, int64_t tile_ws_floats,
-             uintptr_t lr_tab, uintptr_t class_w, float label_smooth) {
+             uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             dct::MlpArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
                                                    b1, b2, eps, wd, dropout, seed, step_base, loss_out, mode,
                                                    loss_kind, step_counter, cursor, prof, pending, stage, xg_recv,
                                                    xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll,
-                                                   class_w, label_smooth);
+                                                   class_w, label_smooth, accumulate);
             a.tile_ws = P<float>(tile_ws);
             a.tile_ws_floats = tile_ws_floats;
             a.lr_tab = P<const float>(lr_tab);
@@ -327,7 +352,7 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("stream") = 0, py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL, py::arg("xg_poll") = 0,
           py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0, py::arg("lr_tab") = (uintptr_t)0,
-          py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f)
+          py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f, py::arg("accumulate") = 1)
       .def(
           "prepare_train",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t X, int ldx, uintptr_t Y,
@@ -335,13 +360,13 @@ PYBIND11_MODULE(_dct_native, m) {
              uint32_t seed, uintptr_t loss_out, int64_t loss_len, int loss_kind, uintptr_t step_counter,
              uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank, uintptr_t xg_status,
              int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks, uintptr_t tile_ws, int64_t tile_ws_floats,
-             uintptr_t lr_tab, uintptr_t class_w, float label_smooth) {
+             uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             auto l = std::make_unique<MlpLaunch>(MlpLaunch{plan});
             l->base = make_train_args(plan, p, mo, vo, 0, X, ldx, Y, idx, n_items, B, 1, 0, lr, b1, b2, eps, wd,
                                       dropout, seed, 0, loss_out, 0, loss_kind, step_counter, 0, 0, 0, 0, xg_recv,
                                       xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll, class_w,
-                                      label_smooth);
+                                      label_smooth, accumulate);
             l->base.xg_ticks = P<unsigned long long>(xg_ticks);
             l->base.tile_ws = P<float>(tile_ws);
             l->base.tile_ws_floats = tile_ws_floats;
@@ -356,7 +381,8 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("step_counter"), py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL,
           py::arg("xg_poll") = 0, py::arg("xg_ticks") = 0, py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0,
-          py::arg("lr_tab") = (uintptr_t)0, py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f)
+          py::arg("lr_tab") = (uintptr_t)0, py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f,
+          py::arg("accumulate") = 1)
       .def(
           "eval",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items,
@@ -950,6 +976,14 @@ PYBIND11_MODULE(_dct_native, m) {
   m.def("mlp_tile_ws_floats", [](const std::vector<int>& dims, int B) {
     return (int64_t)dct_mlp_tile_ws_floats(dims.data(), (int)dims.size() - 1, B);
   });
+  // the same for accumulation windows of `accumulate` micro-batches (0: over the slot cap), and the cap
+  m.def("mlp_tile_ws_floats_accum", [](const std::vector<int>& dims, int B, int accumulate) {
+    return (int64_t)dct_mlp_tile_ws_floats_accum(dims.data(), (int)dims.size() - 1, B, accumulate);
+  });
+  m.def("mlp_tile_max_slots", []() { return dct_mlp_tile_max_slots(); });
+  // the batch-tiled trainer's own predicate (mlp_select.h): `accumulate` micro-batches of `batch` rows fit the cap
+  m.def("mlp_tile_window_ok", [](int batch, int accumulate) { return dct::mlp_tile_window_ok(batch, accumulate); },
+        py::arg("batch"), py::arg("accumulate"));
   // batch-tiled inference (mlp_infer.hip): the batch-tiled trainer's shape check (mlp_tile_fwd.h make_plan) under
   // its own name; it and the workspace size need no device
   m.def("mlp_infer_supported", [](const std::vector<int>& dims) {

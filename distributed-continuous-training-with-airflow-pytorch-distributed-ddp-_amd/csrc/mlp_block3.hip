@@ -574,7 +574,7 @@ bool mlp_block3_takes(const MlpShape& sh, const MlpLaunchKey& k) {
   const bool aligned = (sh.woff[1] % 4) == 0 && k.p_aligned && (k.mode != 0 || k.mv_aligned);
   return prof_ok && aligned && sh.L == 3 && sh.dims[1] == blk3::H && sh.dims[2] == blk3::H && sh.dims[0] >= 1 &&
          sh.dims[0] <= blk3::DMAX && sh.dims[3] >= 1 && sh.dims[3] <= 4 && k.B >= 1 && k.B <= blk3::B &&
-         !k.pending && !k.stage && k.xg_world <= 1 && (k.mode == 0 || k.mode == 1);
+         !k.pending && !k.stage && k.xg_world <= 1 && (k.mode == 0 || k.mode == 1) && !k.accum;
 }
 
 // one launch of an instantiation; its dynamic-LDS limit (two 64-KB staging tiles) is raised once

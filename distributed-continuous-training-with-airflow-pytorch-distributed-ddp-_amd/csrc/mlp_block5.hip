@@ -21,14 +21,14 @@ bool mlp_block5_takes(const MlpShape& sh, const MlpLaunchKey& k) {
                      (k.mode == 0 && b5_xg_world_ok(k.xg_world) && k.xg_rank >= 0 && k.xg_rank < k.xg_world &&
                       k.xg_bufs && (!k.prof || k.xg_world == 2 || k.xg_world == 4 || k.xg_world == 8));
   const bool b8_ok = !mlp_block5_two_micro(sh, k.B) || !k.prof;  // no profiling instantiation of the b8 kernels
-  return aligned && b8_ok && mlp_block5_shape_ok(sh.dims, sh.L, k.B) &&
+  return aligned && b8_ok && !k.accum && mlp_block5_shape_ok(sh.dims, sh.L, k.B) &&
          // train mode, or grad mode for ONE step (the DDP step path: grads + loss to grad_out, device cursor)
          ((k.mode == 0 && !k.cursor) || (k.mode == 1 && k.steps == 1 && k.grad_out)) &&
          (k.loss_kind == 0 || k.loss_kind == 1) && !k.pending && (!k.stage || k.mode == 1) && xg_ok;
 }
 
 bool mlp_block5_xg_shape_ok(const MlpShape& sh, const MlpLaunchKey& k) {
-  return k.mode == 0 && mlp_block5_shape_ok(sh.dims, sh.L, k.B) && mlp_block5_xg_bytes(k.xg_world) > 0;
+  return k.mode == 0 && !k.accum && mlp_block5_shape_ok(sh.dims, sh.L, k.B) && mlp_block5_xg_bytes(k.xg_world) > 0;
 }
 
 bool mlp_block5_shape_ok(const int* dims, int L, int B) {

@@ -134,6 +134,14 @@ struct MlpArgs {
   // the plain CE / MSE with the 1 / bs normaliser.  mlp_select.h refuses such a launch on every other trainer.
   const float* class_w;
   float label_smooth;
+  // optional gradient accumulation (batch-tiled trainer only; appended, so every other field keeps its offset): an
+  // optimizer step runs over a window of `accum` micro-batches of B rows - batches [w * accum, (w + 1) * accum) of the
+  // index list - and applies (1 / accum) * sum_kb grad(loss_kb), loss_kb the micro-batch's own mean (Lightning's
+  // accumulate_grad_batches; always 1 / accum, also in a short last window).  `steps`, t0, step_base, the device
+  // counters, the cursor and loss_out count optimizer steps; n_items counts rows; the reported loss is the window's last
+  // live micro-batch's; micro-batch kb of step t draws its dropout masks with step word t * accum + kb.  0 and 1: off.
+  // mlp_select.h refuses such a launch on every other trainer.
+  int accum;
 };
 
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
@@ -201,6 +209,10 @@ size_t dct_mlp_xg_slab_granules(const int* dims, int L);
 // batch-tiled trainer for per-rank batch 17..1024 (mlp_tile.hip; DCT_MLP_BLOCK=tile forces it at smaller batches)
 int dct_mlp_tile_supported(const int* dims, int L);
 long long dct_mlp_tile_ws_floats(const int* dims, int L, int B);
+// the same for windows of `accum` micro-batches (MlpArgs::accum): accum * ceil(B / 32) slots, at most
+// dct_mlp_tile_max_slots() of them (0: over the cap, or not a tile shape / batch); accum <= 1 is the value above
+long long dct_mlp_tile_ws_floats_accum(const int* dims, int L, int B, int accum);
+int dct_mlp_tile_max_slots(void);
 int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream);
 // batch-tiled forward-only inference (mlp_infer.hip); grid <= 0: default.  It and dct_mlp_tile_train share one
 // forward and one host check (mlp_tile_fwd.h): the shapes of dct_mlp_tile_supported, p on a 16-byte boundary

@@ -134,7 +134,7 @@ int dct_mlp_select(const MlpShape* sh, int* nt, int* maxblk) {
 // the generic LDS trainer: no exchange, no staged batches (mlp_select.h sends those elsewhere)
 int dct_mlp_lds_train(const MlpShape& sh, const MlpArgs* a, void* stream) {
   if (!sh.supported) return (int)hipErrorInvalidValue;
-  if (a->B < 1 || a->B > sh.bmax || a->xg_world > 1 || a->stage) return (int)hipErrorInvalidValue;
+  if (a->B < 1 || a->B > sh.bmax || a->xg_world > 1 || a->stage || a->accum > 1) return (int)hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   switch (sh.L) {
     case 2: return (int)dct::mlp_launch_train_L2(sh, *a, st);

@@ -34,6 +34,7 @@ MlpLaunchKey mlp_launch_key(const MlpArgs& a) {
   k.p_aligned = ((uintptr_t)a.p & 15) == 0;
   k.mv_aligned = (((uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0;
   k.weighted = a.class_w != nullptr || a.label_smooth != 0.f;
+  k.accum = a.accum > 1 ? a.accum : 0;
   return k;
 }
 
@@ -47,8 +48,12 @@ MlpChoice mlp_select_trainer(const MlpShape& sh, bool use_wave, bool use_tile, c
     if (xg || k.pending)
       return none("the batch-tiled trainer has no in-kernel all-reduce and no update-then-grad step", true);
     if (!mlp_tile_batch_ok(k.B)) return none("batch outside the batch-tiled trainer's range", false);
+    if (k.accum && !mlp_tile_window_ok(k.B, k.accum))
+      return none("accumulation window over the batch-tiled trainer's slot cap (accum * ceil(B / 32) <= 256)", false);
     return take(MLP_TILE);
   }
+  if (k.accum)
+    return none("gradient accumulation needs the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.weighted)
     return none("class weights / label smoothing need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.pending && !use_wave) return none("update-then-grad needs the single-wave kernel", true);

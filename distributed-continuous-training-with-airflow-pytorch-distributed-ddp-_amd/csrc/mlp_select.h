@@ -29,6 +29,7 @@ struct MlpLaunchKey {
   bool p_aligned;   // p on a 16-byte boundary
   bool mv_aligned;  // m and v on 16-byte boundaries (unbound counts as aligned)
   bool weighted;    // class_w bound or label_smooth != 0: only the batch-tiled trainer computes that loss
+  int accum;        // MlpArgs::accum when > 1 (gradient accumulation on: only the batch-tiled trainer runs windows), else 0
 };
 MlpLaunchKey mlp_launch_key(const MlpArgs& a);  // the only place pointers become bools
 
@@ -54,6 +55,7 @@ bool mlp_block5_two_micro(const MlpShape& sh, int B);  // mlp_block5_b8's two mi
 bool mlp_block3_takes(const MlpShape& sh, const MlpLaunchKey& k);
 // mlp_tile.hip
 bool mlp_tile_batch_ok(int B);
+bool mlp_tile_window_ok(int B, int accum);  // accum micro-batches of B rows fit the slot cap (accum <= 1: always)
 
 }  // namespace dct
 

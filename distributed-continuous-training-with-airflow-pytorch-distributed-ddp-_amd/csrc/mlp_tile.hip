@@ -21,6 +21,12 @@
 //     counters are advanced by the fold's last-arriving workgroup (an arrival counter that it
 //     leaves at zero, so a captured launch pair replays).
 //
+// Gradient accumulation (MlpArgs::accum = K > 1, Lightning's accumulate_grad_batches): an optimizer step is a window of
+// K micro-batches of B rows, run as ONE grid (T, K) - workgroup (tile, kb) works on batch cur * K + kb with its own bs,
+// draws dropout with step word gstep * K + kb and writes slot kb * T + tile - and one fold over the K * T slots in
+// ascending slot index: (1 / K) * sum_kb (micro-batch kb's mean gradient), the loss of the window's last live
+// micro-batch.  K * T <= MAX_SLOTS; the counters, t0, step_base, the cursor and loss_out count optimizer steps.
+//
 // Weights are read straight from the flat parameter buffer (L2 resident, <= 85 KB, on a 16-byte boundary: W1
 // is read as float4); activations and dZ of the tile live in LDS with the two narrow layers' weights (91.5 KB
 // for the 3-layer nets, 57.7 KB for the 2-layer ones).  No LDS-DMA loads.
@@ -41,6 +47,10 @@ namespace dct {
 namespace tile {
 
 constexpr int BMAX = 1024;
+// slots of one optimizer step: accum * ceil(B / R) <= MAX_SLOTS (32 at accum = 1).  256 is one workgroup per CU in a
+// single round (the 3-layer carve's 91.5 KB of LDS leaves room for one per CU); it also bounds the fold's serial sum
+// and the workspace (256 slots of a 3x128 net: about 18 MB)
+constexpr int MAX_SLOTS = 256;
 constexpr int FOLD_NT = 256;
 
 // LDS carve (floats)
@@ -73,7 +83,10 @@ __device__ __forceinline__ float drop_apply(float z, uint32_t seed, uint32_t gst
 
 // WL: the class-weighted / label-smoothed loss (class_w bound or label_smooth != 0), chosen on the host from the
 // launch arguments - the plain instantiation is the kernel as it was
-template <int L, bool WL>
+// ACC: gradient accumulation (MlpArgs::accum > 1), chosen on the host likewise: the grid's second dimension is the
+// micro-batch kb of the window, workgroup (tile, kb) works on batch cur * accum + kb of the index list with that batch's
+// own bs and dropout step word gstep * accum + kb, and writes slot kb * T + tile.  Without it the kernel is as it was.
+template <int L, bool WL, bool ACC>
 __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds lo = lds_layout(L);
@@ -88,7 +101,17 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
   uint32_t gstep = a.step_base;
   if (a.step_counter)
     gstep = (uint32_t)__hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int bs = max(0, min(B, a.n_items - cur * B));
+  // (unsigned, as blockIdx.x: with a signed index the plain kernel's slot address compiled 12 bytes shorter, and the
+  // shifted code measured 0.15 .. 0.3 % slower at batch 256 - profiles/accum_cost.log)
+  unsigned int slot_i = blockIdx.x;
+  if (ACC) {  // from here on `cur` is the micro-batch's index in the list and `gstep` its dropout step word
+    const int kb = blockIdx.y;
+    cur = cur * a.accum + kb;
+    gstep = gstep * (uint32_t)a.accum + (uint32_t)kb;
+    slot_i = blockIdx.y * gridDim.x + blockIdx.x;
+  }
+  const int bs = ACC ? (int)max(0ll, min((long long)B, (long long)a.n_items - (long long)cur * B))
+                     : max(0, min(B, a.n_items - cur * B));
   const int row0 = blockIdx.x * R;
   const bool dropping = a.dropout > 0.f;
   const float dscale = dropping ? a.k_drop_scale : 1.0f;
@@ -111,7 +134,7 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
   float* dZL = lds + lo.dzl;
   float* lossr = lds + lo.lossr;
   int* lab = reinterpret_cast<int*>(lds + lo.lab);
-  float* slot = a.tile_ws + (size_t)blockIdx.x * tp.Pp;
+  float* slot = a.tile_ws + (size_t)slot_i * tp.Pp;
 
   // the epilogue of the hidden layers: dropout keyed by the row within the batch
   const auto drop = [&](int LI, int r, int o, float z) {
@@ -297,8 +320,77 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
   }
 }
 
-// Sum the T slots in ascending tile index; Adam (train mode) or grad_out (grad mode); loss and counters.
+// The folded word e of an accumulation window (ACC): slots kb * T + t in ascending index.  Gradient words (e < P):
+// (1 / accum) * sum_kb g_kb, g_kb the micro-batch's own mean gradient - its tiles already carry 1 / bs_kb, or
+// (weighted) their sum over W_kb = the tiles' w[y] words in tile order, a micro-batch without a live row giving 0.
+// The loss word (e == P): the mean loss of the last live micro-batch alone, n_live = min(accum, ceil(rows left / B)).
 template <bool WL>
+__device__ __forceinline__ float fold_window(const Plan& tp, const MlpArgs& a, int T, int e, int cur) {
+  const float* w = a.tile_ws + e;
+  const float* ww = a.tile_ws + tp.P + 1;
+  if (e < tp.P) {
+    float g = 0.f;
+    if (WL) {
+      for (int kb = 0; kb < a.accum; ++kb) {
+        float gk = 0.f, W = 0.f;
+#pragma unroll 8
+        for (int t = 0; t < T; ++t) gk += w[(size_t)(kb * T + t) * tp.Pp];
+#pragma unroll 8
+        for (int t = 0; t < T; ++t) W += ww[(size_t)(kb * T + t) * tp.Pp];
+        g += W > 0.f ? gk / W : 0.f;
+      }
+    } else {
+      const int S = a.accum * T;
+#pragma unroll 8
+      for (int s = 0; s < S; ++s) g += w[(size_t)s * tp.Pp];
+    }
+    return g / (float)a.accum;
+  }
+  const long long left = (long long)a.n_items - (long long)cur * a.accum * a.B;  // rows from the window's first on
+  if (left <= 0) return 0.f;
+  const int n_live = (int)min((long long)a.accum, (left + a.B - 1) / a.B);
+  const int kb = n_live - 1;
+  float s = 0.f, W = 0.f;
+#pragma unroll 8
+  for (int t = 0; t < T; ++t) s += w[(size_t)(kb * T + t) * tp.Pp];
+  if (WL) {
+#pragma unroll 8
+    for (int t = 0; t < T; ++t) W += ww[(size_t)(kb * T + t) * tp.Pp];
+    return W > 0.f ? s / W : 0.f;
+  }
+  const long long bs = min((long long)a.B, left - (long long)kb * a.B);
+  return s / (float)bs;
+}
+
+// The folded word e of a plain step: the T slots in ascending tile index.  Weighted: the slots hold un-normalised sums
+// and W = the tiles' sums of w[y] in the same order - the same value in every thread, for every parameter and for the
+// loss (0 only for a batch without a live row).  Unweighted: the plain sum - the tiles' gradients carry 1 / bs, the
+// loss word does not (batch_mean).
+template <bool WL>
+__device__ __forceinline__ float fold_plain(const Plan& tp, const MlpArgs& a, int T, int e, int cur) {
+  const float* w = a.tile_ws + e;
+  float g = 0.f;
+#pragma unroll 8
+  for (int t = 0; t < T; ++t) g += w[(size_t)t * tp.Pp];
+  if (WL) {
+    const float* ww = a.tile_ws + tp.P + 1;
+    float W = 0.f;
+#pragma unroll 8
+    for (int t = 0; t < T; ++t) W += ww[(size_t)t * tp.Pp];
+    return W > 0.f ? g / W : 0.f;
+  }
+  return g;
+}
+
+// the unweighted plain step's loss word is the sum over the batch's live rows: its mean
+__device__ __forceinline__ float batch_mean(const MlpArgs& a, int cur, float sum) {
+  const int bs = max(0, min(a.B, a.n_items - cur * a.B));
+  return bs > 0 ? sum / (float)bs : 0.f;
+}
+
+// One word per thread through fold_plain, or (ACC: MlpArgs::accum > 1) the accum * T slots of a window through
+// fold_window; then Adam (train mode) or grad_out (grad mode), the loss and the counters, which count optimizer steps.
+template <bool WL, bool ACC>
 __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs a, int T, unsigned int* done) {
   __shared__ int s_cnt[2];
   const int tid = threadIdx.x;
@@ -311,20 +403,8 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
   const bool adam = (a.mode == 0);
   const int e = blockIdx.x * FOLD_NT + tid;
   if (e <= tp.P) {
-    const float* w = a.tile_ws + e;
-    float g = 0.f;
-#pragma unroll 8
-    for (int t = 0; t < T; ++t) g += w[(size_t)t * tp.Pp];
-    constexpr bool wloss = WL;
-    if (wloss) {
-      // weighted loss: the slots hold un-normalised sums; W = the tiles' sums of w[y] in ascending tile index - the
-      // same value in every thread, for every parameter and for the loss (0 only for a batch without a live row)
-      const float* ww = a.tile_ws + tp.P + 1;
-      float W = 0.f;
-#pragma unroll 8
-      for (int t = 0; t < T; ++t) W += ww[(size_t)t * tp.Pp];
-      g = W > 0.f ? g / W : 0.f;
-    }
+    // the step's gradient word (e < P) or loss word (e == P)
+    const float g = ACC ? fold_window<WL>(tp, a, T, e, cur) : fold_plain<WL>(tp, a, T, e, cur);
     if (e < tp.P) {
       if (adam) {
         const int t = tcur + 1;
@@ -341,8 +421,7 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
         a.grad_out[e] = g;
       }
     } else {
-      const int bs = max(0, min(a.B, a.n_items - cur * a.B));
-      const float bl = wloss ? g : (bs > 0 ? g / (float)bs : 0.f);
+      const float bl = (WL || ACC) ? g : batch_mean(a, cur, g);
       if (a.cursor && cur > 0 && a.loss_out) a.loss_out[cur - 1] = a.grad_out[tp.P];
       if (a.loss_out && !a.cursor) a.loss_out[0] = bl;
       if (!adam) a.grad_out[tp.P] = bl;
@@ -361,24 +440,25 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
   }
 }
 
-template <int L, bool WL>
+template <int L, bool WL, bool ACC>
 static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* done, hipStream_t st) {
   const int T = (a0.B + R - 1) / R;
   const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
-  auto fn = mlp_tile_step_kernel<L, WL>;
+  auto fn = mlp_tile_step_kernel<L, WL, ACC>;
+  const int AK = ACC ? a0.accum : 1;  // micro-batches per optimizer step: the index list advances by AK * B rows
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
   const int fold_grid = (tp.P + 1 + FOLD_NT - 1) / FOLD_NT;
   for (int s = 0; s < a0.steps; ++s) {
     MlpArgs a = a0;
     a.steps = 1;
-    a.idx = a0.idx + (size_t)s * a0.B;
-    a.n_items = a0.n_items - s * a0.B;
+    a.idx = a0.idx + (size_t)s * AK * a0.B;
+    a.n_items = a0.n_items - s * AK * a0.B;
     a.t0 = a0.t0 + s;
     a.step_base = a0.step_base + (uint32_t)s;
     if (a0.loss_out && !a0.cursor) a.loss_out = a0.loss_out + s;
-    hipLaunchKernelGGL(fn, dim3(T), dim3(NT), bytes, st, tp, a);
-    hipLaunchKernelGGL(mlp_tile_fold_kernel<WL>, dim3(fold_grid), dim3(FOLD_NT), 0, st, tp, a, T, done);
+    hipLaunchKernelGGL(fn, dim3(T, AK), dim3(NT), bytes, st, tp, a);
+    hipLaunchKernelGGL((mlp_tile_fold_kernel<WL, ACC>), dim3(fold_grid), dim3(FOLD_NT), 0, st, tp, a, T, done);
   }
   return hipGetLastError();
 }
@@ -386,6 +466,9 @@ static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* 
 }  // namespace tile
 
 bool mlp_tile_batch_ok(int B) { return B >= 1 && B <= tile::BMAX; }
+bool mlp_tile_window_ok(int B, int accum) {
+  return mlp_tile_batch_ok(B) && (accum <= 1 || (long long)accum * ((B + tile::R - 1) / tile::R) <= tile::MAX_SLOTS);
+}
 
 }  // namespace dct
 
@@ -404,23 +487,45 @@ long long dct_mlp_tile_ws_floats(const int* dims, int L, int B) {
   return T * tp.Pp + 4;
 }
 
+long long dct_mlp_tile_ws_floats_accum(const int* dims, int L, int B, int accum) {
+  if (accum <= 1) return dct_mlp_tile_ws_floats(dims, L, B);
+  dct::tile::Plan tp;
+  if (!dct::tile::make_plan(&tp, dims, L) || !dct::mlp_tile_window_ok(B, accum)) return 0;
+  const long long T = (B + dct::tile::R - 1) / dct::tile::R;
+  return accum * T * tp.Pp + 4;
+}
+
+int dct_mlp_tile_max_slots(void) { return dct::tile::MAX_SLOTS; }
+
 int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream) {
   dct::tile::Plan tp;
   if (!dct::tile::plan_launch(&tp, dims, L, a->p)) return (int)hipErrorInvalidValue;
   if (a->B < 1 || a->B > dct::tile::BMAX || a->steps < 1 || a->n_items < 1) return (int)hipErrorInvalidValue;
   if (a->mode == 1 && a->steps != 1) return (int)hipErrorInvalidValue;
-  if (!a->cursor && (long long)(a->steps - 1) * a->B >= a->n_items) return (int)hipErrorInvalidValue;
+  const int accum = a->accum > 1 ? a->accum : 1;
+  if (a->accum < 0 || !dct::mlp_tile_window_ok(a->B, accum)) return (int)hipErrorInvalidValue;
+  if (!a->cursor && (long long)(a->steps - 1) * accum * a->B >= a->n_items) return (int)hipErrorInvalidValue;
   if (a->xg_world > 1 || a->pending) return (int)hipErrorInvalidValue;
   if (!(a->label_smooth >= 0.f && a->label_smooth < 1.f)) return (int)hipErrorInvalidValue;
   if ((a->class_w || a->label_smooth != 0.f) && a->loss_kind != 0) return (int)hipErrorInvalidValue;  // CE only
-  if (!a->tile_ws || a->tile_ws_floats < dct_mlp_tile_ws_floats(dims, L, a->B)) return (int)hipErrorInvalidValue;
+  if (!a->tile_ws || a->tile_ws_floats < dct_mlp_tile_ws_floats_accum(dims, L, a->B, accum))
+    return (int)hipErrorInvalidValue;
   unsigned int* done = reinterpret_cast<unsigned int*>(a->tile_ws + (a->tile_ws_floats - 4));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a->class_w || a->label_smooth != 0.f)
-    return (int)(L == 2 ? dct::tile::launch_steps<2, true>(tp, *a, done, st)
-                        : dct::tile::launch_steps<3, true>(tp, *a, done, st));
-  return (int)(L == 2 ? dct::tile::launch_steps<2, false>(tp, *a, done, st)
-                      : dct::tile::launch_steps<3, false>(tp, *a, done, st));
+  const bool wl = a->class_w || a->label_smooth != 0.f;
+  // (the plain instantiations first: they keep their place at the head of the code object)
+  if (accum <= 1) {
+    if (wl)
+      return (int)(L == 2 ? dct::tile::launch_steps<2, true, false>(tp, *a, done, st)
+                          : dct::tile::launch_steps<3, true, false>(tp, *a, done, st));
+    return (int)(L == 2 ? dct::tile::launch_steps<2, false, false>(tp, *a, done, st)
+                        : dct::tile::launch_steps<3, false, false>(tp, *a, done, st));
+  }
+  if (wl)
+    return (int)(L == 2 ? dct::tile::launch_steps<2, true, true>(tp, *a, done, st)
+                        : dct::tile::launch_steps<3, true, true>(tp, *a, done, st));
+  return (int)(L == 2 ? dct::tile::launch_steps<2, false, true>(tp, *a, done, st)
+                      : dct::tile::launch_steps<3, false, true>(tp, *a, done, st));
 }
 
 }  // extern "C"

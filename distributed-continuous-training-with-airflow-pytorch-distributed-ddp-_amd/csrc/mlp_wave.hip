@@ -26,7 +26,7 @@ size_t dct_mlp_xg_slab_granules(const int* dims, int L) {
 
 int dct_mlp_wave_train(const int* dims, int L, const dct::MlpArgs* a, int rows, void* stream) {
   const dct::MlpLaunchKey k = dct::mlp_launch_key(*a);
-  if (!dct_mlp_wave_supported(dims, L, a->B) || (a->xg_world > 1 && !dct::mlp_wave_xg_takes(L, k)) ||
+  if (!dct_mlp_wave_supported(dims, L, a->B) || k.accum || (a->xg_world > 1 && !dct::mlp_wave_xg_takes(L, k)) ||
       (rows && !dct::mlp_wave_rows_takes(L, k)))
     return (int)hipErrorInvalidValue;
   WaveShape sh{};
@@ -65,13 +65,14 @@ bool mlp_wave_rows_takes(int L, const MlpLaunchKey& k) {
 #else
   const bool prof_ok = !k.prof;
 #endif
-  return L == 2 && k.mode == 0 && !k.cursor && !k.pending && !k.stage && prof_ok && k.B >= 1 && k.B <= 8 && k.moments;
+  return L == 2 && k.mode == 0 && !k.cursor && !k.pending && !k.stage && prof_ok && k.B >= 1 && k.B <= 8 && k.moments &&
+         !k.accum;
 }
 
 // in-kernel data-parallel launches of the wave kernels: 2-layer nets, train mode, up to XG_MAXW ranks
 bool mlp_wave_xg_takes(int L, const MlpLaunchKey& k) {
   return L == 2 && k.mode == 0 && k.xg_bufs && k.xg_world <= XG_MAXW && k.xg_rank >= 0 && k.xg_rank < k.xg_world &&
-         !k.cursor && !k.pending;
+         !k.cursor && !k.pending && !k.accum;
 }
 
 }  // namespace dct

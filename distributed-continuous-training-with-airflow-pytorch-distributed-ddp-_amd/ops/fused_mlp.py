@@ -37,6 +37,21 @@ def tile_supported(dims: Sequence[int]) -> bool:
     return bool(native().mlp_tile_supported([int(d) for d in dims]))
 
 
+def tile_window_ok(dims: Sequence[int], batch: int, accumulate: int) -> bool:
+    """The batch-tiled trainer runs optimizer steps of ``accumulate`` micro-batches of ``batch`` rows for this
+    architecture: its shape rule, and its own window predicate (csrc/mlp_select.h mlp_tile_window_ok: batch 1..1024,
+    ``accumulate * ceil(batch / 32)`` slots within the cap).  No GPU needed."""
+    return tile_supported(dims) and bool(native().mlp_tile_window_ok(int(batch), int(accumulate)))
+
+
+def check_accumulate(accumulate, name: str = "accumulate") -> int:
+    """Micro-batches per optimizer step as an int >= 1 (``Trainer(accumulate_grad_batches=)``, ``train(accumulate=)``);
+    ValueError for a non-integer, a bool or a value < 1 - Lightning's dict schedule is not supported."""
+    if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+        raise ValueError(f"{name} must be an int >= 1, got {accumulate!r}")
+    return accumulate
+
+
 def _mix_hash(a, b, c):
     """csrc/mlp_fused_impl.h mix_hash on numpy uint32 arrays (wrapping arithmetic)."""
     import numpy as np
@@ -172,15 +187,27 @@ class FusedMLPKernel:
         self._tile_ws = None  # slot workspace of the batch-tiled trainer (csrc/mlp_tile.hip)
         self._infer_ws_buf = None  # slot workspace of the inference kernel's statistics (csrc/mlp_infer.hip)
 
-    def _tile_args(self, device) -> dict:
+    def _tile_args(self, device, batch: int = 0, accumulate: int = 1) -> dict:
         """The batch-tiled trainer's slot workspace (partial gradients per tile + the fold's arrival
-        counter, zero between launches), allocated once for batches up to ``bmax``."""
+        counter, zero between launches), allocated once for batches up to ``bmax``; a launch whose accumulation
+        window needs more slots than that gets a larger one (launches bound earlier keep theirs alive)."""
         if not self.plan.use_tile:
             return {}
-        if self._tile_ws is None or self._tile_ws.device != device:
-            n = int(native().mlp_tile_ws_floats(self.dims, max(self.bmax, 16)))
+        n = int(native().mlp_tile_ws_floats(self.dims, max(self.bmax, 16)))
+        if accumulate > 1:
+            n = max(n, int(native().mlp_tile_ws_floats_accum(self.dims, int(batch), int(accumulate))))
+        if self._tile_ws is None or self._tile_ws.device != device or self._tile_ws.numel() < n:
             self._tile_ws = torch.zeros(n, dtype=torch.float32, device=device)
         return dict(tile_ws=ptr(self._tile_ws), tile_ws_floats=self._tile_ws.numel())
+
+    def _check_accumulate(self, accumulate, batch: int) -> dict:
+        """The native argument of a launch over windows of ``accumulate`` micro-batches ({} for 1)."""
+        if check_accumulate(accumulate) == 1:
+            return {}
+        if self.plan.trainer(int(batch), accumulate=accumulate) != "tile":
+            raise ValueError("accumulate > 1 needs the batch-tiled trainer: a plan of bmax 1024 for an architecture it "
+                             f"takes, and accumulate * ceil(batch / 32) <= {int(native().mlp_tile_max_slots())} slots")
+        return dict(accumulate=accumulate)
 
     @property
     def plan(self):
@@ -274,8 +301,15 @@ class FusedMLPKernel:
               pending: Optional[torch.Tensor] = None, stage: Optional[torch.Tensor] = None,
               stream: Optional[int] = None, xg=None, xg_timeout_s: float = 2.0,
               lr_tab: Optional[torch.Tensor] = None, class_weight: Optional[torch.Tensor] = None,
-              label_smoothing: float = 0.0):
+              label_smoothing: float = 0.0, accumulate: int = 1):
         """Run ``steps`` fused optimizer steps (mode 0) or one gradient step (grad_out given).
+
+        ``accumulate`` = K > 1 (Lightning's ``accumulate_grad_batches``; the batch-tiled trainer's plan only): an
+        optimizer step is a window of K micro-batches of ``batch`` rows and applies ``(1 / K) * sum_kb grad(loss_kb)``,
+        ``loss_kb`` the micro-batch's own mean - always 1 / K, also in a short last window.  ``n_items`` still counts
+        rows; ``steps``, ``t0``, ``step_base``, the device counters, the cursor and ``loss_out`` count optimizer steps;
+        the reported loss is the window's last live micro-batch's; micro-batch ``kb`` of step ``t`` draws the dropout
+        mask of ``dropout_keep_mask(seed, t * K + kb, ...)``.
 
         ``class_weight`` (cuda fp32 [C], strictly positive) / ``label_smoothing`` (in [0, 1)): torch's
         ``F.cross_entropy(weight=, label_smoothing=)`` with its weighted-mean normaliser ``sum_i w[y_i]``; CE only,
@@ -295,7 +329,8 @@ class FusedMLPKernel:
         if batch > self.bmax:
             raise ValueError(f"batch {batch} > kernel bmax {self.bmax}")
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
-        if steps < 1 or (cursor is None and (steps - 1) * batch >= n_items):
+        acc_args = self._check_accumulate(accumulate, batch)
+        if steps < 1 or (cursor is None and (steps - 1) * batch * accumulate >= n_items):
             raise ValueError("steps do not match the index list")
         if cursor is not None and (mode != 1 or not (cursor.is_cuda and cursor.dtype == torch.int32)):
             raise ValueError("cursor (cuda int32) is only valid with grad_out")
@@ -327,7 +362,8 @@ class FusedMLPKernel:
             int(seed) & 0xFFFFFFFF, int(step_base) & 0xFFFFFFFF, ptr(loss_out), mode, LOSS_KINDS[loss],
             ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending), ptr(stage),
             stream if stream is not None else stream_handle(),
-            **xg_args, **self._tile_args(p.device), lr_tab=_table_ptr(lr_tab), **wl_args,
+            **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab), **wl_args,
+            **acc_args,
         )
 
     def prepare_train(self, p, m, v, X, Y, idx, n_items: int, batch: int, lr: float, betas=(0.9, 0.999),
@@ -335,18 +371,21 @@ class FusedMLPKernel:
                       loss_out: Optional[torch.Tensor] = None, loss: str = "ce",
                       step_counter: Optional[torch.Tensor] = None, xg=None, xg_timeout_s: float = 2.0,
                       xg_ticks: Optional[torch.Tensor] = None, lr_tab: Optional[torch.Tensor] = None,
-                      class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0) -> "BoundTrain":
+                      class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
+                      accumulate: int = 1) -> "BoundTrain":
         """Validate the operands of persistent train-mode launches ONCE and bind them natively.
 
         ``BoundTrain.run(first_step, steps)`` then launches steps [first_step, first_step+steps)
         over ``idx`` with losses in ``loss_out[first_step + s]`` - the per-launch cost is one
         positional native call (no keyword parsing, no tensor checks), which is what the short
-        timed windows of the benchmark contract see."""
+        timed windows of the benchmark contract see.  ``accumulate`` as in ``train``: the steps are
+        optimizer steps of ``accumulate`` micro-batches each."""
         self._check_params(p, m, v)
         self._check_data(X, Y, idx, n_items)
         if not 1 <= batch <= self.bmax:
             raise ValueError(f"batch {batch} outside 1..{self.bmax}")
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
+        acc_args = self._check_accumulate(accumulate, batch)
         if step_counter is None or not (step_counter.is_cuda and step_counter.dtype == torch.int32):
             raise ValueError("step_counter must be a cuda int32 scalar tensor (launches are step-relative)")
         if loss_out is not None and not (loss_out.is_cuda and loss_out.dtype == torch.float32
@@ -370,7 +409,8 @@ class FusedMLPKernel:
             ptr(p), ptr(m), ptr(v), ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), int(batch), float(lr),
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, ptr(loss_out), 0 if loss_out is None else loss_out.numel(), LOSS_KINDS[loss],
-            ptr(step_counter), **xg_args, **self._tile_args(p.device), lr_tab=_table_ptr(lr_tab), **wl_args)
+            ptr(step_counter), **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab),
+            **wl_args, **acc_args)
         return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws, lr_tab,
                                    class_weight),
                           p.device.index or 0)

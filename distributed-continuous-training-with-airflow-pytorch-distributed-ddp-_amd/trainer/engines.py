@@ -34,7 +34,8 @@ import torch
 
 from ..data.sampler import distributed_indices
 from ..ops._native import reload_knobs
-from ..ops.fused_mlp import TILE_BMAX, FusedMLPKernel, mlp_num_params, tile_supported, weighted_infer_stats
+from ..ops.fused_mlp import (TILE_BMAX, FusedMLPKernel, check_accumulate, mlp_num_params, tile_supported,
+                             tile_window_ok, weighted_infer_stats)
 from ..ops.nn import BatchGather, bound_params, fold_batch_gather, join_side_work, unit_loss_seed
 from ..ops.optim import FlatAdam, adam_flat_, check_clip_args
 from ..parallel.dist import DistContext, init_native_comm
@@ -99,18 +100,33 @@ class FusedMLPEngine(_EngineBase):
     FUSED_UPDATE = True
 
     @staticmethod
-    def applicable(model, device: torch.device, batch_size: int) -> bool:
+    def applicable(model, device: torch.device, batch_size: int, accumulate: int = 1) -> bool:
         if device.type != "cuda" or not hasattr(model, "fused_spec"):
             return False
         spec = model.fused_spec()
+        if accumulate > 1:
+            # windows of micro-batches: only the batch-tiled trainer runs them - its shapes, any batch 1..1024,
+            # accumulate * ceil(batch / 32) slots within its cap
+            if (spec_weighted(spec) and spec["loss"] != "ce") or not tile_supported(spec["dims"]):
+                return False
+            return 1 <= batch_size <= TILE_BMAX and tile_window_ok(spec["dims"], batch_size, accumulate)
         if spec_weighted(spec):
             # class weights / label smoothing: only the batch-tiled trainer computes that loss, at any batch it takes
             return spec["loss"] == "ce" and tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
         return FusedMLPKernel.supported(spec["dims"], batch_size)
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,
-                 steps_per_launch: int = 0, use_graph: Optional[bool] = None, lr_schedule=None):
+                 steps_per_launch: int = 0, use_graph: Optional[bool] = None, lr_schedule=None,
+                 accumulate_grad_batches: int = 1):
         super().__init__(model, ctx, batch_size, seed)
+        # K = accumulate_grad_batches > 1: an optimizer step is a window of K micro-batches of B rows, one grid and one
+        # fold of the batch-tiled trainer (csrc/mlp_tile.hip), so the kernel is built on the tile plan whatever the
+        # batch.  Steps, losses, the device counters and the lr table count windows.  Under DDP the existing step path
+        # runs once per window (grad-mode launch -> RCCL or the peer all-reduce + Adam -> flat Adam, HIP-graph chunks
+        # included): one all-reduce per optimizer step, of the accumulated gradient; the tile plan has neither the
+        # in-kernel exchange nor update-then-grad.
+        self.K = check_accumulate(accumulate_grad_batches, "accumulate_grad_batches")
+        self.acc = dict(accumulate=self.K) if self.K > 1 else {}
         # trainer/lr_schedule.py LrSchedule or None: every launch that applies Adam - the persistent trainers (with
         # and without the in-kernel exchange), the update-then-grad kernel, flat Adam and the peer all-reduce + Adam
         # of the DDP step path - reads the step's rate from its device table at the device step count
@@ -123,8 +139,12 @@ class FusedMLPEngine(_EngineBase):
         # class-weighted / label-smoothed CE (models/mlp.py): the batch-tiled trainer's plan whatever the batch, and
         # the two arguments on every train launch; validation through the tiled inference kernel
         self.weighted = spec_weighted(spec)
-        bmax = TILE_BMAX if self.weighted else (4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
+        tiled = self.weighted or self.K > 1
+        bmax = TILE_BMAX if tiled else (4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
         self.kernel = FusedMLPKernel(self.dims, bmax=bmax)
+        if self.K > 1 and self.kernel.plan.trainer(self.B, accumulate=self.K) != "tile":
+            raise ValueError(f"accumulate_grad_batches={self.K} at batch {self.B}: over the batch-tiled trainer's "
+                             "slot cap (accumulate * ceil(batch / 32) <= 256)")
         self.P = mlp_num_params(self.dims)
         dev = ctx.device
         self.device = dev
@@ -287,7 +307,7 @@ class FusedMLPEngine(_EngineBase):
 
     def steps_per_epoch(self) -> int:
         n_local = math.ceil(len(self.train_rows) / self.ctx.world_size)
-        return math.ceil(n_local / self.B)
+        return math.ceil(n_local / (self.B * self.K))  # optimizer steps: windows of K batches
 
     def upload_epoch_indices(self, epoch: int, shuffle: bool = True) -> int:
         self.stage.zero_()  # staged batches refer to the previous index list
@@ -315,7 +335,7 @@ class FusedMLPEngine(_EngineBase):
                                            loss_out=loss_out, loss=self.loss, step_counter=self.step_counter,
                                            xg=self.xg, xg_timeout_s=getattr(self, "xg_timeout_s", 20.0),
                                            xg_ticks=getattr(self, "xg_ticks", None) if self.xg is not None else None,
-                                           lr_tab=tab, **self.wloss)
+                                           lr_tab=tab, **self.wloss, **self.acc)
             self._bound, self._bound_key = bl, key
         return bl
 
@@ -333,7 +353,9 @@ class FusedMLPEngine(_EngineBase):
         """Enqueue ``steps`` optimizer steps over batches [first_step, first_step+steps) of self.idx.
 
         loss_out is indexed by the absolute batch index (loss_out[first_step + s]) and must hold
-        first_step + steps entries (with DDP: the cross-rank mean loss).  No host synchronisation."""
+        first_step + steps entries (with DDP: the cross-rank mean loss).  No host synchronisation.
+        With accumulate_grad_batches = K > 1 a step is a window of K batches: steps, first_step and loss_out count
+        windows, and a window's loss is its last live micro-batch's."""
         fr = self._fast_run
         if (fr is not None and loss_out is fr[0] and n_items == fr[1] and 0 < steps and 0 <= first_step
                 and first_step + steps <= fr[2] and fr[3] is self._bound and loss_out.data_ptr() == fr[4]):
@@ -342,12 +364,13 @@ class FusedMLPEngine(_EngineBase):
             return
         if steps <= 0:
             return
-        if (first_step + steps - 1) * self.B >= n_items or loss_out.numel() < first_step + steps:
+        rows = self.B * self.K  # index entries per optimizer step
+        if (first_step + steps - 1) * rows >= n_items or loss_out.numel() < first_step + steps:
             raise ValueError("step range exceeds the epoch's batches / loss buffer")
         if not self.ddp or self.xg is not None:
             bl = self._bound_launch(n_items, loss_out)
             if not self.steps_per_launch:
-                self._fast_run = (loss_out, n_items, min(loss_out.numel(), -(-n_items // self.B)), bl,
+                self._fast_run = (loss_out, n_items, min(loss_out.numel(), -(-n_items // rows)), bl,
                                   loss_out.data_ptr())
             chunk = self.steps_per_launch or steps
             s = 0
@@ -400,7 +423,7 @@ class FusedMLPEngine(_EngineBase):
         self.kernel.train(self.p, None, None, self.X, self.Y, self.idx, n_items=n_items, batch=self.B, steps=1,
                           t0=0, lr=a["lr"], dropout=self.dropout, seed=self.rank_seed, loss=self.loss,
                           grad_out=self.gbuf, step_counter=self.step_counter, cursor=self.cursor,
-                          loss_out=loss_out, **self.wloss)
+                          loss_out=loss_out, **self.wloss, **self.acc)
         if self.gx is not None:
             from ..parallel.xgmi import allreduce_adam_
 
@@ -453,7 +476,7 @@ class FusedMLPEngine(_EngineBase):
 
     def train_epoch(self, epoch: int, shuffle: bool = True) -> torch.Tensor:
         n_items = self.upload_epoch_indices(epoch, shuffle)
-        steps = math.ceil(n_items / self.B)
+        steps = math.ceil(n_items / (self.B * self.K))
         loss_out = getattr(self, "_loss_buf", None)
         if loss_out is None or loss_out.numel() < steps:
             self._loss_buf = loss_out = torch.zeros(max(1, steps), dtype=torch.float32, device=self.device)
@@ -592,10 +615,20 @@ class AutogradEngine(_EngineBase):
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, bucket_cap_bytes: int = 8 << 20,
                  first_bucket_bytes: int = 1 << 20, gradient_clip_val: Optional[float] = None,
-                 gradient_clip_algorithm: str = "norm", optimizers=None):
+                 gradient_clip_algorithm: str = "norm", optimizers=None, accumulate_grad_batches: int = 1):
         """``optimizers``: the model's configure_optimizers() result when the caller already has it (the Trainer, so
-        that optimizer and lr scheduler are created once); None calls it here."""
+        that optimizer and lr scheduler are created once); None calls it here.
+
+        ``accumulate_grad_batches`` = K > 1 (Lightning's automatic optimization): ``train_step`` is called once per
+        micro-batch; gradients are zeroed at a window's first micro-batch only, every micro-batch's mean loss is
+        backpropagated with the seed 1 / K, and the bucket reducer (one all-reduce per optimizer step: ``no_sync`` on
+        the others), clipping, the optimizer and the scheduler hooks run only on the micro-batch that closes the window
+        (``(batch_idx + 1) % K == 0``, or the epoch's last) - ``self.stepped`` tells the caller, and ``global_step``
+        counts optimizer steps.  Such steps run eagerly: neither the captured step graph nor the device loop."""
         super().__init__(model, ctx, batch_size, seed)
+        self.K = check_accumulate(accumulate_grad_batches, "accumulate_grad_batches")
+        self.stepped = True  # the last train_step applied the optimizer (always, without accumulation)
+        self._sync = True    # the gradient hooks hand buckets to the reducer (off while a window accumulates)
         # gradient clipping (Trainer(gradient_clip_val, gradient_clip_algorithm)): after the all-reduce, on the
         # averaged gradient, inside the flat Adam - p.grad keeps the unclipped gradient (ops/optim.py)
         self.clip_val, self.clip_algorithm = check_clip_args(gradient_clip_val, gradient_clip_algorithm)
@@ -665,7 +698,8 @@ class AutogradEngine(_EngineBase):
         if dev.type == "cuda" and os.environ.get("DCT_PHASE_TIMING", "0") == "1":
             from ..utils.tracing import DevicePhaseTimer
 
-            self.phase_timer = DevicePhaseTimer(["fwd", "bwd", "allreduce", "opt"], dev)
+            if self.K == 1:  # (an accumulating micro-batch has no all-reduce / optimizer phase to mark)
+                self.phase_timer = DevicePhaseTimer(["fwd", "bwd", "allreduce", "opt"], dev)
         opt = model.configure_optimizers() if optimizers is None else optimizers
         torch_opt, sched_cfg = parse_configure_optimizers(opt)  # (parsed once: ValueError for what is not supported)
         hp = adam_hparams_of(torch_opt)
@@ -716,7 +750,8 @@ class AutogradEngine(_EngineBase):
 
     def _make_hook(self, i):
         def hook(_p):
-            self.reducer.mark_ready(i)
+            if self._sync:
+                self.reducer.mark_ready(i)
         return hook
 
     def attach_data(self, X: torch.Tensor, Y: torch.Tensor, train_rows: torch.Tensor, val_rows: torch.Tensor):
@@ -726,7 +761,7 @@ class AutogradEngine(_EngineBase):
         self.val_rows = val_rows.to(torch.int64)
 
     def steps_per_epoch(self) -> int:
-        return math.ceil(math.ceil(len(self.train_rows) / self.ctx.world_size) / self.B)
+        return math.ceil(math.ceil(len(self.train_rows) / self.ctx.world_size) / (self.B * self.K))
 
     def _zero_grads(self):
         if self.flat_g.is_cuda:
@@ -743,7 +778,8 @@ class AutogradEngine(_EngineBase):
         fill kernel per step (~4.5 us in the captured TabTransformer step on MI355X)."""
         one = getattr(self, "_one_seed", None)
         if one is None or one.device != loss.device or one.dtype != loss.dtype or one.shape != loss.shape:
-            one = self._one_seed = torch.ones_like(loss)
+            # (accumulate_grad_batches = K: every micro-batch's loss counts 1 / K)
+            one = self._one_seed = torch.ones_like(loss) if self.K == 1 else torch.full_like(loss, 1.0 / self.K)
         loss.backward(one)
         join_side_work()  # weight-gradient GEMMs issued on the side stream (ops/nn.py side_dw)
 
@@ -755,21 +791,30 @@ class AutogradEngine(_EngineBase):
             if i == 4:
                 self.phase_timer.close()
 
-    def _step_body(self, x, y, batch_idx: int):
-        self._zero_grads()
-        if self.reducer is not None:
+    def _step_body(self, x, y, batch_idx: int, first: bool = True, step: bool = True):
+        """One micro-batch.  ``first``: it opens its optimizer step (gradients are zeroed); ``step``: it closes it
+        (reducer, clipping, optimizer, scheduler).  Both hold for every batch without accumulation."""
+        if first:
+            self._zero_grads()
+        self._sync = step
+        if self.reducer is not None and step:
             self.reducer.prepare()
         self._pm(0)
         self.model.train()
         # the step's backward root is training_step's loss with a seed of exactly 1 (_backward): a fused
-        # classifier head may compute its backward inside the forward launch (ops/nn.py unit_loss_seed)
-        with self._bound(), unit_loss_seed():
+        # classifier head may compute its backward inside the forward launch (ops/nn.py unit_loss_seed);
+        # an accumulating step seeds 1 / K instead
+        with self._bound(), (unit_loss_seed() if self.K == 1 else contextlib.nullcontext()):
             loss = self.model.training_step((x, y), batch_idx)
             if isinstance(loss, dict):
                 loss = loss["loss"]
             self._pm(1)
             self._backward(loss)
         self._pm(2)
+        if not step:
+            return loss
+        if self.K > 1:
+            batch_idx = batch_idx // self.K  # the scheduler hook below counts optimizer steps
         if self.reducer is not None:
             self.reducer.finalize()
             assert_reducer_complete(self.reducer)
@@ -799,12 +844,22 @@ class AutogradEngine(_EngineBase):
         st = getattr(self, "_torch_clip_stats", None)
         return (float(st[0]), float(st[1])) if st is not None else (float("nan"), 1.0)
 
-    def train_step(self, rows: torch.Tensor, batch_idx: int):
+    def train_step(self, rows: torch.Tensor, batch_idx: int, is_last: bool = False):
         """One optimizer step.  ``last_step_mode`` tells the Trainer how training_step ran:
         ``eager``; ``captured`` (traced into the step graph, then replayed - the tensors it logged
-        are the graph's static outputs); ``replayed`` (training_step and self.log did NOT run)."""
+        are the graph's static outputs); ``replayed`` (training_step and self.log did NOT run).
+
+        With accumulate_grad_batches = K > 1: one micro-batch, ``batch_idx`` its index in the rank's epoch and
+        ``is_last`` set on the epoch's last one; the optimizer steps when ``(batch_idx + 1) % K == 0 or is_last``
+        (``self.stepped``), always eagerly.  Returns the micro-batch's own (unscaled) loss."""
         rows_d = rows.to(self.device)
         self.last_step_mode = "eager"
+        if self.K > 1:
+            self.stepped = (batch_idx + 1) % self.K == 0 or bool(is_last)
+            loss = self._step_body(self.X[rows_d], self.Y[rows_d], batch_idx, first=batch_idx % self.K == 0,
+                                   step=self.stepped)
+            self.global_step += int(self.stepped)
+            return loss.detach()
         if self._graph_ok(rows_d.numel()):
             self.last_step_mode = "replayed" if getattr(self, "_graph", None) is not None else "captured"
             loss = self._graph_step(rows_d, batch_idx)
@@ -885,7 +940,7 @@ class AutogradEngine(_EngineBase):
     # csrc/optim.hip).  Replaces, per step: host batch slicing, two index_selects, a counter add,
     # a zero kernel and the loss copy.
     def device_loop_ok(self) -> bool:
-        return (self.device.type == "cuda" and self.optimizer is not None and self.X.dim() == 2
+        return (self.K == 1 and self.device.type == "cuda" and self.optimizer is not None and self.X.dim() == 2
                 and self.X.shape[1] % 4 == 0 and os.environ.get("DCT_GRAPH", "1") != "0"
                 and not getattr(self, "_graph_failed", False))
 

@@ -29,6 +29,7 @@ from ..ckpt.callbacks import LearningRateMonitor, ModelCheckpoint
 from ..ckpt.lightning_io import build_checkpoint, load_checkpoint, save_checkpoint
 from ..data.dataset import dataset_tensors
 from ..data.sampler import distributed_indices
+from ..ops.fused_mlp import check_accumulate
 from ..ops.optim import check_clip_args
 from ..parallel.dist import DistContext, init_distributed, shutdown
 from .engines import AutogradEngine, FusedMLPEngine, adam_hparams_of
@@ -70,10 +71,16 @@ class Trainer:
                  log_every_n_steps: int = 50, num_sanity_val_steps: int = 2, engine: str = "auto",
                  steps_per_launch: int = 0, enable_progress_bar: bool = True, default_root_dir: Optional[str] = None,
                  max_steps: int = -1, fault_inject: Optional[Tuple[int, int]] = None, verbose: bool = True,
-                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm"):
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
+                 accumulate_grad_batches: int = 1):
         # Lightning's two arguments: None or 0 is off; ValueError for a negative value or an unknown algorithm
         self.gradient_clip_val, self.gradient_clip_algorithm = check_clip_args(gradient_clip_val,
                                                                                gradient_clip_algorithm)
+        # Lightning's accumulate_grad_batches (an int >= 1; ValueError otherwise): the optimizer steps after batch b of a
+        # rank's epoch when (b + 1) % K == 0 or b is the last, on (1 / K) * the sum of the window's micro-batch
+        # gradients; global_step, max_steps, logging, schedulers and checkpoints count optimizer steps, and the logged
+        # train_loss is the window's last micro-batch's
+        self.accumulate_grad_batches = check_accumulate(accumulate_grad_batches, "accumulate_grad_batches")
         self.max_epochs = int(max_epochs)
         self.max_steps = int(max_steps)
         self.accelerator = accelerator
@@ -249,17 +256,31 @@ class Trainer:
         if self.gradient_clip_val is not None and choice == "fused":
             raise RuntimeError("engine='fused' cannot clip gradients: the persistent small-MLP kernels apply Adam "
                                "inside the launch (use engine='auto', 'graph' or 'autograd' with gradient_clip_val)")
-        fused_ok = adam is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size)
+        # accumulate_grad_batches = K > 1: the fused engine where the batch-tiled trainer takes the model, the batch and
+        # the window (also at batch > 16: the graph engine's wide-MLP executor does not accumulate), otherwise autograd.
+        # The keyword reaches an engine's constructor only then, as **sched does
+        K = self.accumulate_grad_batches
+        acc = dict(accumulate_grad_batches=K) if K > 1 else {}
+        if K > 1 and choice == "graph":
+            raise RuntimeError("engine='graph' cannot accumulate gradients: the wide-MLP executor runs one batch per "
+                               "optimizer step (use engine='auto', 'fused' or 'autograd' with accumulate_grad_batches)")
+        if K > 1:
+            fused_ok = adam is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size, K)
+        else:
+            fused_ok = adam is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size)
         if self.gradient_clip_val is not None:
             fused_ok = False  # clipping: the graph engine where it applies, otherwise autograd
-        if choice == "auto" and fused_ok and batch_size > 16 and GraphMLPEngine.applicable(model, ctx.device, batch_size):
+        if (choice == "auto" and fused_ok and batch_size > 16 and K == 1
+                and GraphMLPEngine.applicable(model, ctx.device, batch_size)):
             fused_ok = False  # batch > 16: the graph engine keeps the models it takes; the batch-tiled trainer the rest
         if choice in ("auto", "fused") and fused_ok:
             sched = dict(lr_schedule=LrSchedule.from_config(torch_opt, sched_cfg)) if sched_cfg is not None else {}
-            return FusedMLPEngine(model, ctx, batch_size, seed, adam, steps_per_launch=self.steps_per_launch, **sched)
+            return FusedMLPEngine(model, ctx, batch_size, seed, adam, steps_per_launch=self.steps_per_launch, **sched,
+                                  **acc)
         if choice == "fused":
             raise RuntimeError("engine='fused' requested but the model/device/batch is not supported by it")
-        if choice in ("auto", "graph") and adam is not None and GraphMLPEngine.applicable(model, ctx.device, batch_size):
+        if (choice in ("auto", "graph") and K == 1 and adam is not None
+                and GraphMLPEngine.applicable(model, ctx.device, batch_size)):
             sched = dict(lr_schedule=LrSchedule.from_config(torch_opt, sched_cfg)) if sched_cfg is not None else {}
             return GraphMLPEngine(model, ctx, batch_size, seed, adam, self.strategy.bucket_cap_bytes,
                                   self.strategy.first_bucket_bytes, **clip, **sched)
@@ -269,7 +290,7 @@ class Trainer:
         # (with a scheduler the engine takes this call's optimizer and scheduler: they belong together)
         opts = dict(optimizers=optimizers) if sched_cfg is not None else {}
         return AutogradEngine(model, ctx, batch_size, seed, self.strategy.bucket_cap_bytes,
-                              self.strategy.first_bucket_bytes, **clip, **opts)
+                              self.strategy.first_bucket_bytes, **clip, **opts, **acc)
 
     # ------------------------------------------------------------------ checkpoints
     def _checkpoint_dict(self, batches_in_epoch: int = 0, val_batches: int = 0) -> Dict[str, Any]:
@@ -480,17 +501,25 @@ class Trainer:
             return n
         local = eng.epoch_local_indices(len(eng.train_rows), epoch, shuffle)
         rows_all = eng.train_rows[local]
-        n_steps = math.ceil(len(rows_all) / B)
+        n_batches = math.ceil(len(rows_all) / B)
+        # accumulate_grad_batches = K: the loop runs micro-batches, everything below `continue` runs per optimizer step
+        K = self.accumulate_grad_batches
+        n_steps = math.ceil(n_batches / K)
         first = self.global_step
         if sched is not None:
             # (max_steps ends the epoch early: a step-interval scheduler is advanced by the steps that run)
             n_fill = n_steps if self.max_steps <= 0 else max(1, min(n_steps, self.max_steps - first))
             sched.begin_epoch(first, n_fill, device=eng.device)
-        for bi in range(n_steps):
+        for bi in range(n_batches):
             rows = rows_all[bi * B: (bi + 1) * B]
             self._cur_batch_size = len(rows)
             self._step_logs = {}
-            loss = eng.train_step(rows, bi)
+            if K > 1:
+                loss = eng.train_step(rows, bi, is_last=bi == n_batches - 1)
+                if not eng.stepped:
+                    continue  # Lightning logs nothing while accumulating: the step's logs are its last micro-batch's
+            else:
+                loss = eng.train_step(rows, bi)
             mode = getattr(eng, "last_step_mode", "eager")
             if mode == "captured":
                 # what training_step logged while it was traced into the step graph are the graph's

@@ -40,6 +40,8 @@ def parse_args(argv=None):
                    help="clip gradients before the optimizer step (default: no clipping)")
     p.add_argument("--gradient-clip-algorithm", default=cfg.optim.gradient_clip_algorithm, choices=("norm", "value"),
                    help="norm: global L2 norm (clip_grad_norm_); value: element-wise (clip_grad_value_)")
+    p.add_argument("--accumulate-grad-batches", type=int, default=cfg.optim.accumulate_grad_batches,
+                   help="micro-batches per optimizer step: the step applies the mean of their gradients (default 1)")
     p.add_argument("--model", default=cfg.model.name)
     p.add_argument("--class-weight", default=cfg.model.class_weight,
                    help="cross-entropy class weights: 'balanced' (n / (C * count_c) over the training split) or "
@@ -116,6 +118,7 @@ def main(argv=None) -> int:
         engine=a.engine,
         gradient_clip_val=a.gradient_clip_val,
         gradient_clip_algorithm=a.gradient_clip_algorithm,
+        accumulate_grad_batches=a.accumulate_grad_batches,
     )
     last = os.path.join(a.model_dir, "last.ckpt")
     # --resume, or a torchrun elastic restart after a failed rank: continue from last.ckpt
