@@ -477,7 +477,10 @@ static bool attn_mfma(bool bwd, const uint16_t* q, const uint16_t* k, const uint
                       uint16_t* dv, int Bsz, int H, int T, int D, int ldq, int ldo, float scale, hipStream_t st,
                       hipError_t* err) {
   if (T % 16 || D % 16 || T > 64 || !(D == 16 || D == 32 || D == 64)) return false;
-  if (ldq % 4 || ldo % 4 || ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)dout)) & 7)) return false;
+  // (o and dout are null in the forward; the backward reads both with 8-byte loads)
+  if (ldq % 4 || ldo % 4 ||
+      ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)o) | ((uintptr_t)dout)) & 7))
+    return false;
   const int BH = Bsz * H, DT = D / 16;
   switch (T / 16) {
     case 1: *err = attn_mfma_d<1>(DT, bwd, q, k, v, o, dout, lse_in, lse_out, out0, dk, dv, BH, H, ldq, ldo, scale, st); break;

@@ -523,8 +523,10 @@ int dct_bias_act_bwd(const void* dY, const void* act_aux, uint16_t* dZ, float* d
   return (int)hipGetLastError();
 }
 
-static int ln_lpr(int N, const void* a, const void* b2, const void* c) {
-  if (N % 4 || N > 256 || ((((uintptr_t)a) | ((uintptr_t)b2) | ((uintptr_t)c)) & 15)) return 0;
+// lanes per row of the narrow kernels, 0 when they cannot take the call: every operand they touch
+// with 16-byte accesses goes through here (a null optional operand passes)
+static int ln_lpr(int N, const void* a, const void* b2, const void* c, const void* d) {
+  if (N % 4 || N > 256 || ((((uintptr_t)a) | ((uintptr_t)b2) | ((uintptr_t)c) | ((uintptr_t)d)) & 15)) return 0;
   int l = 1;
   while (l * 4 < N) l <<= 1;
   return l;
@@ -535,7 +537,7 @@ int dct_layernorm_fwd(const void* x, const float* w, const float* b, void* y, fl
   if (N > 64 * dct::LN_MAX) return (int)hipErrorInvalidValue;
   if (M <= 0) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (const int lpr = ln_lpr(N, x, y, w)) {
+  if (const int lpr = ln_lpr(N, x, y, w, b)) {
     const int rows_per_block = 4 * (64 / lpr);
     const int grid = grid_cap((M + rows_per_block - 1) / rows_per_block, 1, 4096);
 #define LNF(L) hipLaunchKernelGGL(dct::layernorm_fwd_small<L>, dim3(grid), dim3(256), 0, st, x, w, b, y, mean, rstd, M, N, eps, in_bf16, out_bf16)
@@ -553,7 +555,7 @@ int dct_layernorm_bwd_ex(const void* dy, int dy_bf16, const void* x, int x_bf16,
                          const float* rstd, void* dx, int dx_bf16, uint16_t* dx2, const float* dres, float* dw,
                          float* db, float* ws, int M, int N, void* stream) {
   if (M <= 0) return 0;
-  const int lpr = ln_lpr(N, dy, x, dx);
+  const int lpr = ln_lpr(N, dy, x, dx, w);
   if (!lpr || !ws || (dres && (((uintptr_t)dres) & 15)) || (dx2 && (((uintptr_t)dx2) & 7)))
     return (int)hipErrorInvalidValue;
   dct::LnBwdArgs a{dy, x, w, mean, rstd, dx, dx2, dres, dw, db, ws, M, N, dy_bf16, x_bf16, dx_bf16};
