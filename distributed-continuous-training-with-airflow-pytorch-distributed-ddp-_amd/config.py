@@ -61,11 +61,14 @@ class ModelConfig:
 
 @dataclass
 class OptimConfig:
-    name: str = "adam"
+    name: str = "adam"  # adam | adamw | sgd (MLP family: models/mlp.py configure_optimizers)
     lr: float = 0.01  # :88
     betas: Sequence[float] = (0.9, 0.999)
     eps: float = 1e-8
     weight_decay: float = 0.0
+    momentum: float = 0.0  # SGD
+    dampening: float = 0.0  # SGD
+    nesterov: bool = False  # SGD
     gradient_clip_val: Optional[float] = None  # Trainer(gradient_clip_val): None or 0 = no clipping
     gradient_clip_algorithm: str = "norm"  # norm (global L2 norm, clip_grad_norm_) | value (clip_grad_value_)
     accumulate_grad_batches: int = 1  # Trainer(accumulate_grad_batches): micro-batches per optimizer step
@@ -206,6 +209,17 @@ class PipelineConfig:
             else:
                 d = yaml.safe_load(f)
         return cls.from_dict(d)
+
+
+def optimizer_kwargs(optim: "OptimConfig") -> Dict[str, Any]:
+    """The MLP family's optimizer keywords (models/mlp.py MLPClassifier) an OptimConfig asks for: only what differs
+    from the reference's plain Adam, so a default config builds the model with no extra argument."""
+    from .models.mlp import OPTIM_DEFAULTS
+
+    want = dict(optimizer=str(optim.name).lower(), weight_decay=float(optim.weight_decay),
+                momentum=float(optim.momentum), dampening=float(optim.dampening), nesterov=bool(optim.nesterov),
+                betas=tuple(float(b) for b in optim.betas), eps=float(optim.eps))
+    return {k: v for k, v in want.items() if v != OPTIM_DEFAULTS[k]}
 
 
 def parse_class_weight(text) -> Any:

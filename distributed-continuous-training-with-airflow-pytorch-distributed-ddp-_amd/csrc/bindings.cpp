@@ -70,11 +70,19 @@ struct MlpPlan {
 };
 
 
+// MlpArgs::opt_kind of an optimizer's name
+static int optimizer_kind(const std::string& name) {
+  if (name == "adam") return dct::MLP_OPT_ADAM;
+  if (name == "adamw") return dct::MLP_OPT_ADAMW;
+  if (name == "sgd") return dct::MLP_OPT_SGD;
+  throw std::invalid_argument("optimizer must be 'adam', 'adamw' or 'sgd', got '" + name + "'");
+}
+
 // The key of a described launch (MlpPlan.trainer): what mlp_launch_key would derive from its arguments,
 // with every buffer the description implies bound.
 static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, int rank, int loss_kind, bool prof,
                                    bool cursor, bool stage, bool pending, bool aligned, bool weighted,
-                                   int accumulate) {
+                                   int accumulate, const std::string& optimizer = "adam") {
   dct::MlpLaunchKey k{};
   k.B = batch; k.mode = mode; k.steps = steps; k.loss_kind = loss_kind;
   k.xg_world = world; k.xg_rank = rank;
@@ -85,6 +93,7 @@ static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, in
   k.p_aligned = k.mv_aligned = aligned;
   k.weighted = weighted;
   k.accum = accumulate > 1 ? accumulate : 0;
+  k.other_opt = mode == 0 && optimizer_kind(optimizer) != dct::MLP_OPT_ADAM;
   return k;
 }
 
@@ -96,7 +105,8 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
                                     uintptr_t step_counter, uintptr_t cursor, uintptr_t prof, uintptr_t pending,
                                     uintptr_t stage, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
                                     uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t class_w = 0,
-                                    float label_smooth = 0.f, int accum = 1) {
+                                    float label_smooth = 0.f, int accum = 1, const std::string& optimizer = "adam",
+                                    float momentum = 0.f, float dampening = 0.f, bool nesterov = false) {
   if (!plan.supported) throw std::runtime_error("MLP too large for the fused kernel");
   if (steps < 1 || n_items < 1 || B < 1) throw std::invalid_argument("empty launch");
   if (accum < 1) throw std::invalid_argument("accumulate must be >= 1");
@@ -147,6 +157,19 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
     throw std::invalid_argument("class weights / label smoothing: cross-entropy only");
   a.class_w = P<const float>(class_w);
   a.label_smooth = label_smooth;
+  // the optimizer of a train-mode launch (grad mode applies none: its launches keep the Adam key)
+  a.opt_kind = optimizer_kind(optimizer);
+  if (mode == 0 && a.opt_kind != dct::MLP_OPT_ADAM) {
+    if (!(wd >= 0.f)) throw std::invalid_argument("weight_decay must be >= 0");
+    if (a.opt_kind == dct::MLP_OPT_SGD) {
+      if (!(momentum >= 0.f)) throw std::invalid_argument("momentum must be >= 0");
+      if (nesterov && (momentum <= 0.f || dampening != 0.f))
+        throw std::invalid_argument("Nesterov momentum requires a momentum and zero dampening");
+      a.momentum = momentum; a.dampening = dampening; a.nesterov = nesterov ? 1 : 0;
+    }
+  } else {
+    a.opt_kind = dct::MLP_OPT_ADAM;
+  }
   // a request no trainer of this plan serves is an invalid argument; a chosen trainer's own refusal of
   // the arguments surfaces in launch_train
   const dct::MlpChoice c = plan.select(dct::mlp_launch_key(a));
@@ -286,35 +309,36 @@ PYBIND11_MODULE(_dct_native, m) {
       // the trainer a launch of this description reaches: "wave_single", "wave_rows", "block5", "block5_b8",
       // "block3", "lds", "tile" or "none".  `aligned`: the flat buffers lie on 16-byte boundaries; `weighted`: class
       // weights or label smoothing are on (the batch-tiled trainer's plan only); `accumulate`: micro-batches per
-      // optimizer step (> 1: the batch-tiled trainer's plan only, within its slot cap).  No device needed.
+      // optimizer step (> 1: the batch-tiled trainer's plan only, within its slot cap); `optimizer`: "adam", "adamw"
+      // or "sgd" (a train-mode launch of the last two: the batch-tiled trainer's plan only).  No device needed.
 #define MLP_QUERY_ARGS                                                                                              \
   py::arg("batch"), py::arg("mode") = 0, py::arg("steps") = 1, py::arg("world") = 1, py::arg("rank") = 0,           \
       py::arg("loss_kind") = 0, py::arg("prof") = false, py::arg("cursor") = false, py::arg("stage") = false,       \
       py::arg("pending") = false, py::arg("aligned") = true, py::arg("weighted") = false,                           \
-      py::arg("accumulate") = 1
+      py::arg("accumulate") = 1, py::arg("optimizer") = "adam"
       .def("trainer", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
                          bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted,
-                         int accumulate) {
+                         int accumulate, const std::string& optimizer) {
         return std::string(dct::mlp_trainer_name(
             plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
-                                  weighted, accumulate))
+                                  weighted, accumulate, optimizer))
                 .trainer));
       }, MLP_QUERY_ARGS)
       // whether that launch reads its staged-batch buffer (the wave kernels and mlp_block5's grad mode do)
       .def("uses_stage", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
                             bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted,
-                            int accumulate) {
+                            int accumulate, const std::string& optimizer) {
         return plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
-                                     weighted, accumulate))
+                                     weighted, accumulate, optimizer))
             .use_stage;
       }, MLP_QUERY_ARGS)
       // one trainer's own predicate on that launch, whatever the selector would choose first (tests): "block5",
       // "block5_xg", "block3", "wave_rows", "wave_xg"
       .def("takes", [](const MlpPlan& plan, const std::string& which, int batch, int mode, int steps, int world,
                        int rank, int loss_kind, bool prof, bool cursor, bool stage, bool pending, bool aligned,
-                       bool weighted, int accumulate) {
+                       bool weighted, int accumulate, const std::string& optimizer) {
         const dct::MlpLaunchKey k = query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending,
-                                              aligned, weighted, accumulate);
+                                              aligned, weighted, accumulate, optimizer);
         const dct::MlpShape& sh = *plan.sh();
         if (which == "block5") return dct::mlp_block5_takes(sh, k);
         if (which == "block5_xg") return dct::mlp_block5_xg_shape_ok(sh, k);
@@ -332,13 +356,15 @@ PYBIND11_MODULE(_dct_native, m) {
              int loss_kind, uintptr_t step_counter, uintptr_t cursor, uintptr_t prof, uintptr_t pending,
              uintptr_t stage, uintptr_t stream, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
              uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t tile_ws, int64_t tile_ws_floats,
-             uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate) {
+             uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate, const std::string& optimizer,
+             float momentum, float dampening, bool nesterov) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             dct::MlpArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
                                                    b1, b2, eps, wd, dropout, seed, step_base, loss_out, mode,
                                                    loss_kind, step_counter, cursor, prof, pending, stage, xg_recv,
                                                    xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll,
-                                                   class_w, label_smooth, accumulate);
+                                                   class_w, label_smooth, accumulate, optimizer, momentum,
+                                                   dampening, nesterov);
             a.tile_ws = P<float>(tile_ws);
             a.tile_ws_floats = tile_ws_floats;
             a.lr_tab = P<const float>(lr_tab);
@@ -352,7 +378,9 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("stream") = 0, py::arg("xg_recv") = 0, py::arg("xg_peers") = 0, py::arg("xg_world") = 0,
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL, py::arg("xg_poll") = 0,
           py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0, py::arg("lr_tab") = (uintptr_t)0,
-          py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f, py::arg("accumulate") = 1)
+          py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f, py::arg("accumulate") = 1,
+          py::arg("optimizer") = "adam", py::arg("momentum") = 0.f, py::arg("dampening") = 0.f,
+          py::arg("nesterov") = false)
       .def(
           "prepare_train",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t X, int ldx, uintptr_t Y,
@@ -360,13 +388,14 @@ PYBIND11_MODULE(_dct_native, m) {
              uint32_t seed, uintptr_t loss_out, int64_t loss_len, int loss_kind, uintptr_t step_counter,
              uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank, uintptr_t xg_status,
              int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks, uintptr_t tile_ws, int64_t tile_ws_floats,
-             uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate) {
+             uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate, const std::string& optimizer,
+             float momentum, float dampening, bool nesterov) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             auto l = std::make_unique<MlpLaunch>(MlpLaunch{plan});
             l->base = make_train_args(plan, p, mo, vo, 0, X, ldx, Y, idx, n_items, B, 1, 0, lr, b1, b2, eps, wd,
                                       dropout, seed, 0, loss_out, 0, loss_kind, step_counter, 0, 0, 0, 0, xg_recv,
                                       xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll, class_w,
-                                      label_smooth, accumulate);
+                                      label_smooth, accumulate, optimizer, momentum, dampening, nesterov);
             l->base.xg_ticks = P<unsigned long long>(xg_ticks);
             l->base.tile_ws = P<float>(tile_ws);
             l->base.tile_ws_floats = tile_ws_floats;
@@ -382,7 +411,8 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("xg_rank") = 0, py::arg("xg_status") = 0, py::arg("xg_timeout") = 200000000LL,
           py::arg("xg_poll") = 0, py::arg("xg_ticks") = 0, py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0,
           py::arg("lr_tab") = (uintptr_t)0, py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f,
-          py::arg("accumulate") = 1)
+          py::arg("accumulate") = 1, py::arg("optimizer") = "adam", py::arg("momentum") = 0.f,
+          py::arg("dampening") = 0.f, py::arg("nesterov") = false)
       .def(
           "eval",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items,
@@ -418,6 +448,21 @@ PYBIND11_MODULE(_dct_native, m) {
       py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("p_bf16"), py::arg("n"), py::arg("lr"),
       py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("t"), py::arg("grad_scale"),
       py::arg("decoupled"), py::arg("step_counter"), py::arg("stream"), py::arg("lr_tab") = (uintptr_t)0);
+  m.def("sgd_flat_step",
+        [](uintptr_t p, uintptr_t g, uintptr_t mo, int64_t n, float lr, float momentum, float dampening, bool nesterov,
+           float wd, int64_t t, float grad_scale, uintptr_t step_counter, uintptr_t cursor, uintptr_t loss_slot,
+           uintptr_t loss_out, int loss_cap, uintptr_t stream, uintptr_t lr_tab) {
+          check(dct_sgd_flat_step(P<float>(p), P<const float>(g), P<float>(mo), n, lr, momentum, dampening,
+                                  nesterov ? 1 : 0, wd, t, grad_scale, P<const int>(step_counter), P<int>(cursor),
+                                  P<const float>(loss_slot), P<float>(loss_out), loss_cap, P<const float>(lr_tab),
+                                  reinterpret_cast<void*>(stream)),
+                "sgd_flat_step");
+        },
+        py::arg("p"), py::arg("g"), py::arg("m"), py::arg("n"), py::arg("lr"), py::arg("momentum"),
+        py::arg("dampening"), py::arg("nesterov"), py::arg("wd"), py::arg("t"), py::arg("grad_scale"),
+        py::arg("step_counter") = (uintptr_t)0, py::arg("cursor") = (uintptr_t)0, py::arg("loss_slot") = (uintptr_t)0,
+        py::arg("loss_out") = (uintptr_t)0, py::arg("loss_cap") = 0, py::arg("stream") = (uintptr_t)0,
+        py::arg("lr_tab") = (uintptr_t)0);
   m.def("xg_adam_buffer_bytes", &dct_xg_adam_buffer_bytes, py::arg("n"), py::arg("world"));
   m.def(
       "xg_allreduce_adam",

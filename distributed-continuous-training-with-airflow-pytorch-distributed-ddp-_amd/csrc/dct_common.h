@@ -43,6 +43,21 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 // per call, which was ~40 % of a 2.3 us single-wave optimizer step.)
 __device__ __forceinline__ float pow_t(float log2b, float t) { return __builtin_amdgcn_exp2f(t * log2b); }
 
+// torch.optim.SGD (maximize=False) on one element, in torch's operation order: g += wd p; with momentum mu != 0 the
+// buffer is g itself on the first step (torch has no buffer yet: what `buf` held is ignored) and mu buf + (1 - damp) g
+// afterwards, and the step direction is g + mu buf (Nesterov) or buf; p -= lr g.  mu == 0 leaves `buf` alone.
+// Shared by the batch-tiled trainer's fold (mlp_tile.hip) and the flat step (optim.hip).
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, float lr, float mu, float damp, float wd,
+                                         bool nesterov, bool first) {
+  g += wd * p;
+  if (mu != 0.f) {
+    const float b = first ? g : mu * buf + (1.f - damp) * g;
+    buf = b;
+    g = nesterov ? g + mu * b : b;
+  }
+  p -= lr * g;
+}
+
 // erf(x) by Abramowitz-Stegun 7.1.26 (|err| < 6e-7 in fp32) on one v_rcp_f32 + one v_exp_f32,
 // given e = exp(-x^2).  The ocml erff is ~44 VALU ops with range branches; GEMM epilogues that
 // apply GELU to every output element were bound by it.

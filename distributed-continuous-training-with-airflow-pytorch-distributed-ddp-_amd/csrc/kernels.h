@@ -249,6 +249,15 @@ int dct_adam_flat_step_parts_lr(float* p, const float* g, float* m, float* v, ui
                                 const int* step_counter, int* cursor, const float* loss_slot, float* loss_out,
                                 int loss_cap, int nparts, const int64_t* part_off, const int64_t* part_n,
                                 const float* const* part, const int* part_splits, const float* lr_tab, void* stream);
+// Flat SGD over [0, n) (optim.hip; torch.optim.SGD, maximize=False): g scaled by grad_scale, += wd p; momentum != 0:
+// m = g on the first step (whatever m held), else momentum m + (1 - dampening) g, and the direction g + momentum m
+// (nesterov) or m; p -= lr direction.  Step count, rate table, step epilogue and alignment as dct_adam_flat_step_lr:
+// host t (first step: t == 1) or the device step_counter, which already includes this step (first: 1; the table's
+// entry for counter - 1).  m is not read when momentum == 0 and may be null.  hipErrorInvalidValue: momentum or wd
+// < 0, nesterov without momentum or with dampening, a misaligned p / g / m, a table without step_counter.
+int dct_sgd_flat_step(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,
+                      int nesterov, float wd, int64_t t, float grad_scale, const int* step_counter, int* cursor,
+                      const float* loss_slot, float* loss_out, int loss_cap, const float* lr_tab, void* stream);
 int dct_f32_to_bf16(const float* in, uint16_t* out, int64_t n, void* stream);
 // device-side barrier of the xGMI peer exchange (step_kernels.hip; barrier slots at byte offset off)
 int dct_xg_barrier(void* recv, void* const* peers, int64_t off, unsigned* status, int world, int rank, unsigned tag,

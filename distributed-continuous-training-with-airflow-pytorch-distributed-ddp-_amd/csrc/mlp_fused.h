@@ -52,7 +52,10 @@ struct MlpShape {
                   // the process-wide knob struct
 };
 
-struct MlpArgs {
+// MlpStepArgs: a launch's arguments up to the optimizer's own fields - what MlpArgs was before AdamW / SGD, field for
+// field.  MlpArgs (below) appends those; the batch-tiled trainer's step kernel and its Adam fold, which read none of them,
+// take this prefix as their kernel argument, so an Adam step runs on the kernel-argument segment it always had.
+struct MlpStepArgs {
   float* p;  // flat params (torch state_dict order): W0,b0,W1,b1,...
   float* m;  // Adam exp_avg (same layout)
   float* v;  // Adam exp_avg_sq
@@ -143,6 +146,21 @@ struct MlpArgs {
   // mlp_select.h refuses such a launch on every other trainer.
   int accum;
 };
+
+struct MlpArgs : MlpStepArgs {
+  // optimizer of a train-mode launch (batch-tiled trainer only; appended, so every other field keeps its offset):
+  // MLP_OPT_ADAM (0) is the launch as it always was; MLP_OPT_ADAMW decays p by lr_t * wd before the Adam update on the
+  // undecayed gradient (torch.optim.AdamW); MLP_OPT_SGD is torch.optim.SGD with `momentum`, `dampening`, `nesterov` and
+  // wd coupled into the gradient - it reads and writes p and m (the momentum buffer) only, v may be null, and so may m
+  // when momentum == 0; at device step count 0 the buffer is set to the gradient, whatever m held.  lr_t is the lr
+  // table's rate when one is bound.  Grad-mode launches apply no optimizer and ignore these.  mlp_select.h refuses a
+  // non-Adam train-mode launch on every other trainer.
+  int opt_kind;
+  float momentum, dampening;
+  int nesterov;
+};
+
+enum MlpOptimizer { MLP_OPT_ADAM = 0, MLP_OPT_ADAMW = 1, MLP_OPT_SGD = 2 };
 
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
 

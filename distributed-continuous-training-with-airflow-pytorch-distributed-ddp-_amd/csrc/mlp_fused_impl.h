@@ -448,9 +448,11 @@ __device__ __forceinline__ BiasDesc make_bias(const MlpShape& sh, int q) {
   return d;
 }
 
+// COUPLED = false: AdamW - the caller has decayed p already, g stays the undecayed gradient and wd is not read
+template <bool COUPLED = true>
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float b1, float b2, float wd,
                                           float step_size, float rbc2, float eps) {
-  g += wd * p;
+  if (COUPLED) g += wd * p;
   m = b1 * m + (1.f - b1) * g;
   v = b2 * v + (1.f - b2) * g * g;
   const float denom = __builtin_amdgcn_sqrtf(v) * rbc2 + eps;

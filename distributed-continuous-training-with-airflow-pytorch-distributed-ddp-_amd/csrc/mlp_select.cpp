@@ -35,6 +35,7 @@ MlpLaunchKey mlp_launch_key(const MlpArgs& a) {
   k.mv_aligned = (((uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0;
   k.weighted = a.class_w != nullptr || a.label_smooth != 0.f;
   k.accum = a.accum > 1 ? a.accum : 0;
+  k.other_opt = a.mode == 0 && a.opt_kind != MLP_OPT_ADAM;
   return k;
 }
 
@@ -54,6 +55,8 @@ MlpChoice mlp_select_trainer(const MlpShape& sh, bool use_wave, bool use_tile, c
   }
   if (k.accum)
     return none("gradient accumulation needs the batch-tiled trainer's plan (bmax 1024)", true);
+  if (k.other_opt)
+    return none("AdamW / SGD need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.weighted)
     return none("class weights / label smoothing need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.pending && !use_wave) return none("update-then-grad needs the single-wave kernel", true);

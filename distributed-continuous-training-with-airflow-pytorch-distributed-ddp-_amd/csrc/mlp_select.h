@@ -30,6 +30,8 @@ struct MlpLaunchKey {
   bool mv_aligned;  // m and v on 16-byte boundaries (unbound counts as aligned)
   bool weighted;    // class_w bound or label_smooth != 0: only the batch-tiled trainer computes that loss
   int accum;        // MlpArgs::accum when > 1 (gradient accumulation on: only the batch-tiled trainer runs windows), else 0
+  bool other_opt;   // a train-mode launch whose MlpArgs::opt_kind is not Adam (AdamW, SGD): only the batch-tiled
+                    // trainer's fold applies those; grad-mode launches apply no optimizer and never set it
 };
 MlpLaunchKey mlp_launch_key(const MlpArgs& a);  // the only place pointers become bools
 
@@ -56,6 +58,7 @@ bool mlp_block3_takes(const MlpShape& sh, const MlpLaunchKey& k);
 // mlp_tile.hip
 bool mlp_tile_batch_ok(int B);
 bool mlp_tile_window_ok(int B, int accum);  // accum micro-batches of B rows fit the slot cap (accum <= 1: always)
+bool mlp_tile_optimizer_ok(const MlpArgs& a);  // a train-mode launch's optimizer fields are ones its fold applies
 
 }  // namespace dct
 

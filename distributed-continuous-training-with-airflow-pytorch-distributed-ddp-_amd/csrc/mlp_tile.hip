@@ -39,6 +39,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mlp_fused_impl.h"
 #include "mlp_select.h"
 #include "mlp_tile_fwd.h"
@@ -87,7 +89,7 @@ __device__ __forceinline__ float drop_apply(float z, uint32_t seed, uint32_t gst
 // micro-batch kb of the window, workgroup (tile, kb) works on batch cur * accum + kb of the index list with that batch's
 // own bs and dropout step word gstep * accum + kb, and writes slot kb * T + tile.  Without it the kernel is as it was.
 template <int L, bool WL, bool ACC>
-__global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
+__global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds lo = lds_layout(L);
   const int tid = threadIdx.x;
@@ -325,7 +327,7 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpArgs a) {
 // (weighted) their sum over W_kb = the tiles' w[y] words in tile order, a micro-batch without a live row giving 0.
 // The loss word (e == P): the mean loss of the last live micro-batch alone, n_live = min(accum, ceil(rows left / B)).
 template <bool WL>
-__device__ __forceinline__ float fold_window(const Plan& tp, const MlpArgs& a, int T, int e, int cur) {
+__device__ __forceinline__ float fold_window(const Plan& tp, const MlpStepArgs& a, int T, int e, int cur) {
   const float* w = a.tile_ws + e;
   const float* ww = a.tile_ws + tp.P + 1;
   if (e < tp.P) {
@@ -367,7 +369,7 @@ __device__ __forceinline__ float fold_window(const Plan& tp, const MlpArgs& a, i
 // loss (0 only for a batch without a live row).  Unweighted: the plain sum - the tiles' gradients carry 1 / bs, the
 // loss word does not (batch_mean).
 template <bool WL>
-__device__ __forceinline__ float fold_plain(const Plan& tp, const MlpArgs& a, int T, int e, int cur) {
+__device__ __forceinline__ float fold_plain(const Plan& tp, const MlpStepArgs& a, int T, int e, int cur) {
   const float* w = a.tile_ws + e;
   float g = 0.f;
 #pragma unroll 8
@@ -383,15 +385,24 @@ __device__ __forceinline__ float fold_plain(const Plan& tp, const MlpArgs& a, in
 }
 
 // the unweighted plain step's loss word is the sum over the batch's live rows: its mean
-__device__ __forceinline__ float batch_mean(const MlpArgs& a, int cur, float sum) {
+__device__ __forceinline__ float batch_mean(const MlpStepArgs& a, int cur, float sum) {
   const int bs = max(0, min(a.B, a.n_items - cur * a.B));
   return bs > 0 ? sum / (float)bs : 0.f;
 }
 
 // One word per thread through fold_plain, or (ACC: MlpArgs::accum > 1) the accum * T slots of a window through
-// fold_window; then Adam (train mode) or grad_out (grad mode), the loss and the counters, which count optimizer steps.
-template <bool WL, bool ACC>
-__global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs a, int T, unsigned int* done) {
+// fold_window; then the optimizer (train mode) or grad_out (grad mode), the loss and the counters, which count
+// optimizer steps.  OPT (MlpArgs::opt_kind, chosen on the host like WL and ACC): MLP_OPT_ADAM is the kernel as it was;
+// MLP_OPT_ADAMW decays p by the step's rate times wd and runs adam_elem on the undecayed gradient; MLP_OPT_SGD
+// (sgd_elem) touches p and the momentum buffer m only - first step (the buffer becomes the gradient) is device step
+// count 0, the word Adam's bias correction reads.  Grad mode never reads OPT's fields: its launches use OPT = Adam.
+// The Adam instantiations take MlpStepArgs, the arguments without the optimizer's fields (mlp_fused.h): their
+// kernel-argument segment, and with it their code, is what it was before those fields existed.
+template <int OPT>
+using FoldArgs = std::conditional_t<OPT == MLP_OPT_ADAM, MlpStepArgs, MlpArgs>;
+
+template <bool WL, bool ACC, int OPT = MLP_OPT_ADAM>
+__global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, FoldArgs<OPT> a, int T, unsigned int* done) {
   __shared__ int s_cnt[2];
   const int tid = threadIdx.x;
   if (tid == 0) {
@@ -406,14 +417,27 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
     // the step's gradient word (e < P) or loss word (e == P)
     const float g = ACC ? fold_window<WL>(tp, a, T, e, cur) : fold_plain<WL>(tp, a, T, e, cur);
     if (e < tp.P) {
-      if (adam) {
+      if constexpr (OPT == MLP_OPT_SGD) {
+        if (adam) {
+          const float lr_t = lr_for(a.lr_tab, a.lr, tcur);
+          const bool mom = a.momentum != 0.f;  // (uniform: a kernel argument)
+          float pv = a.p[e], mv = mom ? a.m[e] : 0.f;
+          sgd_elem(pv, g, mv, lr_t, a.momentum, a.dampening, a.wd, a.nesterov != 0, tcur == 0);
+          a.p[e] = pv;
+          if (mom) a.m[e] = mv;
+        } else {
+          a.grad_out[e] = g;
+        }
+      } else if (adam) {
         const int t = tcur + 1;
         const float bc1 = 1.f - pow_t(log2f(a.b1), (float)t);
         const float bc2 = 1.f - pow_t(log2f(a.b2), (float)t);
-        const float step_size = lr_for(a.lr_tab, a.lr, tcur) / bc1;  // (next to the counter read above)
+        const float lr_t = lr_for(a.lr_tab, a.lr, tcur);  // (next to the counter read above)
+        const float step_size = lr_t / bc1;
         const float rbc2 = __builtin_amdgcn_rsqf(bc2);
         float pv = a.p[e], mv = a.m[e], vv = a.v[e];
-        adam_elem(pv, g, mv, vv, a.b1, a.b2, a.wd, step_size, rbc2, a.eps);
+        if (OPT == MLP_OPT_ADAMW) pv *= 1.f - lr_t * a.wd;
+        adam_elem<OPT != MLP_OPT_ADAMW>(pv, g, mv, vv, a.b1, a.b2, a.wd, step_size, rbc2, a.eps);
         a.p[e] = pv;
         a.m[e] = mv;
         a.v[e] = vv;
@@ -440,6 +464,22 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, MlpArgs
   }
 }
 
+// the fold of a launch: the Adam instantiation (the kernel as it was, on the kernel arguments it always had) for Adam
+// and for every grad-mode launch
+template <bool WL, bool ACC>
+static void launch_fold(int grid, const Plan& tp, const MlpArgs& a, int T, unsigned int* done, hipStream_t st) {
+  const int opt = a.mode == 0 ? a.opt_kind : (int)MLP_OPT_ADAM;
+  const dim3 g(grid), b(FOLD_NT);
+  if (opt == MLP_OPT_ADAM) {
+    const MlpStepArgs& base = a;
+    hipLaunchKernelGGL((mlp_tile_fold_kernel<WL, ACC, MLP_OPT_ADAM>), g, b, 0, st, tp, base, T, done);
+  } else if (opt == MLP_OPT_ADAMW) {
+    hipLaunchKernelGGL((mlp_tile_fold_kernel<WL, ACC, MLP_OPT_ADAMW>), g, b, 0, st, tp, a, T, done);
+  } else {
+    hipLaunchKernelGGL((mlp_tile_fold_kernel<WL, ACC, MLP_OPT_SGD>), g, b, 0, st, tp, a, T, done);
+  }
+}
+
 template <int L, bool WL, bool ACC>
 static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* done, hipStream_t st) {
   const int T = (a0.B + R - 1) / R;
@@ -458,7 +498,7 @@ static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* 
     a.step_base = a0.step_base + (uint32_t)s;
     if (a0.loss_out && !a0.cursor) a.loss_out = a0.loss_out + s;
     hipLaunchKernelGGL(fn, dim3(T, AK), dim3(NT), bytes, st, tp, a);
-    hipLaunchKernelGGL((mlp_tile_fold_kernel<WL, ACC>), dim3(fold_grid), dim3(FOLD_NT), 0, st, tp, a, T, done);
+    launch_fold<WL, ACC>(fold_grid, tp, a, T, done, st);
   }
   return hipGetLastError();
 }
@@ -468,6 +508,19 @@ static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* 
 bool mlp_tile_batch_ok(int B) { return B >= 1 && B <= tile::BMAX; }
 bool mlp_tile_window_ok(int B, int accum) {
   return mlp_tile_batch_ok(B) && (accum <= 1 || (long long)accum * ((B + tile::R - 1) / tile::R) <= tile::MAX_SLOTS);
+}
+
+// a train-mode launch's optimizer fields (grad mode ignores them): a known kind, wd >= 0, and for SGD torch's rules -
+// momentum >= 0, Nesterov only with momentum > 0 and no dampening; p, and the moments the optimizer reads, bound
+bool mlp_tile_optimizer_ok(const MlpArgs& a) {
+  if (a.mode != 0) return true;
+  if (a.opt_kind != MLP_OPT_ADAM && a.opt_kind != MLP_OPT_ADAMW && a.opt_kind != MLP_OPT_SGD) return false;
+  if (a.opt_kind == MLP_OPT_ADAM) return true;  // (the launch as it always was: nothing new refused)
+  if (!(a.wd >= 0.f) || !a.p) return false;
+  if (a.opt_kind == MLP_OPT_ADAMW) return a.m && a.v;
+  if (!(a.momentum >= 0.f)) return false;
+  if (a.nesterov && (a.momentum <= 0.f || a.dampening != 0.f)) return false;
+  return a.momentum == 0.f || a.m;
 }
 
 }  // namespace dct
@@ -506,6 +559,7 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stre
   if (a->accum < 0 || !dct::mlp_tile_window_ok(a->B, accum)) return (int)hipErrorInvalidValue;
   if (!a->cursor && (long long)(a->steps - 1) * accum * a->B >= a->n_items) return (int)hipErrorInvalidValue;
   if (a->xg_world > 1 || a->pending) return (int)hipErrorInvalidValue;
+  if (!dct::mlp_tile_optimizer_ok(*a)) return (int)hipErrorInvalidValue;
   if (!(a->label_smooth >= 0.f && a->label_smooth < 1.f)) return (int)hipErrorInvalidValue;
   if ((a->class_w || a->label_smooth != 0.f) && a->loss_kind != 0) return (int)hipErrorInvalidValue;  // CE only
   if (!a->tile_ws || a->tile_ws_floats < dct_mlp_tile_ws_floats_accum(dims, L, a->B, accum))

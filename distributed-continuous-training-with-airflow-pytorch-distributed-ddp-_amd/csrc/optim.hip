@@ -98,6 +98,78 @@ __global__ __launch_bounds__(CLIP_BLOCK) void grad_clip_coef_kernel(ClipArgs a) 
   }
 }
 
+// Flat SGD (torch.optim.SGD, maximize=False: sgd_elem) for the DDP step path of a model whose optimizer is SGD:
+// adam_flat_range's float4 grid-stride body, tail, step epilogue and late read of the device scalars, over p, g and the
+// momentum buffer m only (m unread and may be null when mu == 0).  The device counter already includes the step being
+// applied (as flat Adam's): counter - 1 steps were taken before it, which indexes the rate table, and the first step
+// (the buffer becomes the gradient, whatever m held) is counter == 1.
+struct SgdArgs {
+  float* p;
+  const float* g;
+  float* m;
+  int64_t n;
+  float lr, mu, damp, wd, grad_scale;
+  int nesterov;
+  int first;                // host step count t == 1; replaced by the device counter's when one is set
+  const int* step_counter;  // optional: t read on device (graph-replayable launches)
+  int* cursor;              // optional step epilogue, as AdamArgs
+  const float* loss_slot;
+  float* loss_out;
+  int loss_cap;
+  const float* lr_tab;  // optional rate table (lr_table.h), with step_counter
+};
+
+__device__ __forceinline__ void sgd_device_scalars(SgdArgs& a) {
+  const int ti = __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  a.lr = lr_for(a.lr_tab, a.lr, ti - 1);
+  a.first = ti == 1;
+}
+
+__device__ __forceinline__ void sgd_one(float& p, float g, float& m, const SgdArgs& a) {
+  sgd_elem(p, g * a.grad_scale, m, a.lr, a.mu, a.damp, a.wd, a.nesterov != 0, a.first != 0);
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_kernel(SgdArgs a) {
+  if (a.cursor && blockIdx.x == 0 && threadIdx.x == 0) {
+    const int c = a.cursor[0];
+    if (a.loss_out && c >= 0 && c < a.loss_cap) a.loss_out[c] = a.loss_slot[0];
+    a.cursor[0] = c + 1;
+  }
+  bool pending = a.step_counter != nullptr;  // read after the first element's loads are issued (adam_flat_range)
+  const bool mom = a.mu != 0.f;              // (uniform: a kernel argument)
+  const int64_t n4 = a.n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float4* p4 = reinterpret_cast<float4*>(a.p);
+  const float4* g4 = reinterpret_cast<const float4*>(a.g);
+  float4* m4 = reinterpret_cast<float4*>(a.m);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 p = p4[i];
+    const float4 g = g4[i];
+    float4 m = mom ? m4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pending) {
+      sgd_device_scalars(a);
+      pending = false;
+    }
+    sgd_one(p.x, g.x, m.x, a);
+    sgd_one(p.y, g.y, m.y, a);
+    sgd_one(p.z, g.z, m.z, a);
+    sgd_one(p.w, g.w, m.w, a);
+    p4[i] = p;
+    if (mom) m4[i] = m;
+  }
+  // tail (n % 4)
+  const int64_t tail0 = n4 << 2;
+  const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gt < a.n - tail0) {
+    if (pending) sgd_device_scalars(a);
+    const int64_t i = tail0 + gt;
+    float p = a.p[i], m = mom ? a.m[i] : 0.f;
+    sgd_one(p, a.g[i], m, a);
+    a.p[i] = p;
+    if (mom) a.m[i] = m;
+  }
+}
+
 }  // namespace dct
 
 static inline int grid_for(int64_t work, int block) {
@@ -187,6 +259,32 @@ int dct_adam_flat_step_lr(float* p, const float* g, float* m, float* v, uint16_t
     hipLaunchKernelGGL(dct::adam_flat_kernel<false>, grid, dim3(256), 0, st, a);
   else if (clip_value > 0.f) hipLaunchKernelGGL(dct::adam_flat_clip_kernel<2>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(dct::adam_flat_clip_kernel<1>, grid, dim3(256), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+int dct_sgd_flat_step(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,
+                      int nesterov, float wd, int64_t t, float grad_scale, const int* step_counter, int* cursor,
+                      const float* loss_slot, float* loss_out, int loss_cap, const float* lr_tab, void* stream) {
+  if (!(momentum >= 0.f) || !(wd >= 0.f) || (nesterov && (momentum <= 0.f || dampening != 0.f)) ||
+      !lr_tab_ok(lr_tab, step_counter))
+    return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  if (cursor && !loss_slot) return (int)hipErrorInvalidValue;
+  if (!p || !g || (momentum != 0.f && !m)) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) return (int)hipErrorInvalidValue;
+  dct::SgdArgs a{};
+  a.p = p; a.g = g; a.m = m; a.n = n;
+  a.lr = lr; a.mu = momentum; a.damp = dampening; a.wd = wd; a.grad_scale = grad_scale;
+  a.nesterov = nesterov ? 1 : 0;
+  a.first = t <= 1;
+  a.step_counter = step_counter;
+  a.cursor = cursor;
+  a.loss_slot = loss_slot;
+  a.loss_out = loss_out;
+  a.loss_cap = loss_cap;
+  a.lr_tab = lr_tab;
+  hipLaunchKernelGGL(dct::sgd_flat_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
 }
 

@@ -20,16 +20,34 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.fused_mlp import check_class_weight, check_label_smoothing
+from ..ops.fused_mlp import check_class_weight, check_label_smoothing, check_optimizer
 from ..trainer.module import TrainModule
+
+# configure_optimizers()'s options and their defaults, which reproduce the reference's Adam(lr): a model records only
+# the ones that differ (checkpoints, YAML), so a default model records what it always did
+OPTIM_DEFAULTS = dict(optimizer="adam", weight_decay=0.0, momentum=0.0, dampening=0.0, nesterov=False,
+                      betas=(0.9, 0.999), eps=1e-8)
 
 
 class MLPClassifier(TrainModule):
     def __init__(self, input_dim: int, hidden: Sequence[int] = (64,), num_classes: int = 2, dropout: float = 0.2,
                  loss: str = "ce", lr: float = 0.01, class_weight: Optional[Sequence[float]] = None,
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, optimizer: str = "adam", weight_decay: float = 0.0,
+                 momentum: float = 0.0, nesterov: bool = False, betas: Sequence[float] = (0.9, 0.999),
+                 eps: float = 1e-8, dampening: float = 0.0):
         super().__init__()
         self.save_hyperparameters()
+        # the optimizer configure_optimizers() builds: torch.optim.Adam / AdamW / SGD, checked with torch's rules here
+        # (an unknown name, a negative decay or momentum, Nesterov without momentum or with dampening: ValueError)
+        self.optim = dict(optimizer=check_optimizer(optimizer, weight_decay, momentum, dampening, nesterov),
+                          weight_decay=float(weight_decay), momentum=float(momentum), dampening=float(dampening),
+                          nesterov=bool(nesterov), betas=tuple(float(b) for b in betas), eps=float(eps))
+        for key, default in OPTIM_DEFAULTS.items():
+            if key in self.hparams:
+                if self.optim[key] != default:
+                    self.hparams[key] = list(self.optim[key]) if key == "betas" else self.optim[key]
+                else:
+                    del self.hparams[key]
         if loss not in ("ce", "mse"):
             raise ValueError("loss must be 'ce' or 'mse'")
         # torch's CrossEntropyLoss(weight=, label_smoothing=): exactly num_classes finite, strictly positive weights,
@@ -94,7 +112,12 @@ class MLPClassifier(TrainModule):
         return loss
 
     def configure_optimizers(self):
-        return torch.optim.Adam(self.parameters(), lr=self.lr)
+        o = self.optim
+        if o["optimizer"] == "sgd":
+            return torch.optim.SGD(self.parameters(), lr=self.lr, momentum=o["momentum"], dampening=o["dampening"],
+                                   weight_decay=o["weight_decay"], nesterov=o["nesterov"])
+        cls = torch.optim.AdamW if o["optimizer"] == "adamw" else torch.optim.Adam
+        return cls(self.parameters(), lr=self.lr, betas=o["betas"], eps=o["eps"], weight_decay=o["weight_decay"])
 
     # ---- fused-engine contract
     def fused_spec(self):
@@ -113,12 +136,14 @@ class MLPClassifier(TrainModule):
 class WeatherClassifier(MLPClassifier):
     """Reference model: Linear(D,64)-ReLU-Dropout(0.2)-Linear(64,2), CE, Adam(lr=0.01)."""
 
-    def __init__(self, input_dim: int, class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0):
+    def __init__(self, input_dim: int, class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0,
+                 **optim):
         super().__init__(input_dim=input_dim, hidden=(64,), num_classes=2, dropout=0.2, loss="ce", lr=0.01,
-                         class_weight=class_weight, label_smoothing=label_smoothing)
-        # the reference records exactly {"input_dim": D} (save_hyperparameters at :53); the two loss options join
-        # it only when set
+                         class_weight=class_weight, label_smoothing=label_smoothing, **optim)
+        # the reference records exactly {"input_dim": D} (save_hyperparameters at :53); the loss and optimizer options
+        # join it only when set
         hp = {"input_dim": int(input_dim)}
+        hp.update({k: self.hparams[k] for k in OPTIM_DEFAULTS if k in self.hparams})
         if self.class_weight is not None:
             hp["class_weight"] = [float(x) for x in self.class_weight.tolist()]
         if self.label_smoothing != 0.0:
@@ -128,9 +153,11 @@ class WeatherClassifier(MLPClassifier):
 
 def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None, num_classes: int = 2,
               dropout: float = 0.2, loss: str = "ce", lr: float = 0.01,
-              class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0) -> MLPClassifier:
+              class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0,
+              **optim) -> MLPClassifier:
+    """``optim``: MLPClassifier's optimizer options (OPTIM_DEFAULTS' keys)."""
     if name == "weather":
-        return WeatherClassifier(input_dim, class_weight=class_weight, label_smoothing=label_smoothing)
+        return WeatherClassifier(input_dim, class_weight=class_weight, label_smoothing=label_smoothing, **optim)
     # name -> (hidden widths, dropout, loss, lr); BASELINE.json configs 1-4
     presets = {
         "weather-mlp-3x128": ((128, 128), 0.2, "ce", 0.01),
@@ -139,4 +166,4 @@ def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None,
     if name in presets and hidden is None:
         hidden, dropout, loss, lr = presets[name]
     return MLPClassifier(input_dim, hidden=hidden or (64,), num_classes=num_classes, dropout=dropout, loss=loss, lr=lr,
-                         class_weight=class_weight, label_smoothing=label_smoothing)
+                         class_weight=class_weight, label_smoothing=label_smoothing, **optim)

@@ -52,6 +52,28 @@ def check_accumulate(accumulate, name: str = "accumulate") -> int:
     return accumulate
 
 
+OPTIMIZERS = ("adam", "adamw", "sgd")  # train(optimizer=): torch.optim.Adam / AdamW / SGD (csrc/mlp_fused.h MlpOptimizer)
+
+
+def check_optimizer(optimizer, weight_decay: float = 0.0, momentum: float = 0.0, dampening: float = 0.0,
+                    nesterov: bool = False) -> str:
+    """The optimizer name of a train launch, checked with torch's own rules for the two optimizers added to Adam:
+    ValueError for an unknown name, a negative weight decay or momentum, and Nesterov momentum without a momentum or
+    with dampening.  ``"adam"`` is passed through with nothing new refused."""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+    if optimizer == "adam":
+        return optimizer
+    if not float(weight_decay) >= 0.0:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+    if optimizer == "sgd":
+        if not float(momentum) >= 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if nesterov and (float(momentum) <= 0.0 or float(dampening) != 0.0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+    return optimizer
+
+
 def _mix_hash(a, b, c):
     """csrc/mlp_fused_impl.h mix_hash on numpy uint32 arrays (wrapping arithmetic)."""
     import numpy as np
@@ -209,6 +231,30 @@ class FusedMLPKernel:
                              f"takes, and accumulate * ceil(batch / 32) <= {int(native().mlp_tile_max_slots())} slots")
         return dict(accumulate=accumulate)
 
+    def _check_optimizer(self, optimizer, batch: int, weight_decay, momentum, dampening, nesterov, train: bool) -> dict:
+        """The native arguments of a launch's optimizer ({} for Adam, and for a grad-mode launch, which applies none)."""
+        if check_optimizer(optimizer, weight_decay, momentum, dampening, nesterov) == "adam" or not train:
+            return {}
+        if self.plan.trainer(int(batch), optimizer=optimizer) != "tile":
+            raise ValueError(f"optimizer={optimizer!r} needs the batch-tiled trainer: a plan of bmax 1024 "
+                             "(any batch 1..1024) for an architecture it takes")
+        if optimizer == "sgd":
+            return dict(optimizer="sgd", momentum=float(momentum), dampening=float(dampening), nesterov=bool(nesterov))
+        return dict(optimizer="adamw")
+
+    @staticmethod
+    def _moments_of(opt_args: dict, m, v):
+        """The moment buffers a launch that applies an optimizer binds: m and v for Adam / AdamW; for SGD the momentum
+        buffer m alone, and not even that without momentum (what the launch does not read is passed as null)."""
+        if opt_args.get("optimizer") == "sgd":
+            m = m if opt_args["momentum"] != 0.0 else None
+            if opt_args["momentum"] != 0.0 and m is None:
+                raise ValueError("SGD with momentum needs the momentum buffer m")
+            return m, None
+        if opt_args and (m is None or v is None):  # (Adam: checked as it always was)
+            raise ValueError("an AdamW launch needs the moment buffers m and v")
+        return m, v
+
     @property
     def plan(self):
         if self._plan is None:
@@ -301,8 +347,16 @@ class FusedMLPKernel:
               pending: Optional[torch.Tensor] = None, stage: Optional[torch.Tensor] = None,
               stream: Optional[int] = None, xg=None, xg_timeout_s: float = 2.0,
               lr_tab: Optional[torch.Tensor] = None, class_weight: Optional[torch.Tensor] = None,
-              label_smoothing: float = 0.0, accumulate: int = 1):
+              label_smoothing: float = 0.0, accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0,
+              dampening: float = 0.0, nesterov: bool = False):
         """Run ``steps`` fused optimizer steps (mode 0) or one gradient step (grad_out given).
+
+        ``optimizer``: ``"adam"`` (torch.optim.Adam), or on the batch-tiled trainer's plan ``"adamw"``
+        (torch.optim.AdamW: ``p *= 1 - lr_t * weight_decay``, then Adam on the undecayed gradient) and ``"sgd"``
+        (torch.optim.SGD with ``momentum``, ``dampening``, ``nesterov`` and the coupled ``weight_decay``; ``betas`` /
+        ``eps`` are ignored, ``m`` is the momentum buffer - overwritten with the gradient at step count 0, and not
+        needed (None) without momentum - and ``v`` is not touched and may be None).  ``lr_t`` is ``lr_tab``'s rate when
+        a table is bound.  A grad-mode launch applies no optimizer and ignores all of it.
 
         ``accumulate`` = K > 1 (Lightning's ``accumulate_grad_batches``; the batch-tiled trainer's plan only): an
         optimizer step is a window of K micro-batches of ``batch`` rows and applies ``(1 / K) * sum_kb grad(loss_kb)``,
@@ -322,6 +376,9 @@ class FusedMLPKernel:
         inside the kernel over peer-mapped receive buffers (see ``parallel.xgmi``)."""
         mode = 1 if grad_out is not None else 0
         need_mv = mode == 0 or pending is not None
+        opt_args = self._check_optimizer(optimizer, batch, weight_decay, momentum, dampening, nesterov, mode == 0)
+        if need_mv:
+            m, v = self._moments_of(opt_args, m, v)
         self._check_params(p, m if need_mv else None, v if need_mv else None)
         if pending is not None and not (pending.is_cuda and pending.dtype == torch.int32):
             raise ValueError("pending must be a cuda int32 flag")
@@ -363,7 +420,7 @@ class FusedMLPKernel:
             ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending), ptr(stage),
             stream if stream is not None else stream_handle(),
             **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab), **wl_args,
-            **acc_args,
+            **acc_args, **opt_args,
         )
 
     def prepare_train(self, p, m, v, X, Y, idx, n_items: int, batch: int, lr: float, betas=(0.9, 0.999),
@@ -372,18 +429,22 @@ class FusedMLPKernel:
                       step_counter: Optional[torch.Tensor] = None, xg=None, xg_timeout_s: float = 2.0,
                       xg_ticks: Optional[torch.Tensor] = None, lr_tab: Optional[torch.Tensor] = None,
                       class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
-                      accumulate: int = 1) -> "BoundTrain":
+                      accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0, dampening: float = 0.0,
+                      nesterov: bool = False) -> "BoundTrain":
         """Validate the operands of persistent train-mode launches ONCE and bind them natively.
 
         ``BoundTrain.run(first_step, steps)`` then launches steps [first_step, first_step+steps)
         over ``idx`` with losses in ``loss_out[first_step + s]`` - the per-launch cost is one
         positional native call (no keyword parsing, no tensor checks), which is what the short
         timed windows of the benchmark contract see.  ``accumulate`` as in ``train``: the steps are
-        optimizer steps of ``accumulate`` micro-batches each."""
-        self._check_params(p, m, v)
-        self._check_data(X, Y, idx, n_items)
+        optimizer steps of ``accumulate`` micro-batches each.  ``optimizer`` / ``momentum`` / ``dampening`` /
+        ``nesterov`` as in ``train``."""
         if not 1 <= batch <= self.bmax:
             raise ValueError(f"batch {batch} outside 1..{self.bmax}")
+        opt_args = self._check_optimizer(optimizer, batch, weight_decay, momentum, dampening, nesterov, True)
+        m, v = self._moments_of(opt_args, m, v)
+        self._check_params(p, m, v)
+        self._check_data(X, Y, idx, n_items)
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
         if step_counter is None or not (step_counter.is_cuda and step_counter.dtype == torch.int32):
@@ -410,7 +471,7 @@ class FusedMLPKernel:
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, ptr(loss_out), 0 if loss_out is None else loss_out.numel(), LOSS_KINDS[loss],
             ptr(step_counter), **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab),
-            **wl_args, **acc_args)
+            **wl_args, **acc_args, **opt_args)
         return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws, lr_tab,
                                    class_weight),
                           p.device.index or 0)

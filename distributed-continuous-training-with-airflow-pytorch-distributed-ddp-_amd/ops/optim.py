@@ -6,6 +6,9 @@ into one flat gradient buffer, which is what the bucketed reducer all-reduces), 
 is one fused kernel launch on the GPU (csrc/optim.hip) or one vectorised torch expression on
 the CPU plumbing path.  ``state_dict()`` emits exactly torch.optim.Adam's format so the
 Lightning checkpoint's ``optimizer_states`` entry stays loadable by torch 2.1 / Lightning 2.1.
+
+``sgd_flat_`` / ``FlatSGD`` are the same for ``torch.optim.SGD`` (momentum, dampening, Nesterov, coupled weight decay):
+the flat step of the fused engine's DDP step path for an SGD model, and torch's ``momentum_buffer`` state layout.
 """
 from __future__ import annotations
 
@@ -277,3 +280,148 @@ class FlatAdam:
             self.step_count = 0
         if getattr(self, "_counter", None) is not None:
             self._counter.fill_(self.step_count)
+
+
+# ---------------------------------------------------------------------------------------------- SGD
+def sgd_flat_(p: torch.Tensor, g: torch.Tensor, m: Optional[torch.Tensor], step: int, lr: float,
+              momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
+              grad_scale: float = 1.0, step_counter: Optional[torch.Tensor] = None,
+              lr_tab: Optional[torch.Tensor] = None, epilogue=None):
+    """In-place ``torch.optim.SGD`` (maximize=False) on flat fp32 buffers; ``m`` is the momentum buffer (None allowed
+    without momentum) and ``step`` the 1-based step count after this update: at step 1 torch has no buffer yet, so the
+    buffer becomes the gradient and what ``m`` held is ignored.  On the GPU one kernel (csrc/optim.hip); with
+    ``step_counter`` (a cuda int32 that already includes this step) the count, and ``lr_tab``'s rate for
+    ``*step_counter - 1`` steps taken, are read on the device.  ``epilogue=(cursor, loss, loss_out)`` as FlatAdam.step.
+    ``g`` is not rewritten."""
+    n = p.numel()
+    momentum, dampening, weight_decay = float(momentum), float(dampening), float(weight_decay)
+    if not momentum >= 0.0:
+        raise ValueError(f"Invalid momentum value: {momentum}")
+    if not weight_decay >= 0.0:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+    if nesterov and (momentum <= 0.0 or dampening != 0.0):
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+    if momentum != 0.0 and m is None:
+        raise ValueError("sgd_flat_: momentum needs the buffer m")
+    for t in (g, m):
+        if t is not None and (t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.device != p.device):
+            raise ValueError("sgd_flat_: p/g/m must be contiguous fp32 buffers of equal size on one device")
+    if p.is_cuda:
+        if step_counter is not None and not (step_counter.is_cuda and step_counter.dtype == torch.int32):
+            raise ValueError("step_counter must be a cuda int32 tensor")
+        if lr_tab is not None and (step_counter is None or not lr_tab.is_cuda or lr_tab.dtype != torch.float32
+                                   or lr_tab.numel() < 5):
+            raise ValueError("lr_tab must be a cuda fp32 rate table (4 header words + >= 1 rate) used with step_counter")
+        cursor, loss, loss_out = epilogue if epilogue is not None else (None, None, None)
+        native().sgd_flat_step(ptr(p), ptr(g), ptr(m) if momentum != 0.0 else 0, n, float(lr), momentum, dampening,
+                               bool(nesterov), weight_decay, max(1, int(step)), float(grad_scale), ptr(step_counter),
+                               ptr(cursor), ptr(loss), ptr(loss_out), 0 if loss_out is None else loss_out.numel(),
+                               stream_handle(p.device), ptr(lr_tab))
+        return
+    if lr_tab is not None or epilogue is not None:
+        raise ValueError("sgd_flat_: a rate table / step epilogue is the GPU kernel's; on the CPU pass the rate as lr")
+    gg = g * grad_scale if grad_scale != 1.0 else g
+    if weight_decay:
+        gg = gg + weight_decay * p
+    if momentum != 0.0:
+        if int(step) <= 1:
+            m.copy_(gg)
+        else:
+            m.mul_(momentum).add_(gg, alpha=1 - dampening)
+        gg = gg.add(m, alpha=momentum) if nesterov else m
+    p.add_(gg, alpha=-lr)
+
+
+def _torch_sgd_group_defaults() -> Dict:
+    """The param-group keys the installed ``torch.optim.SGD`` writes (as _torch_adam_group_defaults)."""
+    try:
+        d = dict(torch.optim.SGD([torch.zeros(1, requires_grad=True)], lr=1e-3).defaults)
+    except Exception:  # noqa: BLE001
+        d = dict(lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, maximize=False, foreach=None,
+                 differentiable=False, fused=None)
+    return d
+
+
+def _torch_adamw_group_defaults() -> Dict:
+    """The param-group keys the installed ``torch.optim.AdamW`` writes (as _torch_adam_group_defaults)."""
+    try:
+        d = dict(torch.optim.AdamW([torch.zeros(1, requires_grad=True)]).defaults)
+    except Exception:  # noqa: BLE001
+        d = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, maximize=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None)
+    return d
+
+
+class FlatSGD:
+    """SGD over a flat parameter buffer, torch.optim.SGD-compatible state_dict: a per-parameter ``momentum_buffer``,
+    present only with momentum and once a step has been taken.  torch's SGD state has no step count: the holder's
+    ``step_count`` is the caller's to carry (the engines keep it as ``global_step``)."""
+
+    def __init__(self, flat_param: torch.Tensor, flat_grad: torch.Tensor, param_shapes: Sequence[torch.Size],
+                 lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
+                 nesterov: bool = False, lr_schedule=None, momentum_buffer: Optional[torch.Tensor] = None):
+        """``momentum_buffer``: an existing flat buffer to hold (an engine's own), instead of a new zeroed one."""
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self.p = flat_param
+        self.g = flat_grad
+        self.m = torch.zeros_like(flat_param) if momentum_buffer is None else momentum_buffer
+        self.shapes = [torch.Size(s) for s in param_shapes]
+        group = _torch_sgd_group_defaults()
+        group.update(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                     params=list(range(len(self.shapes))))
+        self.param_groups = [group]
+        self.step_count = 0
+        self.lr_schedule = lr_schedule
+
+    @property
+    def lr(self):
+        return self.param_groups[0]["lr"]
+
+    def step(self, grad_scale: float = 1.0):
+        self.step_count += 1
+        g = self.param_groups[0]
+        lr, lr_tab, counter = g["lr"], None, None
+        if self.lr_schedule is not None:
+            if self.p.is_cuda:
+                lr_tab = self.lr_schedule.device_table(self.p.device)
+                counter = torch.full((1,), self.step_count, dtype=torch.int32, device=self.p.device)
+            else:
+                lr = self.lr_schedule.rate_for(self.step_count - 1)
+        sgd_flat_(self.p, self.g, self.m, self.step_count, lr, g["momentum"], g["dampening"], g["nesterov"],
+                  g["weight_decay"], grad_scale=grad_scale, step_counter=counter, lr_tab=lr_tab)
+
+    def zero_grad(self):
+        self.g.zero_()
+
+    def _views(self, flat):
+        out, off = [], 0
+        for s in self.shapes:
+            n = s.numel()
+            out.append(flat[off: off + n].view(s))
+            off += n
+        return out
+
+    def state_dict(self) -> Dict:
+        state = {}
+        if self.step_count > 0 and self.param_groups[0]["momentum"] != 0:
+            for i, mv in enumerate(self._views(self.m)):
+                state[i] = {"momentum_buffer": mv.detach().to("cpu", torch.float32).clone()}
+        return {"state": state, "param_groups": [dict(g) for g in self.param_groups]}
+
+    def load_state_dict(self, sd: Dict):
+        pg = sd["param_groups"][0]
+        for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov"):
+            if k in pg:
+                self.param_groups[0][k] = pg[k]
+        st = sd.get("state", {})
+        loaded = False
+        for i, mv in enumerate(self._views(self.m)):
+            s = st.get(i, st.get(str(i)))
+            if s is not None and s.get("momentum_buffer") is not None:
+                mv.copy_(s["momentum_buffer"])
+                loaded = True
+        # (no step count in torch's SGD state: a loaded buffer means at least one step was taken - the first-step rule
+        # must not overwrite it; the caller sets the true count)
+        self.step_count = 1 if loaded else 0

@@ -18,6 +18,10 @@
   ``training_step`` + autograd, parameters/gradients as views of flat buffers, the bucketed
   reducer hooked on ``post_accumulate_grad`` (overlap with backward), flat Adam.
 
+The fused engine applies torch.optim.Adam natively on every plan, and torch.optim.AdamW / SGD (optim_hparams_of) on the
+batch-tiled trainer's plan (csrc/mlp_tile.hip: the optimizer is the fold kernel's), with flat SGD / flat Adam with
+decoupled decay on its DDP step path; every other optimizer runs on the autograd engine as the torch optimizer itself.
+
 A learning-rate scheduler returned by ``configure_optimizers()`` (trainer/lr_schedule.py) is followed by the autograd
 all three engines (the graph engine: trainer/graph_engine.py): every launch that applies Adam reads the step's rate
 from a device table at the device step count, so persistent launches and captured graphs follow a per-step schedule.
@@ -37,7 +41,7 @@ from ..ops._native import reload_knobs
 from ..ops.fused_mlp import (TILE_BMAX, FusedMLPKernel, check_accumulate, mlp_num_params, tile_supported,
                              tile_window_ok, weighted_infer_stats)
 from ..ops.nn import BatchGather, bound_params, fold_batch_gather, join_side_work, unit_loss_seed
-from ..ops.optim import FlatAdam, adam_flat_, check_clip_args
+from ..ops.optim import FlatAdam, FlatSGD, _torch_adamw_group_defaults, adam_flat_, check_clip_args, sgd_flat_
 from ..parallel.dist import DistContext, init_native_comm
 from ..parallel.reducer import NativeBucketReducer, TorchBucketReducer, plan_buckets
 from ..utils.debug import assert_reducer_complete, check_device
@@ -65,6 +69,26 @@ def adam_hparams_of(opt) -> Optional[Dict]:
         return None
     return dict(lr=float(g["lr"]), betas=tuple(float(b) for b in g["betas"]), eps=float(g["eps"]),
                 weight_decay=float(g["weight_decay"]))
+
+
+def optim_hparams_of(opt) -> Optional[Dict]:
+    """Hyper-parameters of an optimizer the fused engine applies natively, None for every other one (another class,
+    ``amsgrad``, ``maximize``, param groups that differ): Adam's dict exactly as adam_hparams_of gives it (no ``kind``
+    key), the same keys plus ``kind="adamw"`` for torch.optim.AdamW, and for torch.optim.SGD
+    ``dict(kind="sgd", lr, momentum, dampening, nesterov, weight_decay)``."""
+    if type(opt) is torch.optim.Adam:
+        return adam_hparams_of(opt)
+    if type(opt) not in (torch.optim.AdamW, torch.optim.SGD):
+        return None
+    g = opt.param_groups[0]
+    keys = ("lr", "betas", "eps", "weight_decay", "amsgrad", "maximize", "momentum", "dampening", "nesterov")
+    if g.get("amsgrad") or g.get("maximize") or any(h.get(k) != g.get(k) for h in opt.param_groups[1:] for k in keys):
+        return None
+    if type(opt) is torch.optim.AdamW:
+        return dict(kind="adamw", lr=float(g["lr"]), betas=tuple(float(b) for b in g["betas"]), eps=float(g["eps"]),
+                    weight_decay=float(g["weight_decay"]))
+    return dict(kind="sgd", lr=float(g["lr"]), momentum=float(g["momentum"]), dampening=float(g["dampening"]),
+                nesterov=bool(g["nesterov"]), weight_decay=float(g["weight_decay"]))
 
 
 def spec_weighted(spec: Dict) -> bool:
@@ -100,10 +124,15 @@ class FusedMLPEngine(_EngineBase):
     FUSED_UPDATE = True
 
     @staticmethod
-    def applicable(model, device: torch.device, batch_size: int, accumulate: int = 1) -> bool:
+    def applicable(model, device: torch.device, batch_size: int, accumulate: int = 1, optimizer: str = "adam") -> bool:
         if device.type != "cuda" or not hasattr(model, "fused_spec"):
             return False
         spec = model.fused_spec()
+        if optimizer != "adam" and accumulate <= 1:
+            # AdamW / SGD: only the batch-tiled trainer's fold applies them, at any batch it takes
+            if (spec_weighted(spec) and spec["loss"] != "ce") or not tile_supported(spec["dims"]):
+                return False
+            return 1 <= batch_size <= TILE_BMAX
         if accumulate > 1:
             # windows of micro-batches: only the batch-tiled trainer runs them - its shapes, any batch 1..1024,
             # accumulate * ceil(batch / 32) slots within its cap
@@ -136,10 +165,23 @@ class FusedMLPEngine(_EngineBase):
         self.dropout = float(spec["dropout"])
         self.loss = spec["loss"]
         self.adam = adam
+        # the optimizer (optim_hparams_of: ``kind`` absent means Adam).  AdamW / SGD live in the batch-tiled trainer's
+        # fold alone, so such a model is built on the tile plan whatever the batch, like a weighted loss or K > 1 -
+        # without the in-kernel exchange, update-then-grad or the peer all-reduce + Adam kernel; its DDP step path is
+        # grad-mode launch -> RCCL -> flat SGD / flat Adam with decoupled decay.  self.hp: the optimizer's keywords of a
+        # train-mode launch
+        self.kind = adam.get("kind", "adam")
+        if self.kind == "sgd":
+            self.hp = dict(lr=adam["lr"], weight_decay=adam["weight_decay"], optimizer="sgd",
+                           momentum=adam["momentum"], dampening=adam["dampening"], nesterov=adam["nesterov"])
+        else:
+            self.hp = {k: adam[k] for k in ("lr", "betas", "eps", "weight_decay") if k in adam}
+            if self.kind != "adam":
+                self.hp["optimizer"] = self.kind
         # class-weighted / label-smoothed CE (models/mlp.py): the batch-tiled trainer's plan whatever the batch, and
         # the two arguments on every train launch; validation through the tiled inference kernel
         self.weighted = spec_weighted(spec)
-        tiled = self.weighted or self.K > 1
+        tiled = self.weighted or self.K > 1 or self.kind != "adam"
         bmax = TILE_BMAX if tiled else (4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
         self.kernel = FusedMLPKernel(self.dims, bmax=bmax)
         if self.K > 1 and self.kernel.plan.trainer(self.B, accumulate=self.K) != "tile":
@@ -165,7 +207,7 @@ class FusedMLPEngine(_EngineBase):
         # DDP step path; DCT_FORCE_DDP=1 drives it at world size 1 (single-GPU test of the
         # RCCL communicator + graph capture + device cursors)
         self.ddp = ctx.is_distributed or os.environ.get("DCT_FORCE_DDP", "0") == "1"
-        self.fused_update = self.kernel.fused_update_supported(self.B) and self.FUSED_UPDATE
+        self.fused_update = self.kernel.fused_update_supported(self.B) and self.FUSED_UPDATE  # (never on the tile plan)
         self.pending = torch.zeros(1, dtype=torch.int32, device=dev)
         self.stage = torch.zeros(64 * 4, dtype=torch.int32, device=dev)  # next-batch hand-off
         # (mlp_block5's grad mode takes no batch hand-off between DDP step launches: it measured 0.5 us
@@ -201,7 +243,7 @@ class FusedMLPEngine(_EngineBase):
             self.xg_timeout_s = timeout_s()
             # exchange time of the launches (s_memrealtime ticks, 100 MHz) -> allreduce_ms per epoch
             self.xg_ticks = torch.zeros(1, dtype=torch.int64, device=dev) if self.xg is not None else None
-            if self.xg is None and not self.fused_update:
+            if self.xg is None and not self.fused_update and self.kind == "adam":  # (xg_adam.hip applies Adam)
                 self.gx = setup_grad_exchange(ctx, self.P + 1)
             if xg_mode() == "xgmi" and self.xg is None and self.gx is None:
                 raise RuntimeError("DCT_ALLREDUCE=xgmi but neither the in-kernel exchange nor the peer "
@@ -209,7 +251,7 @@ class FusedMLPEngine(_EngineBase):
             if self.xg is None and self.gx is None and self.comm is None:
                 raise RuntimeError("distributed fused engine needs RCCL (backend nccl) or the in-kernel "
                                    "xGMI exchange; neither is available")
-        elif self.ddp and not self.fused_update and os.environ.get("DCT_XG_GRAD") == "1":
+        elif self.ddp and not self.fused_update and self.kind == "adam" and os.environ.get("DCT_XG_GRAD") == "1":
             # single-GPU rehearsal (DCT_FORCE_DDP=1 DCT_XG_GRAD=1): the exchange kernel of one rank
             # (no pushes, no polls) in place of the one-rank RCCL all-reduce + flat Adam
             from ..ops._native import native
@@ -256,21 +298,35 @@ class FusedMLPEngine(_EngineBase):
     def load_from_model(self):
         self.p.copy_(self._flat_from_model().to(self.device))
 
-    def optimizer_state_dict(self) -> Dict:
+    def _flat_optimizer(self):
+        """The state-dict face of the optimizer in use, over this engine's buffers: torch's own layout - ``exp_avg`` /
+        ``exp_avg_sq`` / ``step`` for Adam and AdamW (whose param-group keys are AdamW's), ``momentum_buffer`` for SGD."""
         shapes = [t.shape for t in self._linear_params()]
-        fa = FlatAdam(self.p, self.p, shapes, lr=self.adam["lr"], betas=self.adam["betas"], eps=self.adam["eps"],
-                      weight_decay=self.adam["weight_decay"])
-        fa.m, fa.v = self.m, self.v
-        fa.step_count = self.global_step
-        return fa.state_dict()
+        a = self.adam
+        if self.kind == "sgd":
+            fo = FlatSGD(self.p, self.p, shapes, lr=a["lr"], momentum=a["momentum"], dampening=a["dampening"],
+                         weight_decay=a["weight_decay"], nesterov=a["nesterov"], momentum_buffer=self.m)
+            return fo
+        fo = FlatAdam(self.p, self.p, shapes, lr=a["lr"], betas=a["betas"], eps=a["eps"],
+                      weight_decay=a["weight_decay"])
+        if self.kind == "adamw":
+            group = _torch_adamw_group_defaults()
+            group.update({k: fo.param_groups[0][k] for k in ("lr", "betas", "eps", "weight_decay", "params")})
+            fo.param_groups = [group]
+        fo.m, fo.v = self.m, self.v
+        return fo
+
+    def optimizer_state_dict(self) -> Dict:
+        fo = self._flat_optimizer()
+        fo.step_count = self.global_step
+        return fo.state_dict()
 
     def load_optimizer_state(self, sd: Dict, global_step: int):
-        shapes = [t.shape for t in self._linear_params()]
-        fa = FlatAdam(self.p, self.p, shapes, **self.adam)
-        fa.m, fa.v = self.m, self.v
-        fa.load_state_dict(sd)
+        fo = self._flat_optimizer()
+        fo.load_state_dict(sd)
         self.global_step = global_step
-        self.step_counter.fill_(int(fa.step_count))
+        # (torch's SGD state carries no step count: the checkpoint's global_step is the count)
+        self.step_counter.fill_(int(global_step if self.kind == "sgd" else fo.step_count))
         self._reset_exchanges()  # exchange tags derive from the step counter: drop stale granules
 
     def _reset_exchanges(self):
@@ -328,10 +384,8 @@ class FusedMLPEngine(_EngineBase):
         key = (n_items, loss_out.data_ptr(), loss_out.numel(), 0 if tab is None else tab.data_ptr())
         bl = getattr(self, "_bound", None)
         if bl is None or self._bound_key != key:
-            a = self.adam
             bl = self.kernel.prepare_train(self.p, self.m, self.v, self.X, self.Y, self.idx, n_items=n_items,
-                                           batch=self.B, lr=a["lr"], betas=a["betas"], eps=a["eps"],
-                                           weight_decay=a["weight_decay"], dropout=self.dropout, seed=self.rank_seed,
+                                           batch=self.B, **self.hp, dropout=self.dropout, seed=self.rank_seed,
                                            loss_out=loss_out, loss=self.loss, step_counter=self.step_counter,
                                            xg=self.xg, xg_timeout_s=getattr(self, "xg_timeout_s", 20.0),
                                            xg_ticks=getattr(self, "xg_ticks", None) if self.xg is not None else None,
@@ -393,9 +447,7 @@ class FusedMLPEngine(_EngineBase):
         for _ in range(steps - done):
             self._ddp_step(n_items, loss_out)
         if self.fused_update:  # the last step's update is still pending: apply it
-            a = self.adam
-            adam_flat_(self.p, self.gbuf[: self.P], self.m, self.v, 1, a["lr"], a["betas"], a["eps"],
-                       a["weight_decay"], step_counter=self.step_counter, lr_tab=self._lr_tab())
+            self._flat_step()
             self.pending.zero_()
         # the last step's reduced loss is flushed by the next kernel; flush it here instead
         last = first_step + steps - 1
@@ -431,8 +483,19 @@ class FusedMLPEngine(_EngineBase):
                             a["betas"], a["eps"], a["weight_decay"], timeout=self.xg_timeout_s, lr_tab=self._lr_tab())
             return
         self.comm.allreduce(self.gbuf.data_ptr(), self.P + 1, nat.DT_F32, nat.OP_AVG, stream)
+        self._flat_step()
+
+    def _flat_step(self):
+        """The DDP step path's optimizer on the all-reduced gradient in gbuf, at the device step count (which the
+        grad-mode launch has advanced already): flat Adam, flat Adam with decoupled decay (AdamW) or flat SGD."""
+        a = self.adam
+        if self.kind == "sgd":
+            sgd_flat_(self.p, self.gbuf[: self.P], self.m, 1, a["lr"], a["momentum"], a["dampening"], a["nesterov"],
+                      a["weight_decay"], step_counter=self.step_counter, lr_tab=self._lr_tab())
+            return
         adam_flat_(self.p, self.gbuf[: self.P], self.m, self.v, 1, a["lr"], a["betas"], a["eps"],
-                   a["weight_decay"], step_counter=self.step_counter, lr_tab=self._lr_tab())
+                   a["weight_decay"], decoupled=self.kind == "adamw", step_counter=self.step_counter,
+                   lr_tab=self._lr_tab())
 
     def _get_graph(self, n_items: int, C: int, loss_out: torch.Tensor):
         key = (n_items, C, loss_out.data_ptr())

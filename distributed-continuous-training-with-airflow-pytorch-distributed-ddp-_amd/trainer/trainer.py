@@ -32,7 +32,7 @@ from ..data.sampler import distributed_indices
 from ..ops.fused_mlp import check_accumulate
 from ..ops.optim import check_clip_args
 from ..parallel.dist import DistContext, init_distributed, shutdown
-from .engines import AutogradEngine, FusedMLPEngine, adam_hparams_of
+from .engines import AutogradEngine, FusedMLPEngine, adam_hparams_of, optim_hparams_of
 from .graph_engine import GraphMLPEngine
 from .lr_schedule import LrSchedule, parse_configure_optimizers
 from ..utils.debug import assert_reducer_ordering
@@ -252,6 +252,12 @@ class Trainer:
         optimizers = model.configure_optimizers()
         torch_opt, sched_cfg = parse_configure_optimizers(optimizers)  # (ValueError: > 1 optimizer / scheduler)
         adam = adam_hparams_of(torch_opt)
+        # AdamW / SGD (optim_hparams_of): the fused engine applies them in the batch-tiled trainer's fold, at any batch
+        # that plan takes - also above 16, where the graph engine would take an Adam model: it knows only Adam.  The
+        # kind reaches FusedMLPEngine.applicable as a keyword, and only when it is not Adam.
+        hp = adam if adam is not None else optim_hparams_of(torch_opt)
+        kind = (hp or {}).get("kind", "adam")
+        other = dict(optimizer=kind) if kind != "adam" else {}
         clip = dict(gradient_clip_val=self.gradient_clip_val, gradient_clip_algorithm=self.gradient_clip_algorithm)
         if self.gradient_clip_val is not None and choice == "fused":
             raise RuntimeError("engine='fused' cannot clip gradients: the persistent small-MLP kernels apply Adam "
@@ -265,17 +271,17 @@ class Trainer:
             raise RuntimeError("engine='graph' cannot accumulate gradients: the wide-MLP executor runs one batch per "
                                "optimizer step (use engine='auto', 'fused' or 'autograd' with accumulate_grad_batches)")
         if K > 1:
-            fused_ok = adam is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size, K)
+            fused_ok = hp is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size, K, **other)
         else:
-            fused_ok = adam is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size)
+            fused_ok = hp is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size, **other)
         if self.gradient_clip_val is not None:
             fused_ok = False  # clipping: the graph engine where it applies, otherwise autograd
-        if (choice == "auto" and fused_ok and batch_size > 16 and K == 1
+        if (choice == "auto" and fused_ok and batch_size > 16 and K == 1 and not other
                 and GraphMLPEngine.applicable(model, ctx.device, batch_size)):
             fused_ok = False  # batch > 16: the graph engine keeps the models it takes; the batch-tiled trainer the rest
         if choice in ("auto", "fused") and fused_ok:
             sched = dict(lr_schedule=LrSchedule.from_config(torch_opt, sched_cfg)) if sched_cfg is not None else {}
-            return FusedMLPEngine(model, ctx, batch_size, seed, adam, steps_per_launch=self.steps_per_launch, **sched,
+            return FusedMLPEngine(model, ctx, batch_size, seed, hp, steps_per_launch=self.steps_per_launch, **sched,
                                   **acc)
         if choice == "fused":
             raise RuntimeError("engine='fused' requested but the model/device/batch is not supported by it")

@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import dct_amd  # noqa: E402
 from dct_amd.ckpt import ModelCheckpoint, resume_checkpoint  # noqa: E402
-from dct_amd.config import balanced_class_weight, default_config, parse_class_weight  # noqa: E402
+from dct_amd.config import balanced_class_weight, default_config, optimizer_kwargs, parse_class_weight  # noqa: E402
 from dct_amd.data.dataset import TensorPairDataset, WeatherDataset  # noqa: E402
 from dct_amd.models import build_model  # noqa: E402
 from dct_amd.tracking import MLFlowLogger  # noqa: E402
@@ -36,6 +36,11 @@ def parse_args(argv=None):
     p.add_argument("--epochs", type=int, default=cfg.train.max_epochs)
     p.add_argument("--batch-size", type=int, default=cfg.data.batch_size)
     p.add_argument("--lr", type=float, default=cfg.optim.lr)
+    p.add_argument("--optimizer", default=cfg.optim.name, choices=("adam", "adamw", "sgd"),
+                   help="torch.optim.Adam, AdamW or SGD (MLP family; default adam)")
+    p.add_argument("--weight-decay", type=float, default=cfg.optim.weight_decay)
+    p.add_argument("--momentum", type=float, default=cfg.optim.momentum, help="SGD momentum (default 0)")
+    p.add_argument("--nesterov", action="store_true", default=cfg.optim.nesterov, help="SGD: Nesterov momentum")
     p.add_argument("--gradient-clip-val", type=float, default=cfg.optim.gradient_clip_val,
                    help="clip gradients before the optimizer step (default: no clipping)")
     p.add_argument("--gradient-clip-algorithm", default=cfg.optim.gradient_clip_algorithm, choices=("norm", "value"),
@@ -62,6 +67,16 @@ def parse_args(argv=None):
                    help="directory: every rank writes its final flat parameters to params_rank<R>.json "
                         "(replica-consistency checks in tests)")
     return p.parse_args(argv)
+
+
+def model_optim_kwargs(a) -> dict:
+    """The model's optimizer keywords of the parsed flags: the config's optimizer section with the flags laid over it,
+    reduced to what differs from plain Adam (nothing for the default command line)."""
+    import dataclasses
+
+    optim = dataclasses.replace(default_config().optim, name=a.optimizer, weight_decay=a.weight_decay,
+                                momentum=a.momentum, nesterov=a.nesterov)
+    return optimizer_kwargs(optim)
 
 
 def main(argv=None) -> int:
@@ -103,7 +118,7 @@ def main(argv=None) -> int:
         loss_kw["class_weight"] = class_weight
     if a.label_smoothing:
         loss_kw["label_smoothing"] = a.label_smoothing
-    model = build_model(a.model, input_dim, lr=a.lr, **loss_kw)
+    model = build_model(a.model, input_dim, lr=a.lr, **loss_kw, **model_optim_kwargs(a))
 
     world_size = int(os.environ.get("WORLD_SIZE", 1))
     trainer = Trainer(
