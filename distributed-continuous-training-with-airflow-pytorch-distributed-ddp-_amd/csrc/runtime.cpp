@@ -25,7 +25,11 @@
 namespace dct {
 
 static void hip_check(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+  if (e == hipSuccess) return;
+  // the exception carries the error: take it out of HIP's per-thread last-error slot, or the launch
+  // check of the caller's next, unrelated kernel (torch's after every launch) reports it once more
+  (void)hipGetLastError();
+  throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 static void nccl_check(ncclResult_t r, const char* what) {
   if (r != ncclSuccess) throw std::runtime_error(std::string(what) + ": " + ncclGetErrorString(r));
@@ -109,10 +113,24 @@ void Comm::all_gather(uintptr_t send, uintptr_t recv, int64_t send_count, int dt
 }
 
 // ------------------------------------------------------------------------- BucketReducer
-uintptr_t cu_masked_stream(const std::vector<uint32_t>& mask) {
+// The mask's bits are the driver's, not "CU k of XCD x": on a device of several XCDs they interleave
+// the XCDs (bit i is a CU of XCD i % 8 on the MI355X's 8 x 32 CUs), and a queue runs on every XCD, so
+// a mask needs a CU on each of them.  A driver may refuse one that leaves an XCD empty (bits 0, 32,
+// .., 224 are eight CUs of XCD 0), and the runtime reports the queue it did not get as "out of memory".
+static hipStream_t masked_stream(const std::vector<uint32_t>& mask) {
   hipStream_t s = nullptr;
-  hip_check(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()), "hipExtStreamCreateWithCUMask");
-  return reinterpret_cast<uintptr_t>(s);
+  const hipError_t e = hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data());
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    throw std::runtime_error(std::string("hipExtStreamCreateWithCUMask: ") + hipGetErrorString(e) +
+                             " (no queue with this CU mask: mask bit i is a CU of XCD i % number of XCDs, and every "
+                             "XCD needs at least one)");
+  }
+  return s;
+}
+
+uintptr_t cu_masked_stream(const std::vector<uint32_t>& mask) {
+  return reinterpret_cast<uintptr_t>(masked_stream(mask));
 }
 
 void stream_destroy(uintptr_t stream) { hip_check(hipStreamDestroy(reinterpret_cast<hipStream_t>(stream)), "hipStreamDestroy"); }
@@ -271,8 +289,7 @@ void BucketReducer::reset_timing() {
 }
 
 void BucketReducer::set_comm_cu_mask(const std::vector<uint32_t>& mask) {
-  hipStream_t s = nullptr;
-  hip_check(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()), "hipExtStreamCreateWithCUMask");
+  hipStream_t s = masked_stream(mask);
   hip_check(hipStreamSynchronize(comm_stream_), "hipStreamSynchronize");
   hip_check(hipStreamDestroy(comm_stream_), "hipStreamDestroy");
   comm_stream_ = s;

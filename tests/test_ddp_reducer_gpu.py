@@ -85,7 +85,11 @@ def test_tabular_reducer_on_reserved_cus(cuda, monkeypatch):
     """CU reservation (profiles/ddp_reducer_cu_reservation_r6.log): the step on a stream masked to every
     CU but 8, the reducer's collectives on a stream masked to those 8 (no collective kernel can share a
     CU with the backward's LDS-DMA GEMM tiles).  The masks round-trip, the reducer reports the
-    reserved set, and training follows the no-reducer trajectory as in (a)."""
+    reserved set, and training follows the no-reducer trajectory as in (a).
+
+    The reserved 8 are mask bits 0..7, one CU of each XCD: the mask interleaves the XCDs (bit i is a CU
+    of XCD i % 8), a queue runs on all of them, and a driver may refuse a mask that leaves an XCD
+    without a CU - bits 0, 32, .., 224, eight CUs of XCD 0, are such a mask."""
     from dct_amd.ops._native import native
 
     nat = native()
@@ -94,7 +98,7 @@ def test_tabular_reducer_on_reserved_cus(cuda, monkeypatch):
     words = (ncu + 31) // 32
     full = [0xFFFFFFFF if 32 * (w + 1) <= ncu else (1 << (ncu - 32 * w)) - 1 for w in range(words)]
     comm = [0] * words
-    for c in range(0, ncu, ncu // 8):
+    for c in range(8):
         comm[c // 32] |= 1 << (c % 32)
     compute = [f & ~c for f, c in zip(full, comm)]
     h = nat.cu_masked_stream(compute)
@@ -125,6 +129,19 @@ def test_tabular_reducer_on_reserved_cus(cuda, monkeypatch):
     finally:
         torch.cuda.synchronize()
         nat.stream_destroy(h)
+
+
+def test_refused_cu_mask_leaves_no_stale_hip_error(cuda):
+    """A refused mask (an empty one: hipErrorInvalidValue on any driver) is a RuntimeError and nothing
+    else: the error does not stay in HIP's last-error slot, where torch's check of the next kernel
+    launch would report it against that kernel."""
+    from dct_amd.ops._native import native
+
+    with pytest.raises(RuntimeError, match="hipExtStreamCreateWithCUMask"):
+        native().cu_masked_stream([])
+    x = torch.zeros(4, device=cuda) + 1.0
+    torch.cuda.synchronize()
+    assert x.sum().item() == 4.0
 
 
 def _tt(forced, monkeypatch, defer="1", steps=10, B=128, groups="1"):
