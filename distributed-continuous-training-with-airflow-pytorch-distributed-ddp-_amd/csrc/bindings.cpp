@@ -82,7 +82,7 @@ static int optimizer_kind(const std::string& name) {
 // with every buffer the description implies bound.
 static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, int rank, int loss_kind, bool prof,
                                    bool cursor, bool stage, bool pending, bool aligned, bool weighted,
-                                   int accumulate, const std::string& optimizer = "adam") {
+                                   int accumulate, const std::string& optimizer = "adam", bool clipped = false) {
   dct::MlpLaunchKey k{};
   k.B = batch; k.mode = mode; k.steps = steps; k.loss_kind = loss_kind;
   k.xg_world = world; k.xg_rank = rank;
@@ -94,11 +94,12 @@ static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, in
   k.weighted = weighted;
   k.accum = accumulate > 1 ? accumulate : 0;
   k.other_opt = mode == 0 && optimizer_kind(optimizer) != dct::MLP_OPT_ADAM;
+  k.clipped = mode == 0 && clipped;
   return k;
 }
 
-// Validated MlpArgs of a training launch (the kernels trust their arguments).
-static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t grad_out,
+// Validated arguments of a training launch (the kernels trust their arguments).
+static dct::MlpClipArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t grad_out,
                                     uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items, int B, int steps,
                                     int t0, float lr, float b1, float b2, float eps, float wd, float dropout,
                                     uint32_t seed, uint32_t step_base, uintptr_t loss_out, int mode, int loss_kind,
@@ -106,13 +107,14 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
                                     uintptr_t stage, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
                                     uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t class_w = 0,
                                     float label_smooth = 0.f, int accum = 1, const std::string& optimizer = "adam",
-                                    float momentum = 0.f, float dampening = 0.f, bool nesterov = false) {
+                                    float momentum = 0.f, float dampening = 0.f, bool nesterov = false,
+                                    int clip_kind = 0, float clip_val = 0.f) {
   if (!plan.supported) throw std::runtime_error("MLP too large for the fused kernel");
   if (steps < 1 || n_items < 1 || B < 1) throw std::invalid_argument("empty launch");
   if (accum < 1) throw std::invalid_argument("accumulate must be >= 1");
   // (with accumulation a step is a window of accum batches)
   if (!cursor && (int64_t)(steps - 1) * B * accum >= n_items) throw std::invalid_argument("more steps than batches");
-  dct::MlpArgs a{};
+  dct::MlpClipArgs a{};
   a.accum = accum;
   a.p = P<float>(p);
   a.m = P<float>(mo);
@@ -170,6 +172,13 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
   } else {
     a.opt_kind = dct::MLP_OPT_ADAM;
   }
+  // gradient clipping of a train-mode launch (grad mode ignores it: its launches keep the unclipped key)
+  if (mode == 0 && clip_kind != dct::MLP_CLIP_OFF) {
+    a.clip_kind = clip_kind;
+    a.clip_val = clip_val;
+    if (!dct::mlp_tile_clip_ok(a))
+      throw std::invalid_argument("clip_kind must be 0 (off), 1 (norm) or 2 (value) with a finite clip_val > 0");
+  }
   // a request no trainer of this plan serves is an invalid argument; a chosen trainer's own refusal of
   // the arguments surfaces in launch_train
   const dct::MlpChoice c = plan.select(dct::mlp_launch_key(a));
@@ -183,7 +192,7 @@ static dct::MlpArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t 
   return a;
 }
 
-static void launch_train(const MlpPlan& plan, dct::MlpArgs& a, uintptr_t stream) {
+static void launch_train(const MlpPlan& plan, dct::MlpClipArgs& a, uintptr_t stream) {
   const dct::MlpShape* sh = plan.sh();
   void* st = reinterpret_cast<void*>(stream);
   const dct::MlpChoice c = plan.select(dct::mlp_launch_key(a));
@@ -218,7 +227,7 @@ static void launch_train(const MlpPlan& plan, dct::MlpArgs& a, uintptr_t stream)
 // keyword arguments and the Python-side operand checks.
 struct MlpLaunch {
   MlpPlan plan;
-  dct::MlpArgs base{};
+  dct::MlpClipArgs base{};
   int64_t n_items = 0;   // index entries bound at base.idx
   int64_t loss_len = 0;  // loss slots bound at base.loss_out (0 = none)
   void run(int first_step, int steps, uintptr_t stream) const {
@@ -227,7 +236,7 @@ struct MlpLaunch {
     const int64_t off = (int64_t)first_step * rows;
     if (off + (int64_t)(steps - 1) * rows >= n_items) throw std::invalid_argument("MlpLaunch.run: past the index list");
     if (base.loss_out && first_step + steps > loss_len) throw std::invalid_argument("MlpLaunch.run: past the loss buffer");
-    dct::MlpArgs a = base;
+    dct::MlpClipArgs a = base;
     a.idx = base.idx + off;
     a.n_items = (int)(n_items - off);
     a.steps = steps;
@@ -310,35 +319,36 @@ PYBIND11_MODULE(_dct_native, m) {
       // "block3", "lds", "tile" or "none".  `aligned`: the flat buffers lie on 16-byte boundaries; `weighted`: class
       // weights or label smoothing are on (the batch-tiled trainer's plan only); `accumulate`: micro-batches per
       // optimizer step (> 1: the batch-tiled trainer's plan only, within its slot cap); `optimizer`: "adam", "adamw"
-      // or "sgd" (a train-mode launch of the last two: the batch-tiled trainer's plan only).  No device needed.
+      // or "sgd" (a train-mode launch of the last two: the batch-tiled trainer's plan only); `clipped`: a train-mode
+      // launch that clips its gradient (by norm or by value: the batch-tiled trainer's plan only).  No device needed.
 #define MLP_QUERY_ARGS                                                                                              \
   py::arg("batch"), py::arg("mode") = 0, py::arg("steps") = 1, py::arg("world") = 1, py::arg("rank") = 0,           \
       py::arg("loss_kind") = 0, py::arg("prof") = false, py::arg("cursor") = false, py::arg("stage") = false,       \
       py::arg("pending") = false, py::arg("aligned") = true, py::arg("weighted") = false,                           \
-      py::arg("accumulate") = 1, py::arg("optimizer") = "adam"
+      py::arg("accumulate") = 1, py::arg("optimizer") = "adam", py::arg("clipped") = false
       .def("trainer", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
                          bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted,
-                         int accumulate, const std::string& optimizer) {
+                         int accumulate, const std::string& optimizer, bool clipped) {
         return std::string(dct::mlp_trainer_name(
             plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
-                                  weighted, accumulate, optimizer))
+                                  weighted, accumulate, optimizer, clipped))
                 .trainer));
       }, MLP_QUERY_ARGS)
       // whether that launch reads its staged-batch buffer (the wave kernels and mlp_block5's grad mode do)
       .def("uses_stage", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
                             bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted,
-                            int accumulate, const std::string& optimizer) {
+                            int accumulate, const std::string& optimizer, bool clipped) {
         return plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
-                                     weighted, accumulate, optimizer))
+                                     weighted, accumulate, optimizer, clipped))
             .use_stage;
       }, MLP_QUERY_ARGS)
       // one trainer's own predicate on that launch, whatever the selector would choose first (tests): "block5",
       // "block5_xg", "block3", "wave_rows", "wave_xg"
       .def("takes", [](const MlpPlan& plan, const std::string& which, int batch, int mode, int steps, int world,
                        int rank, int loss_kind, bool prof, bool cursor, bool stage, bool pending, bool aligned,
-                       bool weighted, int accumulate, const std::string& optimizer) {
+                       bool weighted, int accumulate, const std::string& optimizer, bool clipped) {
         const dct::MlpLaunchKey k = query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending,
-                                              aligned, weighted, accumulate, optimizer);
+                                              aligned, weighted, accumulate, optimizer, clipped);
         const dct::MlpShape& sh = *plan.sh();
         if (which == "block5") return dct::mlp_block5_takes(sh, k);
         if (which == "block5_xg") return dct::mlp_block5_xg_shape_ok(sh, k);
@@ -357,14 +367,17 @@ PYBIND11_MODULE(_dct_native, m) {
              uintptr_t stage, uintptr_t stream, uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank,
              uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t tile_ws, int64_t tile_ws_floats,
              uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate, const std::string& optimizer,
-             float momentum, float dampening, bool nesterov) {
+             float momentum, float dampening, bool nesterov, int clip_kind, float clip_val, uintptr_t clip_ws,
+             int64_t clip_ws_floats) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
-            dct::MlpArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
-                                                   b1, b2, eps, wd, dropout, seed, step_base, loss_out, mode,
-                                                   loss_kind, step_counter, cursor, prof, pending, stage, xg_recv,
-                                                   xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll,
-                                                   class_w, label_smooth, accumulate, optimizer, momentum,
-                                                   dampening, nesterov);
+            dct::MlpClipArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
+                                                 b1, b2, eps, wd, dropout, seed, step_base, loss_out, mode, loss_kind,
+                                                 step_counter, cursor, prof, pending, stage, xg_recv, xg_peers,
+                                                 xg_world, xg_rank, xg_status, xg_timeout, xg_poll, class_w,
+                                                 label_smooth, accumulate, optimizer, momentum, dampening, nesterov,
+                                                 clip_kind, clip_val);
+            a.clip_ws = P<float>(clip_ws);
+            a.clip_ws_floats = clip_ws_floats;
             a.tile_ws = P<float>(tile_ws);
             a.tile_ws_floats = tile_ws_floats;
             a.lr_tab = P<const float>(lr_tab);
@@ -380,7 +393,8 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0, py::arg("lr_tab") = (uintptr_t)0,
           py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f, py::arg("accumulate") = 1,
           py::arg("optimizer") = "adam", py::arg("momentum") = 0.f, py::arg("dampening") = 0.f,
-          py::arg("nesterov") = false)
+          py::arg("nesterov") = false, py::arg("clip_kind") = 0, py::arg("clip_val") = 0.f,
+          py::arg("clip_ws") = (uintptr_t)0, py::arg("clip_ws_floats") = 0)
       .def(
           "prepare_train",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t X, int ldx, uintptr_t Y,
@@ -389,13 +403,17 @@ PYBIND11_MODULE(_dct_native, m) {
              uintptr_t xg_recv, uintptr_t xg_peers, int xg_world, int xg_rank, uintptr_t xg_status,
              int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks, uintptr_t tile_ws, int64_t tile_ws_floats,
              uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate, const std::string& optimizer,
-             float momentum, float dampening, bool nesterov) {
+             float momentum, float dampening, bool nesterov, int clip_kind, float clip_val, uintptr_t clip_ws,
+             int64_t clip_ws_floats) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             auto l = std::make_unique<MlpLaunch>(MlpLaunch{plan});
             l->base = make_train_args(plan, p, mo, vo, 0, X, ldx, Y, idx, n_items, B, 1, 0, lr, b1, b2, eps, wd,
                                       dropout, seed, 0, loss_out, 0, loss_kind, step_counter, 0, 0, 0, 0, xg_recv,
                                       xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll, class_w,
-                                      label_smooth, accumulate, optimizer, momentum, dampening, nesterov);
+                                      label_smooth, accumulate, optimizer, momentum, dampening, nesterov, clip_kind,
+                                      clip_val);
+            l->base.clip_ws = P<float>(clip_ws);
+            l->base.clip_ws_floats = clip_ws_floats;
             l->base.xg_ticks = P<unsigned long long>(xg_ticks);
             l->base.tile_ws = P<float>(tile_ws);
             l->base.tile_ws_floats = tile_ws_floats;
@@ -412,7 +430,8 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("xg_poll") = 0, py::arg("xg_ticks") = 0, py::arg("tile_ws") = 0, py::arg("tile_ws_floats") = 0,
           py::arg("lr_tab") = (uintptr_t)0, py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f,
           py::arg("accumulate") = 1, py::arg("optimizer") = "adam", py::arg("momentum") = 0.f,
-          py::arg("dampening") = 0.f, py::arg("nesterov") = false)
+          py::arg("dampening") = 0.f, py::arg("nesterov") = false, py::arg("clip_kind") = 0,
+          py::arg("clip_val") = 0.f, py::arg("clip_ws") = (uintptr_t)0, py::arg("clip_ws_floats") = 0)
       .def(
           "eval",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items,
@@ -463,6 +482,24 @@ PYBIND11_MODULE(_dct_native, m) {
         py::arg("step_counter") = (uintptr_t)0, py::arg("cursor") = (uintptr_t)0, py::arg("loss_slot") = (uintptr_t)0,
         py::arg("loss_out") = (uintptr_t)0, py::arg("loss_cap") = 0, py::arg("stream") = (uintptr_t)0,
         py::arg("lr_tab") = (uintptr_t)0);
+  // flat SGD on a clipped gradient: clip_coef (device, grad_clip_coef's stats + 1) / clip_value as adam_flat_step_clipped
+  m.def("sgd_flat_step_clipped",
+        [](uintptr_t p, uintptr_t g, uintptr_t mo, int64_t n, float lr, float momentum, float dampening, bool nesterov,
+           float wd, int64_t t, float grad_scale, uintptr_t step_counter, uintptr_t cursor, uintptr_t loss_slot,
+           uintptr_t loss_out, int loss_cap, uintptr_t clip_coef, float clip_value, uintptr_t stream,
+           uintptr_t lr_tab) {
+          check(dct_sgd_flat_step_clipped(P<float>(p), P<const float>(g), P<float>(mo), n, lr, momentum, dampening,
+                                          nesterov ? 1 : 0, wd, t, grad_scale, P<const int>(step_counter),
+                                          P<int>(cursor), P<const float>(loss_slot), P<float>(loss_out), loss_cap,
+                                          P<const float>(lr_tab), P<const float>(clip_coef), clip_value,
+                                          reinterpret_cast<void*>(stream)),
+                "sgd_flat_step_clipped");
+        },
+        py::arg("p"), py::arg("g"), py::arg("m"), py::arg("n"), py::arg("lr"), py::arg("momentum"),
+        py::arg("dampening"), py::arg("nesterov"), py::arg("wd"), py::arg("t"), py::arg("grad_scale"),
+        py::arg("step_counter") = (uintptr_t)0, py::arg("cursor") = (uintptr_t)0, py::arg("loss_slot") = (uintptr_t)0,
+        py::arg("loss_out") = (uintptr_t)0, py::arg("loss_cap") = 0, py::arg("clip_coef") = (uintptr_t)0,
+        py::arg("clip_value") = 0.f, py::arg("stream") = (uintptr_t)0, py::arg("lr_tab") = (uintptr_t)0);
   m.def("xg_adam_buffer_bytes", &dct_xg_adam_buffer_bytes, py::arg("n"), py::arg("world"));
   m.def(
       "xg_allreduce_adam",
@@ -1026,6 +1063,14 @@ PYBIND11_MODULE(_dct_native, m) {
     return (int64_t)dct_mlp_tile_ws_floats_accum(dims.data(), (int)dims.size() - 1, B, accumulate);
   });
   m.def("mlp_tile_max_slots", []() { return dct_mlp_tile_max_slots(); });
+  // floats of a norm-clipped launch's clip_ws: the folded gradient, the workgroups' partial sums and {norm, coef}
+  m.def("mlp_tile_clip_ws_floats", [](const std::vector<int>& dims) {
+    return (int64_t)dct_mlp_tile_clip_ws_floats(dims.data(), (int)dims.size() - 1);
+  }, py::arg("dims"));
+  // word offset of {norm, coef} in it
+  m.def("mlp_tile_clip_stats_offset", [](const std::vector<int>& dims) {
+    return (int64_t)dct_mlp_tile_clip_ws_floats(dims.data(), (int)dims.size() - 1) - 4;
+  }, py::arg("dims"));
   // the batch-tiled trainer's own predicate (mlp_select.h): `accumulate` micro-batches of `batch` rows fit the cap
   m.def("mlp_tile_window_ok", [](int batch, int accumulate) { return dct::mlp_tile_window_ok(batch, accumulate); },
         py::arg("batch"), py::arg("accumulate"));

@@ -258,6 +258,14 @@ int dct_adam_flat_step_parts_lr(float* p, const float* g, float* m, float* v, ui
 int dct_sgd_flat_step(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,
                       int nesterov, float wd, int64_t t, float grad_scale, const int* step_counter, int* cursor,
                       const float* loss_slot, float* loss_out, int loss_cap, const float* lr_tab, void* stream);
+// dct_sgd_flat_step on a clipped gradient, clip_coef / clip_value as dct_adam_flat_step_clipped: grad_scale is
+// multiplied by *clip_coef (optional, read on the device), then clip_value > 0 clamps the scaled g to
+// [-clip_value, clip_value] - before the coupled wd p is added.  g itself is not rewritten.  Null clip_coef and
+// clip_value == 0: dct_sgd_flat_step itself.  hipErrorInvalidValue also for clip_value < 0.
+int dct_sgd_flat_step_clipped(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,
+                              int nesterov, float wd, int64_t t, float grad_scale, const int* step_counter,
+                              int* cursor, const float* loss_slot, float* loss_out, int loss_cap, const float* lr_tab,
+                              const float* clip_coef, float clip_value, void* stream);
 int dct_f32_to_bf16(const float* in, uint16_t* out, int64_t n, void* stream);
 // device-side barrier of the xGMI peer exchange (step_kernels.hip; barrier slots at byte offset off)
 int dct_xg_barrier(void* recv, void* const* peers, int64_t off, unsigned* status, int world, int rank, unsigned tag,

@@ -162,6 +162,27 @@ struct MlpArgs : MlpStepArgs {
 
 enum MlpOptimizer { MLP_OPT_ADAM = 0, MLP_OPT_ADAMW = 1, MLP_OPT_SGD = 2 };
 
+// MlpClipArgs: MlpArgs with the optional gradient-clipping fields of a train-mode launch after `nesterov` (batch-tiled
+// trainer only).  What the host builds and hands to the launchers; every kernel but the batch-tiled trainer's clipped
+// folds takes its MlpArgs / MlpStepArgs prefix, so an unclipped launch runs on the kernel-argument segments it had.
+// Clipping acts on the step's final gradient word - after the fold's tile-order sum, the weighted / W and the window's
+// 1 / accum, before anything the optimizer adds (coupled wd p, AdamW's decay of p):
+//   MLP_CLIP_NORM   g *= min(clip_val / (sqrt(sum_{e < P} g_e^2) + 1e-6), 1)  (torch.nn.utils.clip_grad_norm_; the
+//                   product is taken also when the coefficient is 1, where it is exact)
+//   MLP_CLIP_VALUE  g = clamp(g, -clip_val, clip_val)                         (clip_grad_value_)
+// The loss word is never part of the norm and never clipped.  Grad-mode launches ignore these fields (grad_out is the
+// unclipped gradient).  clip_ws (norm only): dct_mlp_tile_clip_ws_floats(dims, L) floats on a 16-byte boundary -
+// the folded gradient gf[P + 1], one partial sum of squares per fold workgroup and the step's {norm, coef}.
+// mlp_select.h refuses a clipped launch on every other trainer.
+struct MlpClipArgs : MlpArgs {
+  int clip_kind;
+  float clip_val;
+  float* clip_ws;
+  long long clip_ws_floats;
+};
+
+enum MlpClip { MLP_CLIP_OFF = 0, MLP_CLIP_NORM = 1, MLP_CLIP_VALUE = 2 };
+
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
 
 // One launch of the batch-tiled inference kernel (mlp_infer.hip): forward only, rows 0 .. n - 1 of the index
@@ -231,7 +252,12 @@ long long dct_mlp_tile_ws_floats(const int* dims, int L, int B);
 // dct_mlp_tile_max_slots() of them (0: over the cap, or not a tile shape / batch); accum <= 1 is the value above
 long long dct_mlp_tile_ws_floats_accum(const int* dims, int L, int B, int accum);
 int dct_mlp_tile_max_slots(void);
-int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream);
+// floats of MlpClipArgs::clip_ws (clipping by norm): gf[P + 1], part[ceil((P + 1) / 256)] and {norm, coef}, each on a
+// 16-byte boundary (0: not a tile shape)
+long long dct_mlp_tile_clip_ws_floats(const int* dims, int L);
+// hipErrorInvalidValue also for an unknown clip_kind, a clip_val that is not a finite value > 0 while the kind is set,
+// and norm clipping without a clip_ws of that size (train mode; grad mode ignores the clip fields)
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpClipArgs* a, void* stream);
 // batch-tiled forward-only inference (mlp_infer.hip); grid <= 0: default.  It and dct_mlp_tile_train share one
 // forward and one host check (mlp_tile_fwd.h): the shapes of dct_mlp_tile_supported, p on a 16-byte boundary
 int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, void* stream);

@@ -32,8 +32,11 @@ struct MlpLaunchKey {
   int accum;        // MlpArgs::accum when > 1 (gradient accumulation on: only the batch-tiled trainer runs windows), else 0
   bool other_opt;   // a train-mode launch whose MlpArgs::opt_kind is not Adam (AdamW, SGD): only the batch-tiled
                     // trainer's fold applies those; grad-mode launches apply no optimizer and never set it
+  bool clipped;     // a train-mode launch with MlpClipArgs::clip_kind set: only the batch-tiled trainer clips the
+                    // gradient between its fold and its optimizer; grad-mode launches ignore the clip fields
 };
-MlpLaunchKey mlp_launch_key(const MlpArgs& a);  // the only place pointers become bools
+MlpLaunchKey mlp_launch_key(const MlpArgs& a);  // the only place pointers become bools (clipped: false)
+MlpLaunchKey mlp_launch_key(const MlpClipArgs& a);  // the same, with `clipped` from the clip fields
 
 struct MlpChoice {
   MlpTrainer trainer;
@@ -59,6 +62,9 @@ bool mlp_block3_takes(const MlpShape& sh, const MlpLaunchKey& k);
 bool mlp_tile_batch_ok(int B);
 bool mlp_tile_window_ok(int B, int accum);  // accum micro-batches of B rows fit the slot cap (accum <= 1: always)
 bool mlp_tile_optimizer_ok(const MlpArgs& a);  // a train-mode launch's optimizer fields are ones its fold applies
+// a train-mode launch's clip fields: a known kind and, while one is set, a finite clip_val > 0 (the workspace of norm
+// clipping is the launcher's to size)
+bool mlp_tile_clip_ok(const MlpClipArgs& a);
 
 }  // namespace dct
 

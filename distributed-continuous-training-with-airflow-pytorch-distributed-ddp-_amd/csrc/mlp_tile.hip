@@ -390,19 +390,72 @@ __device__ __forceinline__ float batch_mean(const MlpStepArgs& a, int cur, float
   return bs > 0 ? sum / (float)bs : 0.f;
 }
 
+// The fold's train-mode branches as a function of the gradient word g, for the norm-clipped step's apply kernel: the
+// optimizer (OPT: MlpArgs::opt_kind) on parameter e after tcur steps, statement for statement what the fold below does,
+// so a clipped step differs from an unclipped one in g alone.  (The fold keeps its own copy: calling this from it
+// reordered the Adam instantiations' bias-correction instructions, and an unclipped step's code is not to change.)
+template <int OPT, class A>
+__device__ __forceinline__ void opt_elem(const A& a, int e, float g, int tcur) {
+  if constexpr (OPT == MLP_OPT_SGD) {
+    const float lr_t = lr_for(a.lr_tab, a.lr, tcur);
+    const bool mom = a.momentum != 0.f;  // (uniform: a kernel argument)
+    float pv = a.p[e], mv = mom ? a.m[e] : 0.f;
+    sgd_elem(pv, g, mv, lr_t, a.momentum, a.dampening, a.wd, a.nesterov != 0, tcur == 0);
+    a.p[e] = pv;
+    if (mom) a.m[e] = mv;
+  } else {
+    const int t = tcur + 1;
+    const float bc1 = 1.f - pow_t(log2f(a.b1), (float)t);
+    const float bc2 = 1.f - pow_t(log2f(a.b2), (float)t);
+    const float lr_t = lr_for(a.lr_tab, a.lr, tcur);  // (next to the counter read above)
+    const float step_size = lr_t / bc1;
+    const float rbc2 = __builtin_amdgcn_rsqf(bc2);
+    float pv = a.p[e], mv = a.m[e], vv = a.v[e];
+    if (OPT == MLP_OPT_ADAMW) pv *= 1.f - lr_t * a.wd;
+    adam_elem<OPT != MLP_OPT_ADAMW>(pv, g, mv, vv, a.b1, a.b2, a.wd, step_size, rbc2, a.eps);
+    a.p[e] = pv;
+    a.m[e] = mv;
+    a.v[e] = vv;
+  }
+}
+
+// the last workgroup of a launch to arrive advances the counters (every workgroup has read them by then) and leaves
+// the arrival counter at zero, so a captured launch sequence replays
+template <class A>
+__device__ __forceinline__ void advance_counters(const A& a, unsigned int* done, int cur, int tcur) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    const unsigned int old = atomicAdd(done, 1u);
+    if (old == gridDim.x - 1) {
+      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.cursor) __hip_atomic_store(a.cursor, cur + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.step_counter) __hip_atomic_store(a.step_counter, tcur + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // One word per thread through fold_plain, or (ACC: MlpArgs::accum > 1) the accum * T slots of a window through
 // fold_window; then the optimizer (train mode) or grad_out (grad mode), the loss and the counters, which count
 // optimizer steps.  OPT (MlpArgs::opt_kind, chosen on the host like WL and ACC): MLP_OPT_ADAM is the kernel as it was;
 // MLP_OPT_ADAMW decays p by the step's rate times wd and runs adam_elem on the undecayed gradient; MLP_OPT_SGD
 // (sgd_elem) touches p and the momentum buffer m only - first step (the buffer becomes the gradient) is device step
 // count 0, the word Adam's bias correction reads.  Grad mode never reads OPT's fields: its launches use OPT = Adam.
-// The Adam instantiations take MlpStepArgs, the arguments without the optimizer's fields (mlp_fused.h): their
-// kernel-argument segment, and with it their code, is what it was before those fields existed.
-template <int OPT>
-using FoldArgs = std::conditional_t<OPT == MLP_OPT_ADAM, MlpStepArgs, MlpArgs>;
+// CLIP (MlpClipArgs::clip_kind, train mode only, chosen on the host likewise): MLP_CLIP_VALUE clamps the gradient word
+// to [-clip_val, clip_val] before the optimizer sees it (a NaN stays one); clipping by norm needs the whole gradient
+// first and is the kernel pair below, not an instantiation of this one.
+// The Adam instantiations take MlpStepArgs, the arguments without the optimizer's fields (mlp_fused.h), the other
+// unclipped ones MlpArgs, the arguments without the clip fields: their kernel-argument segment, and with it their
+// code, is what it was before those fields existed.
+template <int OPT, int CLIP = MLP_CLIP_OFF>
+using FoldArgs = std::conditional_t<CLIP != MLP_CLIP_OFF, MlpClipArgs,
+                                    std::conditional_t<OPT == MLP_OPT_ADAM, MlpStepArgs, MlpArgs>>;
+static_assert(sizeof(MlpStepArgs) == 312 && sizeof(MlpArgs) == 328,
+              "the unclipped tile kernels' kernel-argument types keep their size (README: 16 more bytes cost 1 %)");
 
-template <bool WL, bool ACC, int OPT = MLP_OPT_ADAM>
-__global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, FoldArgs<OPT> a, int T, unsigned int* done) {
+template <bool WL, bool ACC, int OPT = MLP_OPT_ADAM, int CLIP = MLP_CLIP_OFF>
+__global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, FoldArgs<OPT, CLIP> a, int T,
+                                                                unsigned int* done) {
   __shared__ int s_cnt[2];
   const int tid = threadIdx.x;
   if (tid == 0) {
@@ -415,8 +468,10 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, FoldArg
   const int e = blockIdx.x * FOLD_NT + tid;
   if (e <= tp.P) {
     // the step's gradient word (e < P) or loss word (e == P)
-    const float g = ACC ? fold_window<WL>(tp, a, T, e, cur) : fold_plain<WL>(tp, a, T, e, cur);
+    float g = ACC ? fold_window<WL>(tp, a, T, e, cur) : fold_plain<WL>(tp, a, T, e, cur);
     if (e < tp.P) {
+      if constexpr (CLIP == MLP_CLIP_VALUE)
+        if (adam) g = g > a.clip_val ? a.clip_val : (g < -a.clip_val ? -a.clip_val : g);
       if constexpr (OPT == MLP_OPT_SGD) {
         if (adam) {
           const float lr_t = lr_for(a.lr_tab, a.lr, tcur);
@@ -451,17 +506,100 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_kernel(Plan tp, FoldArg
       if (!adam) a.grad_out[tp.P] = bl;
     }
   }
-  // the last workgroup to arrive advances the counters: every workgroup has read them by then
+  advance_counters(a, done, cur, tcur);
+}
+
+// ---- clipping by norm: the fold and the optimizer as two kernels, with the global norm between them.
+// fold_norm (grid ceil((P + 1) / 256), as the fold): thread e computes its word through fold_plain / fold_window - the
+// bits a grad-mode launch writes - and stores it to gf[e] (the batch loss to gf[P]); the workgroup sums g^2 over its
+// e < P in a fixed order - wave butterfly, then the four wave sums through LDS in wave order - into part[blockIdx.x],
+// a plain vector store.  It reads the cursor (the window / live-row count of the fold) and advances nothing.
+template <bool WL, bool ACC>
+__global__ __launch_bounds__(FOLD_NT) void mlp_tile_fold_norm_kernel(Plan tp, MlpStepArgs a, int T, float* gf,
+                                                                     float* part) {
+  __shared__ int s_cur;
+  __shared__ float wsums[FOLD_NT / 64];
+  const int tid = threadIdx.x;
+  if (tid == 0) s_cur = a.cursor ? __hip_atomic_load(a.cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
   __syncthreads();
-  if (tid == 0) {
-    __threadfence();
-    const unsigned int old = atomicAdd(done, 1u);
-    if (old == gridDim.x - 1) {
-      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.cursor) __hip_atomic_store(a.cursor, cur + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.step_counter) __hip_atomic_store(a.step_counter, tcur + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int cur = s_cur;
+  const int e = blockIdx.x * FOLD_NT + tid;
+  float sq = 0.f;
+  if (e <= tp.P) {
+    const float g = ACC ? fold_window<WL>(tp, a, T, e, cur) : fold_plain<WL>(tp, a, T, e, cur);
+    if (e < tp.P) {
+      gf[e] = g;
+      sq = g * g;
+    } else {
+      gf[e] = (WL || ACC) ? g : batch_mean(a, cur, g);
     }
   }
+  sq = wave_sum(sq);
+  if ((tid & 63) == 0) wsums[tid >> 6] = sq;
+  __syncthreads();
+  if (tid == 0) {
+    float v = wsums[0];
+#pragma unroll
+    for (int w = 1; w < FOLD_NT / 64; ++w) v += wsums[w];
+    part[blockIdx.x] = v;
+  }
+}
+
+// apply (same grid, the launch behind fold_norm: the kernel boundary is what makes part[] visible across XCDs): every
+// wave sums all gridDim.x <= 84 partials itself in one fixed order - lane l adds partials l, l + 64, .., then the
+// butterfly - so every thread of the grid holds the same bits of norm and coef = min(clip_val / (norm + 1e-6), 1) with
+// no broadcast through memory or LDS; then opt_elem on gf[e] * coef (the product also at coef == 1: exact), the loss
+// word's bookkeeping and the counters as the fold.  Workgroup 0 leaves {norm, coef} in stats.
+template <int OPT>
+__global__ __launch_bounds__(FOLD_NT) void mlp_tile_apply_kernel(Plan tp, MlpClipArgs a, const float* gf,
+                                                                 const float* part, float* stats,
+                                                                 unsigned int* done) {
+  __shared__ int s_cnt[2];
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    s_cnt[0] = a.cursor ? __hip_atomic_load(a.cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    s_cnt[1] = a.step_counter ? __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.t0;
+  }
+  float t = 0.f;
+  for (unsigned int i = tid & 63; i < gridDim.x; i += 64) t += part[i];
+  t = wave_sum(t);
+  const float norm = sqrtf(t);
+  const float c = a.clip_val / (norm + 1e-6f);
+  const float coef = c > 1.0f ? 1.0f : c;  // (a NaN stays a NaN, as torch.clamp(max=1))
+  __syncthreads();
+  const int cur = s_cnt[0], tcur = s_cnt[1];
+  const int e = blockIdx.x * FOLD_NT + tid;
+  if (e < tp.P) {
+    float g;
+    {
+      // the clipped word is rounded on its own: contracted into SGD's g + wd p (fma(gf, coef, wd p)) it would not be
+      // the unclipped step's fma(wd, p, g) at coef == 1
+#pragma clang fp contract(off)
+      g = gf[e] * coef;
+    }
+    opt_elem<OPT>(a, e, g, tcur);
+  } else if (e == tp.P) {  // the fold's loss bookkeeping of a train-mode launch; gf[P] is the batch loss
+    if (a.cursor && cur > 0 && a.loss_out) a.loss_out[cur - 1] = a.grad_out[tp.P];
+    if (a.loss_out && !a.cursor) a.loss_out[0] = gf[e];
+  }
+  if (blockIdx.x == 0 && tid == 0) {
+    stats[0] = norm;
+    stats[1] = coef;
+  }
+  advance_counters(a, done, cur, tcur);
+}
+
+// clip_ws carve (floats, every part on a 16-byte boundary): gf[P + 1] | part[G] | {norm, coef}
+struct ClipWs {
+  int part, stats, total;
+};
+__host__ inline ClipWs clip_ws_layout(const Plan& tp) {
+  ClipWs o;
+  const int G = (tp.P + 1 + FOLD_NT - 1) / FOLD_NT;
+  o.part = (tp.P + 1 + 3) & ~3;
+  o.stats = o.part + ((G + 3) & ~3);
+  o.total = o.stats + 4;
+  return o;
 }
 
 // the fold of a launch: the Adam instantiation (the kernel as it was, on the kernel arguments it always had) for Adam
@@ -480,8 +618,39 @@ static void launch_fold(int grid, const Plan& tp, const MlpArgs& a, int T, unsig
   }
 }
 
-template <int L, bool WL, bool ACC>
-static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* done, hipStream_t st) {
+// what follows the step kernel of a clipped train-mode launch: by value the fold's clamping instantiation, by norm
+// fold_norm + apply over the launch's clip_ws
+template <bool WL, bool ACC>
+static void launch_fold_clipped(int grid, const Plan& tp, const MlpClipArgs& a, int T, unsigned int* done,
+                                hipStream_t st) {
+  const dim3 g(grid), b(FOLD_NT);
+  if (a.clip_kind == MLP_CLIP_VALUE) {
+    if (a.opt_kind == MLP_OPT_ADAM)
+      hipLaunchKernelGGL((mlp_tile_fold_kernel<WL, ACC, MLP_OPT_ADAM, MLP_CLIP_VALUE>), g, b, 0, st, tp, a, T, done);
+    else if (a.opt_kind == MLP_OPT_ADAMW)
+      hipLaunchKernelGGL((mlp_tile_fold_kernel<WL, ACC, MLP_OPT_ADAMW, MLP_CLIP_VALUE>), g, b, 0, st, tp, a, T, done);
+    else
+      hipLaunchKernelGGL((mlp_tile_fold_kernel<WL, ACC, MLP_OPT_SGD, MLP_CLIP_VALUE>), g, b, 0, st, tp, a, T, done);
+    return;
+  }
+  const ClipWs cw = clip_ws_layout(tp);
+  float* gf = a.clip_ws;
+  float* part = a.clip_ws + cw.part;
+  float* stats = a.clip_ws + cw.stats;
+  const MlpStepArgs& base = a;
+  hipLaunchKernelGGL((mlp_tile_fold_norm_kernel<WL, ACC>), g, b, 0, st, tp, base, T, gf, part);
+  if (a.opt_kind == MLP_OPT_ADAM)
+    hipLaunchKernelGGL((mlp_tile_apply_kernel<MLP_OPT_ADAM>), g, b, 0, st, tp, a, gf, part, stats, done);
+  else if (a.opt_kind == MLP_OPT_ADAMW)
+    hipLaunchKernelGGL((mlp_tile_apply_kernel<MLP_OPT_ADAMW>), g, b, 0, st, tp, a, gf, part, stats, done);
+  else
+    hipLaunchKernelGGL((mlp_tile_apply_kernel<MLP_OPT_SGD>), g, b, 0, st, tp, a, gf, part, stats, done);
+}
+
+// CLIPPED: a train-mode launch with a clip kind set - the same step kernel, launch_fold_clipped behind it
+template <int L, bool WL, bool ACC, bool CLIPPED = false>
+static hipError_t launch_steps(const Plan& tp, const std::conditional_t<CLIPPED, MlpClipArgs, MlpArgs>& a0,
+                               unsigned int* done, hipStream_t st) {
   const int T = (a0.B + R - 1) / R;
   const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
   auto fn = mlp_tile_step_kernel<L, WL, ACC>;
@@ -490,7 +659,7 @@ static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* 
   if (e != hipSuccess) return e;
   const int fold_grid = (tp.P + 1 + FOLD_NT - 1) / FOLD_NT;
   for (int s = 0; s < a0.steps; ++s) {
-    MlpArgs a = a0;
+    auto a = a0;
     a.steps = 1;
     a.idx = a0.idx + (size_t)s * AK * a0.B;
     a.n_items = a0.n_items - s * AK * a0.B;
@@ -498,10 +667,15 @@ static hipError_t launch_steps(const Plan& tp, const MlpArgs& a0, unsigned int* 
     a.step_base = a0.step_base + (uint32_t)s;
     if (a0.loss_out && !a0.cursor) a.loss_out = a0.loss_out + s;
     hipLaunchKernelGGL(fn, dim3(T, AK), dim3(NT), bytes, st, tp, a);
-    launch_fold<WL, ACC>(fold_grid, tp, a, T, done, st);
+    if constexpr (CLIPPED) launch_fold_clipped<WL, ACC>(fold_grid, tp, a, T, done, st);
+    else launch_fold<WL, ACC>(fold_grid, tp, a, T, done, st);
   }
   return hipGetLastError();
 }
+
+// the clipped launches' dispatch (defined behind dct_mlp_tile_train: their instantiations follow the unclipped ones)
+static hipError_t train_clipped(const Plan& tp, const MlpClipArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                                hipStream_t st);
 
 }  // namespace tile
 
@@ -521,6 +695,12 @@ bool mlp_tile_optimizer_ok(const MlpArgs& a) {
   if (!(a.momentum >= 0.f)) return false;
   if (a.nesterov && (a.momentum <= 0.f || a.dampening != 0.f)) return false;
   return a.momentum == 0.f || a.m;
+}
+
+bool mlp_tile_clip_ok(const MlpClipArgs& a) {
+  if (a.mode != 0 || a.clip_kind == MLP_CLIP_OFF) return true;
+  if (a.clip_kind != MLP_CLIP_NORM && a.clip_kind != MLP_CLIP_VALUE) return false;
+  return a.clip_val > 0.f && a.clip_val <= 3.402823466e38f;  // finite and > 0 (a NaN fails the first comparison)
 }
 
 }  // namespace dct
@@ -550,7 +730,12 @@ long long dct_mlp_tile_ws_floats_accum(const int* dims, int L, int B, int accum)
 
 int dct_mlp_tile_max_slots(void) { return dct::tile::MAX_SLOTS; }
 
-int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stream) {
+long long dct_mlp_tile_clip_ws_floats(const int* dims, int L) {
+  dct::tile::Plan tp;
+  return dct::tile::make_plan(&tp, dims, L) ? dct::tile::clip_ws_layout(tp).total : 0;
+}
+
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpClipArgs* a, void* stream) {
   dct::tile::Plan tp;
   if (!dct::tile::plan_launch(&tp, dims, L, a->p)) return (int)hipErrorInvalidValue;
   if (a->B < 1 || a->B > dct::tile::BMAX || a->steps < 1 || a->n_items < 1) return (int)hipErrorInvalidValue;
@@ -567,6 +752,13 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stre
   unsigned int* done = reinterpret_cast<unsigned int*>(a->tile_ws + (a->tile_ws_floats - 4));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool wl = a->class_w || a->label_smooth != 0.f;
+  if (!dct::mlp_tile_clip_ok(*a)) return (int)hipErrorInvalidValue;
+  if (a->mode == 0 && a->clip_kind != dct::MLP_CLIP_OFF) {
+    if (a->clip_kind == dct::MLP_CLIP_NORM &&
+        (!a->clip_ws || ((uintptr_t)a->clip_ws & 15) || a->clip_ws_floats < dct_mlp_tile_clip_ws_floats(dims, L)))
+      return (int)hipErrorInvalidValue;
+    return (int)dct::tile::train_clipped(tp, *a, L, wl, accum > 1, done, st);
+  }
   // (the plain instantiations first: they keep their place at the head of the code object)
   if (accum <= 1) {
     if (wl)
@@ -583,3 +775,25 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpArgs* a, void* stre
 }
 
 }  // extern "C"
+
+namespace dct {
+namespace tile {
+
+static hipError_t train_clipped(const Plan& tp, const MlpClipArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                                hipStream_t st) {
+  if (!acc) {
+    if (wl)
+      return L == 2 ? launch_steps<2, true, false, true>(tp, a, done, st)
+                    : launch_steps<3, true, false, true>(tp, a, done, st);
+    return L == 2 ? launch_steps<2, false, false, true>(tp, a, done, st)
+                  : launch_steps<3, false, false, true>(tp, a, done, st);
+  }
+  if (wl)
+    return L == 2 ? launch_steps<2, true, true, true>(tp, a, done, st)
+                  : launch_steps<3, true, true, true>(tp, a, done, st);
+  return L == 2 ? launch_steps<2, false, true, true>(tp, a, done, st)
+                : launch_steps<3, false, true, true>(tp, a, done, st);
+}
+
+}  // namespace tile
+}  // namespace dct

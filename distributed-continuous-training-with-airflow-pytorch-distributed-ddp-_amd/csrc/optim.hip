@@ -119,23 +119,44 @@ struct SgdArgs {
   const float* lr_tab;  // optional rate table (lr_table.h), with step_counter
 };
 
-__device__ __forceinline__ void sgd_device_scalars(SgdArgs& a) {
-  const int ti = __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  a.lr = lr_for(a.lr_tab, a.lr, ti - 1);
-  a.first = ti == 1;
+// the clipped step (dct_sgd_flat_step_clipped), with AdamArgs' meaning: clip_coef = the device coefficient of
+// dct_grad_clip_coef, multiplied into grad_scale (CLIP >= 1); clip_value > 0: the scaled g clamped to
+// [-clip_value, clip_value] before the coupled wd p is added (CLIP == 2).  Appended in a type of its own: the unclipped
+// kernel keeps SgdArgs as its kernel argument.
+struct SgdClipArgs : SgdArgs {
+  const float* clip_coef;
+  float clip_value;
+};
+
+// what a launch reads once from device memory before its first update: the step count and (CLIP) the clip coefficient
+template <int CLIP, class A>
+__device__ __forceinline__ void sgd_device_scalars(A& a) {
+  if (CLIP == 0 || a.step_counter) {
+    const int ti = __hip_atomic_load(a.step_counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a.lr = lr_for(a.lr_tab, a.lr, ti - 1);
+    a.first = ti == 1;
+  }
+  if constexpr (CLIP != 0)
+    if (a.clip_coef) a.grad_scale *= __hip_atomic_load(a.clip_coef, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ void sgd_one(float& p, float g, float& m, const SgdArgs& a) {
-  sgd_elem(p, g * a.grad_scale, m, a.lr, a.mu, a.damp, a.wd, a.nesterov != 0, a.first != 0);
+template <int CLIP, class A>
+__device__ __forceinline__ void sgd_one(float& p, float g, float& m, const A& a) {
+  g *= a.grad_scale;
+  if constexpr (CLIP == 2) g = g > a.clip_value ? a.clip_value : (g < -a.clip_value ? -a.clip_value : g);  // NaN stays
+  sgd_elem(p, g, m, a.lr, a.mu, a.damp, a.wd, a.nesterov != 0, a.first != 0);
 }
 
-__global__ __launch_bounds__(256) void sgd_flat_kernel(SgdArgs a) {
+// CLIP: 0 no clipping (dct_sgd_flat_step: SgdArgs), 1 the device coefficient, 2 the clamp too (SgdClipArgs)
+template <int CLIP, class A>
+__device__ __forceinline__ void sgd_flat_body(A a) {
   if (a.cursor && blockIdx.x == 0 && threadIdx.x == 0) {
     const int c = a.cursor[0];
     if (a.loss_out && c >= 0 && c < a.loss_cap) a.loss_out[c] = a.loss_slot[0];
     a.cursor[0] = c + 1;
   }
   bool pending = a.step_counter != nullptr;  // read after the first element's loads are issued (adam_flat_range)
+  if constexpr (CLIP != 0) pending = pending || a.clip_coef != nullptr;
   const bool mom = a.mu != 0.f;              // (uniform: a kernel argument)
   const int64_t n4 = a.n >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -147,13 +168,13 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(SgdArgs a) {
     const float4 g = g4[i];
     float4 m = mom ? m4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     if (pending) {
-      sgd_device_scalars(a);
+      sgd_device_scalars<CLIP>(a);
       pending = false;
     }
-    sgd_one(p.x, g.x, m.x, a);
-    sgd_one(p.y, g.y, m.y, a);
-    sgd_one(p.z, g.z, m.z, a);
-    sgd_one(p.w, g.w, m.w, a);
+    sgd_one<CLIP>(p.x, g.x, m.x, a);
+    sgd_one<CLIP>(p.y, g.y, m.y, a);
+    sgd_one<CLIP>(p.z, g.z, m.z, a);
+    sgd_one<CLIP>(p.w, g.w, m.w, a);
     p4[i] = p;
     if (mom) m4[i] = m;
   }
@@ -161,13 +182,20 @@ __global__ __launch_bounds__(256) void sgd_flat_kernel(SgdArgs a) {
   const int64_t tail0 = n4 << 2;
   const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gt < a.n - tail0) {
-    if (pending) sgd_device_scalars(a);
+    if (pending) sgd_device_scalars<CLIP>(a);
     const int64_t i = tail0 + gt;
     float p = a.p[i], m = mom ? a.m[i] : 0.f;
-    sgd_one(p, a.g[i], m, a);
+    sgd_one<CLIP>(p, a.g[i], m, a);
     a.p[i] = p;
     if (mom) a.m[i] = m;
   }
+}
+
+__global__ __launch_bounds__(256) void sgd_flat_kernel(SgdArgs a) { sgd_flat_body<0>(a); }
+
+template <int CLIP>
+__global__ __launch_bounds__(256) void sgd_flat_clip_kernel(SgdClipArgs a) {
+  sgd_flat_body<CLIP>(a);
 }
 
 }  // namespace dct
@@ -262,17 +290,22 @@ int dct_adam_flat_step_lr(float* p, const float* g, float* m, float* v, uint16_t
   return (int)hipGetLastError();
 }
 
-int dct_sgd_flat_step(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,
-                      int nesterov, float wd, int64_t t, float grad_scale, const int* step_counter, int* cursor,
-                      const float* loss_slot, float* loss_out, int loss_cap, const float* lr_tab, void* stream) {
+// SgdArgs of a flat step at host step count t, checked (dct_sgd_flat_step and its clipped form); *skip: n <= 0
+static int sgd_step_args(dct::SgdArgs& a, bool* skip, float* p, const float* g, float* m, int64_t n, float lr,
+                         float momentum, float dampening, int nesterov, float wd, int64_t t, float grad_scale,
+                         const int* step_counter, int* cursor, const float* loss_slot, float* loss_out, int loss_cap,
+                         const float* lr_tab) {
+  *skip = false;
   if (!(momentum >= 0.f) || !(wd >= 0.f) || (nesterov && (momentum <= 0.f || dampening != 0.f)) ||
       !lr_tab_ok(lr_tab, step_counter))
     return (int)hipErrorInvalidValue;
-  if (n <= 0) return 0;
+  if (n <= 0) {
+    *skip = true;
+    return 0;
+  }
   if (cursor && !loss_slot) return (int)hipErrorInvalidValue;
   if (!p || !g || (momentum != 0.f && !m)) return (int)hipErrorInvalidValue;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) return (int)hipErrorInvalidValue;
-  dct::SgdArgs a{};
   a.p = p; a.g = g; a.m = m; a.n = n;
   a.lr = lr; a.mu = momentum; a.damp = dampening; a.wd = wd; a.grad_scale = grad_scale;
   a.nesterov = nesterov ? 1 : 0;
@@ -283,8 +316,41 @@ int dct_sgd_flat_step(float* p, const float* g, float* m, int64_t n, float lr, f
   a.loss_out = loss_out;
   a.loss_cap = loss_cap;
   a.lr_tab = lr_tab;
+  return 0;
+}
+
+int dct_sgd_flat_step(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,
+                      int nesterov, float wd, int64_t t, float grad_scale, const int* step_counter, int* cursor,
+                      const float* loss_slot, float* loss_out, int loss_cap, const float* lr_tab, void* stream) {
+  dct::SgdArgs a{};
+  bool skip;
+  const int e = sgd_step_args(a, &skip, p, g, m, n, lr, momentum, dampening, nesterov, wd, t, grad_scale, step_counter,
+                              cursor, loss_slot, loss_out, loss_cap, lr_tab);
+  if (e || skip) return e;
   hipLaunchKernelGGL(dct::sgd_flat_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+
+int dct_sgd_flat_step_clipped(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,
+                              int nesterov, float wd, int64_t t, float grad_scale, const int* step_counter,
+                              int* cursor, const float* loss_slot, float* loss_out, int loss_cap, const float* lr_tab,
+                              const float* clip_coef, float clip_value, void* stream) {
+  if (!(clip_value >= 0.f)) return (int)hipErrorInvalidValue;
+  if (!clip_coef && clip_value == 0.f)  // no clipping: the unclipped kernel
+    return dct_sgd_flat_step(p, g, m, n, lr, momentum, dampening, nesterov, wd, t, grad_scale, step_counter, cursor,
+                             loss_slot, loss_out, loss_cap, lr_tab, stream);
+  dct::SgdClipArgs a{};
+  bool skip;
+  const int e = sgd_step_args(a, &skip, p, g, m, n, lr, momentum, dampening, nesterov, wd, t, grad_scale, step_counter,
+                              cursor, loss_slot, loss_out, loss_cap, lr_tab);
+  if (e || skip) return e;
+  a.clip_coef = clip_coef;
+  a.clip_value = clip_value;
+  const dim3 grid(grid_for((n + 3) / 4, 256));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (clip_value > 0.f) hipLaunchKernelGGL(dct::sgd_flat_clip_kernel<2>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(dct::sgd_flat_clip_kernel<1>, grid, dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
 

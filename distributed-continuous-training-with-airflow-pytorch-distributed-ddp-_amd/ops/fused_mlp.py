@@ -14,8 +14,10 @@ from typing import Optional, Sequence
 import torch
 
 from ._native import native, ptr, stream_handle
+from .optim import check_clip_args
 
 LOSS_KINDS = {"ce": 0, "mse": 1}
+CLIP_KINDS = {"norm": 1, "value": 2}  # csrc/mlp_fused.h MlpClip
 # exchange polling of the wave kernels (csrc/mlp_fused.h xg_poll): two pipelined sweeps in flight
 # (profiles/xg_poll_pipelined_ab_r2.log; probe-then-sweep and sequential polls measured slower)
 XG_POLL = 3
@@ -208,6 +210,7 @@ class FusedMLPKernel:
         self._eval_plan = None
         self._tile_ws = None  # slot workspace of the batch-tiled trainer (csrc/mlp_tile.hip)
         self._infer_ws_buf = None  # slot workspace of the inference kernel's statistics (csrc/mlp_infer.hip)
+        self._clip_ws = None  # norm clipping: folded gradient, partial sums and {norm, coef} (csrc/mlp_tile.hip)
 
     def _tile_args(self, device, batch: int = 0, accumulate: int = 1) -> dict:
         """The batch-tiled trainer's slot workspace (partial gradients per tile + the fold's arrival
@@ -241,6 +244,35 @@ class FusedMLPKernel:
         if optimizer == "sgd":
             return dict(optimizer="sgd", momentum=float(momentum), dampening=float(dampening), nesterov=bool(nesterov))
         return dict(optimizer="adamw")
+
+    def _check_clip(self, clip_val, clip_algorithm: str, batch: int, device, train: bool) -> dict:
+        """The native arguments of a launch that clips its gradient ({} when off, and for a grad-mode launch, which
+        ignores clipping).  By norm the launch gets this kernel's workspace, allocated once (launches bound earlier
+        keep it alive; a captured launch sequence needs its address fixed)."""
+        clip_val, clip_algorithm = check_clip_args(clip_val, clip_algorithm)
+        if clip_val is None or not train:
+            return {}
+        if clip_val == float("inf"):
+            raise ValueError("clip_val must be finite")
+        if self.plan.trainer(int(batch), clipped=True) != "tile":
+            raise ValueError("gradient clipping needs the batch-tiled trainer: a plan of bmax 1024 "
+                             "(any batch 1..1024) for an architecture it takes")
+        args = dict(clip_kind=CLIP_KINDS[clip_algorithm], clip_val=clip_val)
+        if clip_algorithm == "norm":
+            if self._clip_ws is None or self._clip_ws.device != device:
+                n = int(native().mlp_tile_clip_ws_floats(self.dims))
+                self._clip_ws = torch.zeros(n, dtype=torch.float32, device=device)
+                self._clip_ws[n - 4: n - 2] = torch.tensor([float("nan"), 1.0])  # (no norm computed yet)
+            args.update(clip_ws=ptr(self._clip_ws), clip_ws_floats=self._clip_ws.numel())
+        return args
+
+    def clip_stats(self):
+        """(norm, coef) of the last norm-clipped step as Python floats (synchronises: tests and logging); (nan, 1.0)
+        when no norm is computed (no clipped launch yet, or clipping by value)."""
+        if self._clip_ws is None:
+            return float("nan"), 1.0
+        norm, coef = self._clip_ws[-4:-2].tolist()
+        return norm, coef
 
     @staticmethod
     def _moments_of(opt_args: dict, m, v):
@@ -348,8 +380,16 @@ class FusedMLPKernel:
               stream: Optional[int] = None, xg=None, xg_timeout_s: float = 2.0,
               lr_tab: Optional[torch.Tensor] = None, class_weight: Optional[torch.Tensor] = None,
               label_smoothing: float = 0.0, accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0,
-              dampening: float = 0.0, nesterov: bool = False):
+              dampening: float = 0.0, nesterov: bool = False, clip_val: Optional[float] = None,
+              clip_algorithm: str = "norm"):
         """Run ``steps`` fused optimizer steps (mode 0) or one gradient step (grad_out given).
+
+        ``clip_val`` / ``clip_algorithm`` (Lightning's ``gradient_clip_val`` / ``gradient_clip_algorithm``; the
+        batch-tiled trainer's plan only): the step's final gradient - after the fold, the weighted mean and the
+        window's 1 / K, before the optimizer's weight decay - is scaled by ``min(clip_val / (norm + 1e-6), 1)``
+        (``"norm"``: ``clip_grad_norm_``; ``clip_stats()`` reads back the step's norm and coefficient) or clamped to
+        ``[-clip_val, clip_val]`` (``"value"``).  None / 0: off.  A grad-mode launch ignores both: ``grad_out`` is the
+        unclipped gradient.
 
         ``optimizer``: ``"adam"`` (torch.optim.Adam), or on the batch-tiled trainer's plan ``"adamw"``
         (torch.optim.AdamW: ``p *= 1 - lr_t * weight_decay``, then Adam on the undecayed gradient) and ``"sgd"``
@@ -387,6 +427,7 @@ class FusedMLPKernel:
             raise ValueError(f"batch {batch} > kernel bmax {self.bmax}")
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
+        clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, mode == 0)
         if steps < 1 or (cursor is None and (steps - 1) * batch * accumulate >= n_items):
             raise ValueError("steps do not match the index list")
         if cursor is not None and (mode != 1 or not (cursor.is_cuda and cursor.dtype == torch.int32)):
@@ -420,7 +461,7 @@ class FusedMLPKernel:
             ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending), ptr(stage),
             stream if stream is not None else stream_handle(),
             **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab), **wl_args,
-            **acc_args, **opt_args,
+            **acc_args, **opt_args, **clip_args,
         )
 
     def prepare_train(self, p, m, v, X, Y, idx, n_items: int, batch: int, lr: float, betas=(0.9, 0.999),
@@ -430,7 +471,8 @@ class FusedMLPKernel:
                       xg_ticks: Optional[torch.Tensor] = None, lr_tab: Optional[torch.Tensor] = None,
                       class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
                       accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0, dampening: float = 0.0,
-                      nesterov: bool = False) -> "BoundTrain":
+                      nesterov: bool = False, clip_val: Optional[float] = None,
+                      clip_algorithm: str = "norm") -> "BoundTrain":
         """Validate the operands of persistent train-mode launches ONCE and bind them natively.
 
         ``BoundTrain.run(first_step, steps)`` then launches steps [first_step, first_step+steps)
@@ -438,7 +480,7 @@ class FusedMLPKernel:
         positional native call (no keyword parsing, no tensor checks), which is what the short
         timed windows of the benchmark contract see.  ``accumulate`` as in ``train``: the steps are
         optimizer steps of ``accumulate`` micro-batches each.  ``optimizer`` / ``momentum`` / ``dampening`` /
-        ``nesterov`` as in ``train``."""
+        ``nesterov`` and ``clip_val`` / ``clip_algorithm`` as in ``train``."""
         if not 1 <= batch <= self.bmax:
             raise ValueError(f"batch {batch} outside 1..{self.bmax}")
         opt_args = self._check_optimizer(optimizer, batch, weight_decay, momentum, dampening, nesterov, True)
@@ -447,6 +489,7 @@ class FusedMLPKernel:
         self._check_data(X, Y, idx, n_items)
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
+        clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, True)
         if step_counter is None or not (step_counter.is_cuda and step_counter.dtype == torch.int32):
             raise ValueError("step_counter must be a cuda int32 scalar tensor (launches are step-relative)")
         if loss_out is not None and not (loss_out.is_cuda and loss_out.dtype == torch.float32
@@ -471,9 +514,9 @@ class FusedMLPKernel:
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, ptr(loss_out), 0 if loss_out is None else loss_out.numel(), LOSS_KINDS[loss],
             ptr(step_counter), **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab),
-            **wl_args, **acc_args, **opt_args)
+            **wl_args, **acc_args, **opt_args, **clip_args)
         return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws, lr_tab,
-                                   class_weight),
+                                   class_weight, self._clip_ws),
                           p.device.index or 0)
 
     # ------------------------------------------------------------ in-kernel all-reduce

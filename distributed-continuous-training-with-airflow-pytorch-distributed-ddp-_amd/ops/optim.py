@@ -286,12 +286,15 @@ class FlatAdam:
 def sgd_flat_(p: torch.Tensor, g: torch.Tensor, m: Optional[torch.Tensor], step: int, lr: float,
               momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
               grad_scale: float = 1.0, step_counter: Optional[torch.Tensor] = None,
-              lr_tab: Optional[torch.Tensor] = None, epilogue=None):
+              lr_tab: Optional[torch.Tensor] = None, epilogue=None, clip_coef: Optional[torch.Tensor] = None,
+              clip_value: float = 0.0):
     """In-place ``torch.optim.SGD`` (maximize=False) on flat fp32 buffers; ``m`` is the momentum buffer (None allowed
     without momentum) and ``step`` the 1-based step count after this update: at step 1 torch has no buffer yet, so the
     buffer becomes the gradient and what ``m`` held is ignored.  On the GPU one kernel (csrc/optim.hip); with
     ``step_counter`` (a cuda int32 that already includes this step) the count, and ``lr_tab``'s rate for
     ``*step_counter - 1`` steps taken, are read on the device.  ``epilogue=(cursor, loss, loss_out)`` as FlatAdam.step.
+    ``clip_coef`` / ``clip_value`` as adam_flat_: the device coefficient of grad_clip_coef_ is multiplied into
+    ``grad_scale``, then ``clip_value`` > 0 clamps the scaled gradient - before the coupled weight decay is added.
     ``g`` is not rewritten."""
     n = p.numel()
     momentum, dampening, weight_decay = float(momentum), float(dampening), float(weight_decay)
@@ -314,6 +317,13 @@ def sgd_flat_(p: torch.Tensor, g: torch.Tensor, m: Optional[torch.Tensor], step:
                                    or lr_tab.numel() < 5):
             raise ValueError("lr_tab must be a cuda fp32 rate table (4 header words + >= 1 rate) used with step_counter")
         cursor, loss, loss_out = epilogue if epilogue is not None else (None, None, None)
+        if clip_coef is not None or clip_value:
+            native().sgd_flat_step_clipped(ptr(p), ptr(g), ptr(m) if momentum != 0.0 else 0, n, float(lr), momentum,
+                                           dampening, bool(nesterov), weight_decay, max(1, int(step)),
+                                           float(grad_scale), ptr(step_counter), ptr(cursor), ptr(loss), ptr(loss_out),
+                                           0 if loss_out is None else loss_out.numel(), ptr(clip_coef),
+                                           float(clip_value), stream_handle(p.device), ptr(lr_tab))
+            return
         native().sgd_flat_step(ptr(p), ptr(g), ptr(m) if momentum != 0.0 else 0, n, float(lr), momentum, dampening,
                                bool(nesterov), weight_decay, max(1, int(step)), float(grad_scale), ptr(step_counter),
                                ptr(cursor), ptr(loss), ptr(loss_out), 0 if loss_out is None else loss_out.numel(),
@@ -322,6 +332,10 @@ def sgd_flat_(p: torch.Tensor, g: torch.Tensor, m: Optional[torch.Tensor], step:
     if lr_tab is not None or epilogue is not None:
         raise ValueError("sgd_flat_: a rate table / step epilogue is the GPU kernel's; on the CPU pass the rate as lr")
     gg = g * grad_scale if grad_scale != 1.0 else g
+    if clip_coef is not None:
+        gg = gg * clip_coef  # (torch multiplies even by 1.0: exact)
+    if clip_value:
+        gg = gg.clamp(-clip_value, clip_value)
     if weight_decay:
         gg = gg + weight_decay * p
     if momentum != 0.0:
@@ -360,10 +374,16 @@ class FlatSGD:
 
     def __init__(self, flat_param: torch.Tensor, flat_grad: torch.Tensor, param_shapes: Sequence[torch.Size],
                  lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, lr_schedule=None, momentum_buffer: Optional[torch.Tensor] = None):
-        """``momentum_buffer``: an existing flat buffer to hold (an engine's own), instead of a new zeroed one."""
+                 nesterov: bool = False, lr_schedule=None, momentum_buffer: Optional[torch.Tensor] = None,
+                 clip_val: Optional[float] = None, clip_algorithm: str = "norm"):
+        """``momentum_buffer``: an existing flat buffer to hold (an engine's own), instead of a new zeroed one.
+        ``clip_val`` / ``clip_algorithm``: gradient clipping inside the step, as FlatAdam."""
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self.clip_val, self.clip_algorithm = check_clip_args(clip_val, clip_algorithm)
+        self.clip_ws: Optional[torch.Tensor] = None  # {norm, coef, ..} of the last step (by norm), allocated once
+        if self.clip_val is not None and self.clip_algorithm == "norm":
+            self.clip_ws = clip_workspace(flat_param.device)
         self.p = flat_param
         self.g = flat_grad
         self.m = torch.zeros_like(flat_param) if momentum_buffer is None else momentum_buffer
@@ -389,8 +409,22 @@ class FlatSGD:
                 counter = torch.full((1,), self.step_count, dtype=torch.int32, device=self.p.device)
             else:
                 lr = self.lr_schedule.rate_for(self.step_count - 1)
+        clip_coef, clip_value = None, 0.0
+        if self.clip_val is not None:  # (as FlatAdam.step: the coefficient stays on the device, g is not rewritten)
+            if self.clip_algorithm == "norm":
+                clip_coef = grad_clip_coef_(self.g, self.clip_val, self.clip_ws, grad_scale)[1:]
+            else:
+                clip_value = self.clip_val
         sgd_flat_(self.p, self.g, self.m, self.step_count, lr, g["momentum"], g["dampening"], g["nesterov"],
-                  g["weight_decay"], grad_scale=grad_scale, step_counter=counter, lr_tab=lr_tab)
+                  g["weight_decay"], grad_scale=grad_scale, step_counter=counter, lr_tab=lr_tab, clip_coef=clip_coef,
+                  clip_value=clip_value)
+
+    def clip_stats(self):
+        """(norm, coef) of the last step's clipping by norm; (nan, 1.0) when nothing computes a norm (as FlatAdam)."""
+        if self.clip_ws is None:
+            return float("nan"), 1.0
+        norm, coef = self.clip_ws[:2].tolist()
+        return norm, coef
 
     def zero_grad(self):
         self.g.zero_()

@@ -41,7 +41,8 @@ from ..ops._native import reload_knobs
 from ..ops.fused_mlp import (TILE_BMAX, FusedMLPKernel, check_accumulate, mlp_num_params, tile_supported,
                              tile_window_ok, weighted_infer_stats)
 from ..ops.nn import BatchGather, bound_params, fold_batch_gather, join_side_work, unit_loss_seed
-from ..ops.optim import FlatAdam, FlatSGD, _torch_adamw_group_defaults, adam_flat_, check_clip_args, sgd_flat_
+from ..ops.optim import (FlatAdam, FlatSGD, _torch_adamw_group_defaults, adam_flat_, check_clip_args, clip_workspace,
+                         grad_clip_coef_, sgd_flat_)
 from ..parallel.dist import DistContext, init_native_comm
 from ..parallel.reducer import NativeBucketReducer, TorchBucketReducer, plan_buckets
 from ..utils.debug import assert_reducer_complete, check_device
@@ -124,12 +125,13 @@ class FusedMLPEngine(_EngineBase):
     FUSED_UPDATE = True
 
     @staticmethod
-    def applicable(model, device: torch.device, batch_size: int, accumulate: int = 1, optimizer: str = "adam") -> bool:
+    def applicable(model, device: torch.device, batch_size: int, accumulate: int = 1, optimizer: str = "adam",
+                   clipped: bool = False) -> bool:
         if device.type != "cuda" or not hasattr(model, "fused_spec"):
             return False
         spec = model.fused_spec()
-        if optimizer != "adam" and accumulate <= 1:
-            # AdamW / SGD: only the batch-tiled trainer's fold applies them, at any batch it takes
+        if (optimizer != "adam" or clipped) and accumulate <= 1:
+            # AdamW / SGD, gradient clipping: only the batch-tiled trainer has them, at any batch it takes
             if (spec_weighted(spec) and spec["loss"] != "ce") or not tile_supported(spec["dims"]):
                 return False
             return 1 <= batch_size <= TILE_BMAX
@@ -146,8 +148,17 @@ class FusedMLPEngine(_EngineBase):
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,
                  steps_per_launch: int = 0, use_graph: Optional[bool] = None, lr_schedule=None,
-                 accumulate_grad_batches: int = 1):
+                 accumulate_grad_batches: int = 1, gradient_clip_val: Optional[float] = None,
+                 gradient_clip_algorithm: str = "norm", tile_plan: bool = False):
+        """``tile_plan``: build on the batch-tiled trainer's plan whatever the batch and the options (engine="tile")."""
         super().__init__(model, ctx, batch_size, seed)
+        # gradient clipping (Trainer(gradient_clip_val, gradient_clip_algorithm) under engine="tile"): between the fold
+        # and the optimizer of the batch-tiled trainer (csrc/mlp_tile.hip), so the kernel is built on the tile plan
+        # whatever the batch; self.clip: the two keywords of every train-mode launch.  Under DDP the step path is
+        # grad-mode launch (unclipped gradient) -> RCCL -> [norm kernel ->] clipped flat Adam / flat SGD, never the
+        # peer all-reduce + Adam kernel, which cannot clip.
+        self.clip_val, self.clip_algorithm = check_clip_args(gradient_clip_val, gradient_clip_algorithm)
+        self.clip = {} if self.clip_val is None else dict(clip_val=self.clip_val, clip_algorithm=self.clip_algorithm)
         # K = accumulate_grad_batches > 1: an optimizer step is a window of K micro-batches of B rows, one grid and one
         # fold of the batch-tiled trainer (csrc/mlp_tile.hip), so the kernel is built on the tile plan whatever the
         # batch.  Steps, losses, the device counters and the lr table count windows.  Under DDP the existing step path
@@ -181,7 +192,7 @@ class FusedMLPEngine(_EngineBase):
         # class-weighted / label-smoothed CE (models/mlp.py): the batch-tiled trainer's plan whatever the batch, and
         # the two arguments on every train launch; validation through the tiled inference kernel
         self.weighted = spec_weighted(spec)
-        tiled = self.weighted or self.K > 1 or self.kind != "adam"
+        tiled = self.weighted or self.K > 1 or self.kind != "adam" or bool(self.clip) or tile_plan
         bmax = TILE_BMAX if tiled else (4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
         self.kernel = FusedMLPKernel(self.dims, bmax=bmax)
         if self.K > 1 and self.kernel.plan.trainer(self.B, accumulate=self.K) != "tile":
@@ -226,6 +237,9 @@ class FusedMLPEngine(_EngineBase):
         if self.ddp:
             self.gbuf = torch.zeros(self.P + 1, dtype=torch.float32, device=dev)
             self._broadcast_params()
+        # DDP step path, clipping by norm: {norm, coef, ticket, partials} of the flat step, allocated once (a captured
+        # chunk needs static addresses)
+        self._flat_clip_ws = clip_workspace(dev) if self.ddp and self.clip and self.clip_algorithm == "norm" else None
         self.xg = None  # in-kernel xGMI all-reduce (parallel/xgmi.py)
         self.gx = None  # DDP step path: fused peer all-reduce + Adam kernel over xGMI (csrc/xg_adam.hip)
         self._xg_probed = False
@@ -243,7 +257,8 @@ class FusedMLPEngine(_EngineBase):
             self.xg_timeout_s = timeout_s()
             # exchange time of the launches (s_memrealtime ticks, 100 MHz) -> allreduce_ms per epoch
             self.xg_ticks = torch.zeros(1, dtype=torch.int64, device=dev) if self.xg is not None else None
-            if self.xg is None and not self.fused_update and self.kind == "adam":  # (xg_adam.hip applies Adam)
+            # (xg_adam.hip applies plain Adam on the unclipped gradient)
+            if self.xg is None and not self.fused_update and self.kind == "adam" and not self.clip:
                 self.gx = setup_grad_exchange(ctx, self.P + 1)
             if xg_mode() == "xgmi" and self.xg is None and self.gx is None:
                 raise RuntimeError("DCT_ALLREDUCE=xgmi but neither the in-kernel exchange nor the peer "
@@ -251,7 +266,8 @@ class FusedMLPEngine(_EngineBase):
             if self.xg is None and self.gx is None and self.comm is None:
                 raise RuntimeError("distributed fused engine needs RCCL (backend nccl) or the in-kernel "
                                    "xGMI exchange; neither is available")
-        elif self.ddp and not self.fused_update and self.kind == "adam" and os.environ.get("DCT_XG_GRAD") == "1":
+        elif (self.ddp and not self.fused_update and self.kind == "adam" and not self.clip
+              and os.environ.get("DCT_XG_GRAD") == "1"):
             # single-GPU rehearsal (DCT_FORCE_DDP=1 DCT_XG_GRAD=1): the exchange kernel of one rank
             # (no pushes, no polls) in place of the one-rank RCCL all-reduce + flat Adam
             from ..ops._native import native
@@ -389,7 +405,7 @@ class FusedMLPEngine(_EngineBase):
                                            loss_out=loss_out, loss=self.loss, step_counter=self.step_counter,
                                            xg=self.xg, xg_timeout_s=getattr(self, "xg_timeout_s", 20.0),
                                            xg_ticks=getattr(self, "xg_ticks", None) if self.xg is not None else None,
-                                           lr_tab=tab, **self.wloss, **self.acc)
+                                           lr_tab=tab, **self.wloss, **self.acc, **self.clip)
             self._bound, self._bound_key = bl, key
         return bl
 
@@ -489,13 +505,29 @@ class FusedMLPEngine(_EngineBase):
         """The DDP step path's optimizer on the all-reduced gradient in gbuf, at the device step count (which the
         grad-mode launch has advanced already): flat Adam, flat Adam with decoupled decay (AdamW) or flat SGD."""
         a = self.adam
+        clip = {}
+        if self.clip:  # inside the flat step (gbuf keeps the unclipped gradient); by norm one kernel in front of it
+            if self.clip_algorithm == "norm":
+                clip = dict(clip_coef=grad_clip_coef_(self.gbuf[: self.P], self.clip_val, self._flat_clip_ws)[1:])
+            else:
+                clip = dict(clip_value=self.clip_val)
         if self.kind == "sgd":
             sgd_flat_(self.p, self.gbuf[: self.P], self.m, 1, a["lr"], a["momentum"], a["dampening"], a["nesterov"],
-                      a["weight_decay"], step_counter=self.step_counter, lr_tab=self._lr_tab())
+                      a["weight_decay"], step_counter=self.step_counter, lr_tab=self._lr_tab(), **clip)
             return
         adam_flat_(self.p, self.gbuf[: self.P], self.m, self.v, 1, a["lr"], a["betas"], a["eps"],
                    a["weight_decay"], decoupled=self.kind == "adamw", step_counter=self.step_counter,
-                   lr_tab=self._lr_tab())
+                   lr_tab=self._lr_tab(), **clip)
+
+    def grad_clip_stats(self) -> Tuple[float, float]:
+        """(total gradient norm, clip coefficient) of the last step as Python floats; (nan, 1.0) when no norm is
+        computed (clipping off or by value).  Synchronises: for tests and logging."""
+        if not self.clip or self.clip_algorithm != "norm":
+            return float("nan"), 1.0
+        if self._flat_clip_ws is not None:
+            norm, coef = self._flat_clip_ws[:2].tolist()
+            return norm, coef
+        return self.kernel.clip_stats()
 
     def _get_graph(self, n_items: int, C: int, loss_out: torch.Tensor):
         key = (n_items, C, loss_out.data_ptr())

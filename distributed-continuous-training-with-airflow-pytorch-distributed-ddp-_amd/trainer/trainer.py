@@ -274,6 +274,16 @@ class Trainer:
             fused_ok = hp is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size, K, **other)
         else:
             fused_ok = hp is not None and FusedMLPEngine.applicable(model, ctx.device, batch_size, **other)
+        if choice == "tile":
+            # the fused engine on the batch-tiled trainer's plan (csrc/mlp_tile.hip) at any batch it takes, with gradient
+            # clipping passed through: the clipped step's fold / norm / optimizer kernels.  The one route of a clipped
+            # model to the fused engine - "auto" keeps sending it to the graph or autograd engine
+            if hp is None or not FusedMLPEngine.applicable(model, ctx.device, batch_size, K, **other, clipped=True):
+                raise RuntimeError("engine='tile' requested but the batch-tiled trainer does not take this "
+                                   "model/device/batch (tile shape, batch 1..1024, accumulation window within its cap)")
+            sched = dict(lr_schedule=LrSchedule.from_config(torch_opt, sched_cfg)) if sched_cfg is not None else {}
+            return FusedMLPEngine(model, ctx, batch_size, seed, hp, steps_per_launch=self.steps_per_launch, **sched,
+                                  **acc, **clip, tile_plan=True)
         if self.gradient_clip_val is not None:
             fused_ok = False  # clipping: the graph engine where it applies, otherwise autograd
         if (choice == "auto" and fused_ok and batch_size > 16 and K == 1 and not other
