@@ -52,6 +52,7 @@ class ModelConfig:
     # (n / (C * count_c) over the training split) or one strictly positive weight per class; smoothing in [0, 1)
     class_weight: Any = None
     label_smoothing: float = 0.0
+    activation: str = "relu"  # hidden activation of the MLP family: relu | gelu | gelu_tanh | silu
     # TabTransformer-only knobs
     d_model: int = 64
     n_heads: int = 4

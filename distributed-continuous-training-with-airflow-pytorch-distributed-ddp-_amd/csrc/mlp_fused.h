@@ -183,6 +183,21 @@ struct MlpClipArgs : MlpArgs {
 
 enum MlpClip { MLP_CLIP_OFF = 0, MLP_CLIP_NORM = 1, MLP_CLIP_VALUE = 2 };
 
+// The activation of every hidden layer (the head stays linear): MLP_ACT_RELU is every kernel as it always was;
+// MLP_ACT_GELU is torch's default erf form z * Phi(z), MLP_ACT_GELU_TANH its approximate="tanh" form, MLP_ACT_SILU
+// z * sigmoid(z).  The three smooth kinds run on the batch-tiled trainer and the batch-tiled inference kernel only.
+enum MlpAct { MLP_ACT_RELU = 0, MLP_ACT_GELU = 1, MLP_ACT_GELU_TANH = 2, MLP_ACT_SILU = 3 };
+inline bool mlp_act_ok(int kind) { return kind >= MLP_ACT_RELU && kind <= MLP_ACT_SILU; }
+
+// MlpActArgs: MlpClipArgs with the activation kind behind the clip fields - what the host builds and hands to the
+// launchers.  No kernel takes it: the batch-tiled trainer's step kernel gets the kind as a template argument (on its
+// MlpStepArgs prefix, like the ReLU instantiations), every other kernel takes the prefix it always took.  The kind is
+// part of the model, so grad-mode launches honour it (unlike the optimizer and clip fields).  mlp_select.h refuses a
+// non-ReLU launch on every other trainer.
+struct MlpActArgs : MlpClipArgs {
+  int act_kind;
+};
+
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
 
 // One launch of the batch-tiled inference kernel (mlp_infer.hip): forward only, rows 0 .. n - 1 of the index
@@ -210,6 +225,8 @@ struct MlpInferArgs {
   // its denominator W = sum_c w[c] * (row sum c of the confusion matrix) is the host's to compute.
   const float* class_w;
   float label_smooth;
+  // the hidden layers' activation (MlpAct; appended, so every other field keeps its offset): 0 = ReLU
+  int act_kind;
 };
 
 // fills *sh for dims[0 .. L] and plans of up to bmax rows per step (mlp_block = -1: auto, until the plan stamps
@@ -256,10 +273,12 @@ int dct_mlp_tile_max_slots(void);
 // 16-byte boundary (0: not a tile shape)
 long long dct_mlp_tile_clip_ws_floats(const int* dims, int L);
 // hipErrorInvalidValue also for an unknown clip_kind, a clip_val that is not a finite value > 0 while the kind is set,
-// and norm clipping without a clip_ws of that size (train mode; grad mode ignores the clip fields)
-int dct_mlp_tile_train(const int* dims, int L, const dct::MlpClipArgs* a, void* stream);
+// and norm clipping without a clip_ws of that size (train mode; grad mode ignores the clip fields), and for an
+// act_kind that is no MlpAct (both modes)
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpActArgs* a, void* stream);
 // batch-tiled forward-only inference (mlp_infer.hip); grid <= 0: default.  It and dct_mlp_tile_train share one
-// forward and one host check (mlp_tile_fwd.h): the shapes of dct_mlp_tile_supported, p on a 16-byte boundary
+// forward and one host check (mlp_tile_fwd.h): the shapes of dct_mlp_tile_supported, p on a 16-byte boundary;
+// hipErrorInvalidValue also for an act_kind that is no MlpAct
 int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, void* stream);
 long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n);
 }

@@ -76,7 +76,9 @@ __device__ __forceinline__ float pick4(const float (&v)[4], int i) {
 
 // WL: the class-weighted / label-smoothed loss, chosen on the host from the launch arguments - the plain
 // instantiation is the kernel as it was
-template <int L, bool WL>
+// ACT: the hidden layers' activation (MlpInferArgs::act_kind, chosen on the host likewise): MLP_ACT_RELU is the kernel
+// as it was, the smooth kinds run the trainer's own act(z) (mlp_tile_fwd.h act_grad) in the two layers' epilogues
+template <int L, bool WL, int ACT = MLP_ACT_RELU>
 __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, long long T, long long S, int nslots) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds lo = lds_layout(L);
@@ -152,7 +154,8 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
       __syncthreads();
 
       // ---- layer 0: A1 = relu(X0 W0^T + b0)
-      layer0(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
+      if constexpr (ACT == MLP_ACT_RELU) layer0(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
+      else layer0<ACT>(A1, W0s, X0, D0, H1, tid, ActEpilogue<ACT>{});
       __syncthreads();
 
       // ---- layer 1: A2 = relu(A1 W1^T + b1); a wave owns column blocks wave, wave + 4
@@ -161,7 +164,8 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
         for (int c = 0; c < 2; ++c) {
           const int cb = wave + 4 * c;
           if (cb * 16 >= H2) break;
-          layer1_block(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
+          if constexpr (ACT == MLP_ACT_RELU) layer1_block(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
+          else layer1_block<ACT>(A2, A1, wf[c], cb, b1v[c], H1, j, q, ActEpilogue<ACT>{});
         }
         __syncthreads();
       }
@@ -270,10 +274,10 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_infer_fold_kernel(const long long
   }
 }
 
-template <int L, bool WL>
+template <int L, bool WL, int ACT = MLP_ACT_RELU>
 static hipError_t launch(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
   const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
-  auto fn = mlp_infer_kernel<L, WL>;
+  auto fn = mlp_infer_kernel<L, WL, ACT>;
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), bytes, st, tp, a, sl.T, sl.S, sl.nslots);
@@ -282,6 +286,10 @@ static hipError_t launch(const Plan& tp, const MlpInferArgs& a, const Slots& sl,
                        reinterpret_cast<const long long*>(a.ws), sl.nslots, reinterpret_cast<long long*>(a.stats));
   return hipGetLastError();
 }
+
+// a smooth activation's launch (instantiated behind the ReLU kernels, which keep their place in the code object)
+template <int ACT>
+static hipError_t launch_act(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st);
 
 }  // namespace infer
 }  // namespace dct
@@ -303,7 +311,7 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, 
   if (a->loss_kind != 0 && a->loss_kind != 1) return (int)hipErrorInvalidValue;
   if (!(a->label_smooth >= 0.f && a->label_smooth < 1.f)) return (int)hipErrorInvalidValue;
   if ((a->class_w || a->label_smooth != 0.f) && a->loss_kind != 0) return (int)hipErrorInvalidValue;  // CE only
-  if (grid > dct::infer::MAX_GRID) return (int)hipErrorInvalidValue;
+  if (grid > dct::infer::MAX_GRID || !dct::mlp_act_ok(a->act_kind)) return (int)hipErrorInvalidValue;
   const dct::infer::Slots sl = dct::infer::slots_of(a->n);
   if (a->Y) {
     if (!a->ws || !a->stats || reinterpret_cast<uintptr_t>(a->ws) % 8 != 0 ||
@@ -312,6 +320,12 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, 
   }
   if (grid <= 0) grid = sl.nslots < 1024 ? sl.nslots : 1024;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  switch (a->act_kind) {
+    case dct::MLP_ACT_GELU: return (int)dct::infer::launch_act<dct::MLP_ACT_GELU>(tp, *a, sl, grid, st);
+    case dct::MLP_ACT_GELU_TANH: return (int)dct::infer::launch_act<dct::MLP_ACT_GELU_TANH>(tp, *a, sl, grid, st);
+    case dct::MLP_ACT_SILU: return (int)dct::infer::launch_act<dct::MLP_ACT_SILU>(tp, *a, sl, grid, st);
+    default: break;
+  }
   if (a->class_w || a->label_smooth != 0.f)
     return (int)(L == 2 ? dct::infer::launch<2, true>(tp, *a, sl, grid, st)
                         : dct::infer::launch<3, true>(tp, *a, sl, grid, st));
@@ -320,3 +334,16 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, 
 }
 
 }  // extern "C"
+
+namespace dct {
+namespace infer {
+
+template <int ACT>
+static hipError_t launch_act(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
+  if (a.class_w || a.label_smooth != 0.f)
+    return tp.L == 2 ? launch<2, true, ACT>(tp, a, sl, grid, st) : launch<3, true, ACT>(tp, a, sl, grid, st);
+  return tp.L == 2 ? launch<2, false, ACT>(tp, a, sl, grid, st) : launch<3, false, ACT>(tp, a, sl, grid, st);
+}
+
+}  // namespace infer
+}  // namespace dct

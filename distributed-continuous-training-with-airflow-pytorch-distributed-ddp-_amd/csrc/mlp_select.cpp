@@ -45,6 +45,12 @@ MlpLaunchKey mlp_launch_key(const MlpClipArgs& a) {
   return k;
 }
 
+MlpLaunchKey mlp_launch_key(const MlpActArgs& a) {
+  MlpLaunchKey k = mlp_launch_key(static_cast<const MlpClipArgs&>(a));
+  k.act = a.act_kind;
+  return k;
+}
+
 static MlpChoice none(const char* why, bool plan_level) { return MlpChoice{MLP_NONE, false, why, plan_level}; }
 static MlpChoice take(MlpTrainer t, bool use_stage = false) { return MlpChoice{t, use_stage, nullptr, false}; }
 
@@ -65,6 +71,8 @@ MlpChoice mlp_select_trainer(const MlpShape& sh, bool use_wave, bool use_tile, c
     return none("AdamW / SGD need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.clipped)
     return none("gradient clipping needs the batch-tiled trainer's plan (bmax 1024)", true);
+  if (k.act != MLP_ACT_RELU)
+    return none("GELU / tanh-GELU / SiLU need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.weighted)
     return none("class weights / label smoothing need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.pending && !use_wave) return none("update-then-grad needs the single-wave kernel", true);

@@ -34,9 +34,12 @@ struct MlpLaunchKey {
                     // trainer's fold applies those; grad-mode launches apply no optimizer and never set it
   bool clipped;     // a train-mode launch with MlpClipArgs::clip_kind set: only the batch-tiled trainer clips the
                     // gradient between its fold and its optimizer; grad-mode launches ignore the clip fields
+  int act;          // MlpActArgs::act_kind (0 = ReLU): only the batch-tiled trainer has the smooth activations, in
+                    // train and in grad mode alike (the kind is part of the model)
 };
 MlpLaunchKey mlp_launch_key(const MlpArgs& a);  // the only place pointers become bools (clipped: false)
 MlpLaunchKey mlp_launch_key(const MlpClipArgs& a);  // the same, with `clipped` from the clip fields
+MlpLaunchKey mlp_launch_key(const MlpActArgs& a);   // the same, with `act` from the activation kind
 
 struct MlpChoice {
   MlpTrainer trainer;

@@ -88,7 +88,18 @@ __device__ __forceinline__ float drop_apply(float z, uint32_t seed, uint32_t gst
 // ACC: gradient accumulation (MlpArgs::accum > 1), chosen on the host likewise: the grid's second dimension is the
 // micro-batch kb of the window, workgroup (tile, kb) works on batch cur * accum + kb of the index list with that batch's
 // own bs and dropout step word gstep * accum + kb, and writes slot kb * T + tile.  Without it the kernel is as it was.
-template <int L, bool WL, bool ACC>
+// ACT: the hidden layers' activation (MlpAct, chosen on the host from MlpActArgs::act_kind): MLP_ACT_RELU is the kernel
+// as it was.  The ReLU backward rebuilds its mask from the stored activation; a smooth activation's derivative needs the
+// pre-activation z, which the tile does not keep.  Instead the forward epilogues of layers 0 and 1 - which hold z -
+// store A = keep * scale * act(z) where they store it today and the local derivative D = keep * scale * act'(z) into
+// the same (row, unit) of that layer's dZ image, idle until the backward; the two backward sites (head backward, dZ1
+// MFMA epilogue) multiply their incoming gradient by the D they find in place and overwrite it, dZ = g * D: each
+// element is written there by exactly the thread that reads it, behind the barriers that already separate forward
+// and backward.  No LDS image, no recomputation, no barrier more; dW1, dW0, the bias sums and the slots are untouched.
+// Rows >= bs: their D is act'(b0 ..), finite and not zero - it is their g that is an exact zero (dlogits of a dead
+// row are 0, and so is every product and MFMA sum of them), so dZ = 0 * D = 0.  Units beyond H1 / H2 are never
+// written and never read: the widths are multiples of 16 and every loop and column block stops at them.
+template <int L, bool WL, bool ACC, int ACT = MLP_ACT_RELU>
 __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds lo = lds_layout(L);
@@ -142,6 +153,14 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
   const auto drop = [&](int LI, int r, int o, float z) {
     return dropping ? drop_apply(z, a.seed, gstep, LI, row0 + r, o, a.dropout, dscale) : z;
   };
+  // the same of a smooth activation, on the pre-activation: one draw of the same key scales act(z) and act'(z)
+  const auto act_drop = [&](int LI, int r, int o, float z) {
+    float d = 0.f, av = z;
+    if constexpr (ACT != MLP_ACT_RELU) av = act_grad<ACT>(z, d);
+    const float ks = dropping ? drop_apply(1.0f, a.seed, gstep, LI, row0 + r, o, a.dropout, dscale) : 1.0f;
+    (LI == 0 ? dZ1 : dZ2)[r * LDH + o] = d * ks;
+    return av * ks;
+  };
 
   // ---- this wave's W1 fragments of the forward MFMA: issued first, so their L2 round trips overlap the
   // gather and layer 0 instead of chaining inside the k loop
@@ -164,7 +183,8 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
   __syncthreads();
 
   // ---- layer 0: A1 = dropout(relu(X0 W0^T + b0))
-  layer0(A1, W0s, X0, D0, H1, tid, drop);
+  if constexpr (ACT == MLP_ACT_RELU) layer0(A1, W0s, X0, D0, H1, tid, drop);
+  else layer0<ACT>(A1, W0s, X0, D0, H1, tid, act_drop);  // A1 = keep scale act(z), dZ1 = D
   __syncthreads();
 
   // ---- layer 1: A2 = dropout(relu(A1 W1^T + b1)); a wave owns column blocks wave, wave + 4
@@ -173,7 +193,8 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
     for (int c = 0; c < 2; ++c) {
       const int cb = wave + 4 * c;
       if (cb * 16 >= H2) break;
-      layer1_block(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, drop);
+      if constexpr (ACT == MLP_ACT_RELU) layer1_block(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, drop);
+      else layer1_block<ACT>(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, act_drop);  // dZ2 = D
     }
     __syncthreads();
   }
@@ -228,8 +249,12 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
 #pragma unroll
     for (int c = 0; c < 4; ++c)
       if (c < C) g = fmaf(dZL[r * 4 + c], Wl[c * K + k], g);
-    const float av = Ah[r * LDH + k];
-    dZh[r * LDH + k] = (av > 0.f) ? g * dscale : 0.f;
+    if constexpr (ACT == MLP_ACT_RELU) {
+      const float av = Ah[r * LDH + k];
+      dZh[r * LDH + k] = (av > 0.f) ? g * dscale : 0.f;
+    } else {
+      dZh[r * LDH + k] = g * dZh[r * LDH + k];  // the forward's D, in place
+    }
   }
   for (int e = tid; e < C * K; e += NT) {
     const int c = e / K, k = e - c * K;
@@ -282,8 +307,13 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r0 = 4 * q + i, r1 = r0 + 16;
-        dZ1[r0 * LDH + ic] = (A1[r0 * LDH + ic] > 0.f) ? acc0[i] * dscale : 0.f;
-        dZ1[r1 * LDH + ic] = (A1[r1 * LDH + ic] > 0.f) ? acc1[i] * dscale : 0.f;
+        if constexpr (ACT == MLP_ACT_RELU) {
+          dZ1[r0 * LDH + ic] = (A1[r0 * LDH + ic] > 0.f) ? acc0[i] * dscale : 0.f;
+          dZ1[r1 * LDH + ic] = (A1[r1 * LDH + ic] > 0.f) ? acc1[i] * dscale : 0.f;
+        } else {
+          dZ1[r0 * LDH + ic] = acc0[i] * dZ1[r0 * LDH + ic];  // layer 0's D, in place
+          dZ1[r1 * LDH + ic] = acc1[i] * dZ1[r1 * LDH + ic];
+        }
       }
     }
     // ---- dW1 = dZ2^T A1 on the MFMA (M = H2 outputs, N = H1 inputs, k = the tile's 32 rows)
@@ -648,12 +678,13 @@ static void launch_fold_clipped(int grid, const Plan& tp, const MlpClipArgs& a, 
 }
 
 // CLIPPED: a train-mode launch with a clip kind set - the same step kernel, launch_fold_clipped behind it
-template <int L, bool WL, bool ACC, bool CLIPPED = false>
+// ACT: the step kernel's activation; the folds behind it do not know it
+template <int L, bool WL, bool ACC, bool CLIPPED = false, int ACT = MLP_ACT_RELU>
 static hipError_t launch_steps(const Plan& tp, const std::conditional_t<CLIPPED, MlpClipArgs, MlpArgs>& a0,
                                unsigned int* done, hipStream_t st) {
   const int T = (a0.B + R - 1) / R;
   const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
-  auto fn = mlp_tile_step_kernel<L, WL, ACC>;
+  auto fn = mlp_tile_step_kernel<L, WL, ACC, ACT>;
   const int AK = ACC ? a0.accum : 1;  // micro-batches per optimizer step: the index list advances by AK * B rows
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
@@ -676,6 +707,9 @@ static hipError_t launch_steps(const Plan& tp, const std::conditional_t<CLIPPED,
 // the clipped launches' dispatch (defined behind dct_mlp_tile_train: their instantiations follow the unclipped ones)
 static hipError_t train_clipped(const Plan& tp, const MlpClipArgs& a, int L, bool wl, bool acc, unsigned int* done,
                                 hipStream_t st);
+// the smooth activations' dispatch (likewise behind it, and behind the clipped ones)
+static hipError_t train_act(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                            hipStream_t st);
 
 }  // namespace tile
 
@@ -735,9 +769,10 @@ long long dct_mlp_tile_clip_ws_floats(const int* dims, int L) {
   return dct::tile::make_plan(&tp, dims, L) ? dct::tile::clip_ws_layout(tp).total : 0;
 }
 
-int dct_mlp_tile_train(const int* dims, int L, const dct::MlpClipArgs* a, void* stream) {
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpActArgs* a, void* stream) {
   dct::tile::Plan tp;
   if (!dct::tile::plan_launch(&tp, dims, L, a->p)) return (int)hipErrorInvalidValue;
+  if (!dct::mlp_act_ok(a->act_kind)) return (int)hipErrorInvalidValue;
   if (a->B < 1 || a->B > dct::tile::BMAX || a->steps < 1 || a->n_items < 1) return (int)hipErrorInvalidValue;
   if (a->mode == 1 && a->steps != 1) return (int)hipErrorInvalidValue;
   const int accum = a->accum > 1 ? a->accum : 1;
@@ -753,10 +788,13 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpClipArgs* a, void* 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool wl = a->class_w || a->label_smooth != 0.f;
   if (!dct::mlp_tile_clip_ok(*a)) return (int)hipErrorInvalidValue;
-  if (a->mode == 0 && a->clip_kind != dct::MLP_CLIP_OFF) {
-    if (a->clip_kind == dct::MLP_CLIP_NORM &&
-        (!a->clip_ws || ((uintptr_t)a->clip_ws & 15) || a->clip_ws_floats < dct_mlp_tile_clip_ws_floats(dims, L)))
-      return (int)hipErrorInvalidValue;
+  const bool clipped = a->mode == 0 && a->clip_kind != dct::MLP_CLIP_OFF;
+  if (clipped && a->clip_kind == dct::MLP_CLIP_NORM &&
+      (!a->clip_ws || ((uintptr_t)a->clip_ws & 15) || a->clip_ws_floats < dct_mlp_tile_clip_ws_floats(dims, L)))
+    return (int)hipErrorInvalidValue;
+  // a smooth activation: its own step-kernel instantiations in train and grad mode alike, every fold as it is
+  if (a->act_kind != dct::MLP_ACT_RELU) return (int)dct::tile::train_act(tp, *a, L, wl, accum > 1, done, st);
+  if (clipped) {
     return (int)dct::tile::train_clipped(tp, *a, L, wl, accum > 1, done, st);
   }
   // (the plain instantiations first: they keep their place at the head of the code object)
@@ -793,6 +831,40 @@ static hipError_t train_clipped(const Plan& tp, const MlpClipArgs& a, int L, boo
                   : launch_steps<3, true, true, true>(tp, a, done, st);
   return L == 2 ? launch_steps<2, false, true, true>(tp, a, done, st)
                 : launch_steps<3, false, true, true>(tp, a, done, st);
+}
+
+template <int ACT, bool CLIPPED>
+static hipError_t train_act_steps(const Plan& tp, const MlpClipArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                                  hipStream_t st) {
+  if (!acc) {
+    if (wl)
+      return L == 2 ? launch_steps<2, true, false, CLIPPED, ACT>(tp, a, done, st)
+                    : launch_steps<3, true, false, CLIPPED, ACT>(tp, a, done, st);
+    return L == 2 ? launch_steps<2, false, false, CLIPPED, ACT>(tp, a, done, st)
+                  : launch_steps<3, false, false, CLIPPED, ACT>(tp, a, done, st);
+  }
+  if (wl)
+    return L == 2 ? launch_steps<2, true, true, CLIPPED, ACT>(tp, a, done, st)
+                  : launch_steps<3, true, true, CLIPPED, ACT>(tp, a, done, st);
+  return L == 2 ? launch_steps<2, false, true, CLIPPED, ACT>(tp, a, done, st)
+                : launch_steps<3, false, true, CLIPPED, ACT>(tp, a, done, st);
+}
+
+template <int ACT>
+static hipError_t train_act_kind(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                                 hipStream_t st) {
+  if (a.mode == 0 && a.clip_kind != MLP_CLIP_OFF) return train_act_steps<ACT, true>(tp, a, L, wl, acc, done, st);
+  return train_act_steps<ACT, false>(tp, a, L, wl, acc, done, st);
+}
+
+static hipError_t train_act(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                            hipStream_t st) {
+  switch (a.act_kind) {
+    case MLP_ACT_GELU: return train_act_kind<MLP_ACT_GELU>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_GELU_TANH: return train_act_kind<MLP_ACT_GELU_TANH>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_SILU: return train_act_kind<MLP_ACT_SILU>(tp, a, L, wl, acc, done, st);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace tile

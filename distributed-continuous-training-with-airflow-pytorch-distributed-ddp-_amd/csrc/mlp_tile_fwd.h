@@ -3,7 +3,8 @@
 // the device pieces each kernel calls in its own order - W1 fragment load, weight staging, layer 0 on the VALU,
 // layer 1 on v_mfma_f32_16x16x4_f32 (exact fp32), head logits.  The gather, the loss and the LDS carve stay with
 // each kernel.  Layers 0 and 1 hand every post-ReLU value to an epilogue epi(layer, row in the tile, unit, z):
-// the trainer's dropout, the inference kernel's identity.
+// the trainer's dropout, the inference kernel's identity.  With a smooth activation (GELU, tanh-GELU, SiLU) they hand
+// over the pre-activation instead and the epilogue applies act_grad / ActEpilogue below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +63,46 @@ struct NoEpilogue {
   __device__ __forceinline__ float operator()(int, int, int, float z) const { return z; }
 };
 
+// ---- the smooth activations (MlpAct 1 .. 3; ACT = 0, ReLU, is the fmaxf in layer0 / layer1_block themselves).
+// act_grad returns act(z) and leaves act'(z) in d; both come from ONE transcendental's worth of shared terms, in fp32
+// with the full-precision library functions:
+//   gelu       Phi = 0.5 (1 + erff(z / sqrt 2)), phi = exp(-z^2 / 2) / sqrt(2 pi):  z Phi,  Phi + z phi
+//   gelu_tanh  t = tanhf(c (z + 0.044715 z^3)), c = sqrt(2 / pi):  0.5 z (1 + t),
+//              0.5 (1 + t) + 0.5 z (1 - t^2) c (1 + 3 * 0.044715 z^2)     (torch's approximate="tanh" and its backward)
+//   silu       s = 1 / (1 + expf(-z)):  z s,  s (1 + z (1 - s))
+// Every value is finite for a finite z of any size the forward can produce (exp underflows to 0, s to 0 or 1), so
+// 0 * act' is an exact zero - what the trainer's backward relies on for the rows beyond the batch.
+template <int ACT>
+__device__ __forceinline__ float act_grad(float z, float& d) {
+  static_assert(ACT >= 1 && ACT <= 3, "a smooth MlpAct");
+  if constexpr (ACT == 1) {
+    const float Phi = 0.5f * (1.0f + erff(z * 0.70710678118654752440f));
+    const float phi = 0.39894228040143267794f * expf(-0.5f * z * z);
+    d = fmaf(z, phi, Phi);
+    return z * Phi;
+  } else if constexpr (ACT == 2) {
+    const float c = 0.79788456080286535588f, k = 0.044715f;
+    const float z2 = z * z;
+    const float t = tanhf(c * fmaf(k * z2, z, z));
+    const float h = 0.5f * (1.0f + t);
+    d = fmaf(0.5f * z * (1.0f - t * t), c * fmaf(3.0f * k, z2, 1.0f), h);
+    return z * h;
+  } else {
+    const float s = 1.0f / (1.0f + expf(-z));
+    d = s * fmaf(z, 1.0f - s, 1.0f);
+    return z * s;
+  }
+}
+
+// the forward alone (the inference kernel's epilogue): act_grad's value, its unused derivative left to the compiler
+template <int ACT>
+struct ActEpilogue {
+  __device__ __forceinline__ float operator()(int, int, int, float z) const {
+    float d;
+    return act_grad<ACT>(z, d);
+  }
+};
+
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
@@ -91,21 +132,22 @@ __device__ __forceinline__ void stage_weights(float* W0s, float* Wl, const float
   if (tid < tp.H1) W0s[tid * LDX + 32] = p[tp.boff[0] + tid];
 }
 
-// Layer 0 (VALU): A1 = epi(relu(X0 W0^T + b0))
-template <class Epi>
+// Layer 0 (VALU): A1 = epi(relu(X0 W0^T + b0)).  ACT != 0 (a smooth MlpAct): epi gets the pre-activation z itself
+// and applies the activation (ActEpilogue, or the trainer's, which also leaves act'(z) in the dZ image).
+template <int ACT = 0, class Epi>
 __device__ __forceinline__ void layer0(float* A1, const float* W0s, const float* X0, int D0, int H1, int tid,
                                        Epi epi) {
   for (int e = tid; e < R * H1; e += NT) {
     const int r = e / H1, o = e - r * H1;
     float z = W0s[o * LDX + 32];  // b0, staged in the pad column
     for (int k = 0; k < D0; ++k) z = fmaf(W0s[o * LDX + k], X0[r * LDX + k], z);
-    A1[r * LDH + o] = epi(0, r, o, fmaxf(z, 0.f));
+    A1[r * LDH + o] = epi(0, r, o, ACT == 0 ? fmaxf(z, 0.f) : z);
   }
 }
 
 // Column block cb of layer 1 (MFMA): A2[:, 16 cb ..] = epi(relu(A1 W1^T + b1)), two M = 16 row blocks per weight
-// fragment; wf: the block's fragments from load_w1_frags, bv: b1 of this lane's unit 16 cb + j.
-template <class Epi>
+// fragment; wf: the block's fragments from load_w1_frags, bv: b1 of this lane's unit 16 cb + j.  ACT as in layer0.
+template <int ACT = 0, class Epi>
 __device__ __forceinline__ void layer1_block(float* A2, const float* A1, const float4 (&wf)[8], int cb, float bv,
                                              int H1, int j, int q, Epi epi) {
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -131,8 +173,8 @@ __device__ __forceinline__ void layer1_block(float* A2, const float* A1, const f
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r0 = 4 * q + i, r1 = r0 + 16;
-    A2[r0 * LDH + o] = epi(1, r0, o, fmaxf(acc0[i] + bv, 0.f));
-    A2[r1 * LDH + o] = epi(1, r1, o, fmaxf(acc1[i] + bv, 0.f));
+    A2[r0 * LDH + o] = epi(1, r0, o, ACT == 0 ? fmaxf(acc0[i] + bv, 0.f) : acc0[i] + bv);
+    A2[r1 * LDH + o] = epi(1, r1, o, ACT == 0 ? fmaxf(acc1[i] + bv, 0.f) : acc1[i] + bv);
   }
 }
 

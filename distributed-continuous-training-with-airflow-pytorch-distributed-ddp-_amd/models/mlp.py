@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.fused_mlp import check_class_weight, check_label_smoothing, check_optimizer
+from ..ops.fused_mlp import check_activation, check_class_weight, check_label_smoothing, check_optimizer
 from ..trainer.module import TrainModule
 
 # configure_optimizers()'s options and their defaults, which reproduce the reference's Adam(lr): a model records only
@@ -29,14 +29,25 @@ OPTIM_DEFAULTS = dict(optimizer="adam", weight_decay=0.0, momentum=0.0, dampenin
                       betas=(0.9, 0.999), eps=1e-8)
 
 
+def activation_module(activation: str) -> nn.Module:
+    """The torch module of a hidden activation name (ops.fused_mlp.ACTIVATIONS)."""
+    return {"relu": nn.ReLU, "gelu": nn.GELU, "gelu_tanh": lambda: nn.GELU(approximate="tanh"),
+            "silu": nn.SiLU}[check_activation(activation)]()
+
+
 class MLPClassifier(TrainModule):
     def __init__(self, input_dim: int, hidden: Sequence[int] = (64,), num_classes: int = 2, dropout: float = 0.2,
                  loss: str = "ce", lr: float = 0.01, class_weight: Optional[Sequence[float]] = None,
                  label_smoothing: float = 0.0, optimizer: str = "adam", weight_decay: float = 0.0,
                  momentum: float = 0.0, nesterov: bool = False, betas: Sequence[float] = (0.9, 0.999),
-                 eps: float = 1e-8, dampening: float = 0.0):
+                 eps: float = 1e-8, dampening: float = 0.0, activation: str = "relu"):
         super().__init__()
         self.save_hyperparameters()
+        # the hidden layers' activation (every hidden layer the same, the head linear): recorded only when it is not
+        # the ReLU a model always had
+        self.activation = check_activation(activation)
+        if self.activation == "relu":
+            self.hparams.pop("activation", None)
         # the optimizer configure_optimizers() builds: torch.optim.Adam / AdamW / SGD, checked with torch's rules here
         # (an unknown name, a negative decay or momentum, Nesterov without momentum or with dampening: ValueError)
         self.optim = dict(optimizer=check_optimizer(optimizer, weight_decay, momentum, dampening, nesterov),
@@ -72,7 +83,7 @@ class MLPClassifier(TrainModule):
         for i in range(len(dims) - 1):
             layers.append(nn.Linear(dims[i], dims[i + 1]))
             if i < len(dims) - 2:
-                layers += [nn.ReLU(), nn.Dropout(dropout)]
+                layers += [activation_module(self.activation), nn.Dropout(dropout)]  # (same slot: net.<3i> keys)
         self.net = nn.Sequential(*layers)
         self.dims = dims
         self.dropout_p = float(dropout)
@@ -127,6 +138,8 @@ class MLPClassifier(TrainModule):
             spec["class_weight"] = self.class_weight.detach().float().cpu()
         if self.label_smoothing != 0.0:
             spec["label_smoothing"] = self.label_smoothing
+        if self.activation != "relu":
+            spec["activation"] = self.activation
         return spec
 
     def linear_layers(self) -> List[nn.Linear]:
@@ -137,9 +150,9 @@ class WeatherClassifier(MLPClassifier):
     """Reference model: Linear(D,64)-ReLU-Dropout(0.2)-Linear(64,2), CE, Adam(lr=0.01)."""
 
     def __init__(self, input_dim: int, class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0,
-                 **optim):
+                 activation: str = "relu", **optim):
         super().__init__(input_dim=input_dim, hidden=(64,), num_classes=2, dropout=0.2, loss="ce", lr=0.01,
-                         class_weight=class_weight, label_smoothing=label_smoothing, **optim)
+                         class_weight=class_weight, label_smoothing=label_smoothing, activation=activation, **optim)
         # the reference records exactly {"input_dim": D} (save_hyperparameters at :53); the loss and optimizer options
         # join it only when set
         hp = {"input_dim": int(input_dim)}
@@ -148,16 +161,19 @@ class WeatherClassifier(MLPClassifier):
             hp["class_weight"] = [float(x) for x in self.class_weight.tolist()]
         if self.label_smoothing != 0.0:
             hp["label_smoothing"] = self.label_smoothing
+        if self.activation != "relu":
+            hp["activation"] = self.activation
         self._set_hparams(hp)
 
 
 def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None, num_classes: int = 2,
               dropout: float = 0.2, loss: str = "ce", lr: float = 0.01,
               class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0,
-              **optim) -> MLPClassifier:
+              activation: str = "relu", **optim) -> MLPClassifier:
     """``optim``: MLPClassifier's optimizer options (OPTIM_DEFAULTS' keys)."""
     if name == "weather":
-        return WeatherClassifier(input_dim, class_weight=class_weight, label_smoothing=label_smoothing, **optim)
+        return WeatherClassifier(input_dim, class_weight=class_weight, label_smoothing=label_smoothing,
+                                 activation=activation, **optim)
     # name -> (hidden widths, dropout, loss, lr); BASELINE.json configs 1-4
     presets = {
         "weather-mlp-3x128": ((128, 128), 0.2, "ce", 0.01),
@@ -166,4 +182,4 @@ def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None,
     if name in presets and hidden is None:
         hidden, dropout, loss, lr = presets[name]
     return MLPClassifier(input_dim, hidden=hidden or (64,), num_classes=num_classes, dropout=dropout, loss=loss, lr=lr,
-                         class_weight=class_weight, label_smoothing=label_smoothing, **optim)
+                         class_weight=class_weight, label_smoothing=label_smoothing, activation=activation, **optim)

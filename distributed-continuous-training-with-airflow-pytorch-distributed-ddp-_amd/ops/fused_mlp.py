@@ -76,6 +76,25 @@ def check_optimizer(optimizer, weight_decay: float = 0.0, momentum: float = 0.0,
     return optimizer
 
 
+ACTIVATIONS = ("relu", "gelu", "gelu_tanh", "silu")  # csrc/mlp_fused.h MlpAct, in its order
+
+
+def check_activation(activation) -> str:
+    """The hidden layers' activation of a model or a launch: ``"relu"``, ``"gelu"`` (erf form, torch's default),
+    ``"gelu_tanh"`` (``approximate="tanh"``) or ``"silu"``; ValueError for anything else."""
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of {ACTIVATIONS}, got {activation!r}")
+    return activation
+
+
+def activation_fn(activation):
+    """The torch functional of an activation name (the references of the tests and of the torch fallbacks)."""
+    import torch.nn.functional as F
+
+    return {"relu": F.relu, "gelu": F.gelu, "gelu_tanh": lambda t: F.gelu(t, approximate="tanh"),
+            "silu": F.silu}[check_activation(activation)]
+
+
 def _mix_hash(a, b, c):
     """csrc/mlp_fused_impl.h mix_hash on numpy uint32 arrays (wrapping arithmetic)."""
     import numpy as np
@@ -245,6 +264,15 @@ class FusedMLPKernel:
             return dict(optimizer="sgd", momentum=float(momentum), dampening=float(dampening), nesterov=bool(nesterov))
         return dict(optimizer="adamw")
 
+    def _check_activation(self, activation, batch: int) -> dict:
+        """The native argument of a launch of a non-ReLU model ({} for ReLU), in train and in grad mode alike."""
+        if check_activation(activation) == "relu":
+            return {}
+        if self.plan.trainer(int(batch), activation=activation) != "tile":
+            raise ValueError(f"activation={activation!r} needs the batch-tiled trainer: a plan of bmax 1024 "
+                             "(any batch 1..1024) for an architecture it takes")
+        return dict(activation=activation)
+
     def _check_clip(self, clip_val, clip_algorithm: str, batch: int, device, train: bool) -> dict:
         """The native arguments of a launch that clips its gradient ({} when off, and for a grad-mode launch, which
         ignores clipping).  By norm the launch gets this kernel's workspace, allocated once (launches bound earlier
@@ -381,8 +409,12 @@ class FusedMLPKernel:
               lr_tab: Optional[torch.Tensor] = None, class_weight: Optional[torch.Tensor] = None,
               label_smoothing: float = 0.0, accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0,
               dampening: float = 0.0, nesterov: bool = False, clip_val: Optional[float] = None,
-              clip_algorithm: str = "norm"):
+              clip_algorithm: str = "norm", activation: str = "relu"):
         """Run ``steps`` fused optimizer steps (mode 0) or one gradient step (grad_out given).
+
+        ``activation``: the hidden layers' ``"relu"``, or on the batch-tiled trainer's plan ``"gelu"``, ``"gelu_tanh"``
+        or ``"silu"`` (every hidden layer the same, the head linear).  It is part of the model: a grad-mode launch
+        honours it too.
 
         ``clip_val`` / ``clip_algorithm`` (Lightning's ``gradient_clip_val`` / ``gradient_clip_algorithm``; the
         batch-tiled trainer's plan only): the step's final gradient - after the fold, the weighted mean and the
@@ -428,6 +460,7 @@ class FusedMLPKernel:
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
         clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, mode == 0)
+        act_args = self._check_activation(activation, batch)
         if steps < 1 or (cursor is None and (steps - 1) * batch * accumulate >= n_items):
             raise ValueError("steps do not match the index list")
         if cursor is not None and (mode != 1 or not (cursor.is_cuda and cursor.dtype == torch.int32)):
@@ -461,7 +494,7 @@ class FusedMLPKernel:
             ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending), ptr(stage),
             stream if stream is not None else stream_handle(),
             **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab), **wl_args,
-            **acc_args, **opt_args, **clip_args,
+            **acc_args, **opt_args, **clip_args, **act_args,
         )
 
     def prepare_train(self, p, m, v, X, Y, idx, n_items: int, batch: int, lr: float, betas=(0.9, 0.999),
@@ -472,7 +505,7 @@ class FusedMLPKernel:
                       class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
                       accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0, dampening: float = 0.0,
                       nesterov: bool = False, clip_val: Optional[float] = None,
-                      clip_algorithm: str = "norm") -> "BoundTrain":
+                      clip_algorithm: str = "norm", activation: str = "relu") -> "BoundTrain":
         """Validate the operands of persistent train-mode launches ONCE and bind them natively.
 
         ``BoundTrain.run(first_step, steps)`` then launches steps [first_step, first_step+steps)
@@ -480,7 +513,7 @@ class FusedMLPKernel:
         positional native call (no keyword parsing, no tensor checks), which is what the short
         timed windows of the benchmark contract see.  ``accumulate`` as in ``train``: the steps are
         optimizer steps of ``accumulate`` micro-batches each.  ``optimizer`` / ``momentum`` / ``dampening`` /
-        ``nesterov`` and ``clip_val`` / ``clip_algorithm`` as in ``train``."""
+        ``nesterov``, ``clip_val`` / ``clip_algorithm`` and ``activation`` as in ``train``."""
         if not 1 <= batch <= self.bmax:
             raise ValueError(f"batch {batch} outside 1..{self.bmax}")
         opt_args = self._check_optimizer(optimizer, batch, weight_decay, momentum, dampening, nesterov, True)
@@ -490,6 +523,7 @@ class FusedMLPKernel:
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
         clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, True)
+        act_args = self._check_activation(activation, batch)
         if step_counter is None or not (step_counter.is_cuda and step_counter.dtype == torch.int32):
             raise ValueError("step_counter must be a cuda int32 scalar tensor (launches are step-relative)")
         if loss_out is not None and not (loss_out.is_cuda and loss_out.dtype == torch.float32
@@ -514,7 +548,7 @@ class FusedMLPKernel:
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, ptr(loss_out), 0 if loss_out is None else loss_out.numel(), LOSS_KINDS[loss],
             ptr(step_counter), **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab),
-            **wl_args, **acc_args, **opt_args, **clip_args)
+            **wl_args, **acc_args, **opt_args, **clip_args, **act_args)
         return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws, lr_tab,
                                    class_weight, self._clip_ws),
                           p.device.index or 0)
@@ -583,7 +617,8 @@ class FusedMLPKernel:
               loss: str = "ce", logits_out: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
               pred_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, norm=None,
               grid: Optional[int] = None, stream: Optional[int] = None,
-              class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0):
+              class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
+              activation: str = "relu"):
         """One forward-only launch over rows ``idx[0 .. n)`` of ``X`` (``idx=None``: rows ``0 .. n - 1``).
 
         Per-row outputs, each optional: ``logits_out`` / ``probs_out`` fp32 [n, C], ``pred_out`` int32 [n] (argmax,
@@ -595,7 +630,9 @@ class FusedMLPKernel:
         and ``n`` only - not on ``grid``, not on the run.  Without ``Y`` nothing is written to ``stats_out``.
 
         ``class_weight`` (cuda fp32 [C]) / ``label_smoothing`` as in ``train`` (CE only): word 0 is then the numerator
-        ``sum_i num_i`` of torch's weighted mean; ``weighted_infer_stats`` divides it by ``W``."""
+        ``sum_i num_i`` of torch's weighted mean; ``weighted_infer_stats`` divides it by ``W``.
+
+        ``activation``: the model's hidden activation, as in ``train``."""
         if not self.infer_supported(self.dims):
             raise ValueError(f"the inference kernel does not take the architecture {self.dims}")
         self._check_params(p)
@@ -631,6 +668,8 @@ class FusedMLPKernel:
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self.dims[0]):
                     raise ValueError(f"norm = (mean, std) must be contiguous cuda fp32 [{self.dims[0]}] each")
         wl_args = self._check_wloss(class_weight, label_smoothing, loss, p.device)
+        if check_activation(activation) != "relu":
+            wl_args = dict(wl_args, activation=activation)
         ws = self._infer_ws(p.device, n) if Y is not None else None
         native().mlp_infer(self.dims, ptr(p), ptr(X), X.stride(0), ptr(idx), ptr(Y), n, ptr(mean), ptr(std),
                            LOSS_KINDS[loss], ptr(logits_out), ptr(probs_out), ptr(pred_out), ptr(ws),
@@ -673,8 +712,10 @@ class BoundTrain:
 
 
 # ---------------------------------------------------------------------------- reference
-def reference_mlp_forward(p: torch.Tensor, dims: Sequence[int], x: torch.Tensor) -> torch.Tensor:
-    """Plain-torch fp32 forward of the flat-parameter MLP (no dropout), for numerics tests."""
+def reference_mlp_forward(p: torch.Tensor, dims: Sequence[int], x: torch.Tensor,
+                          activation: str = "relu") -> torch.Tensor:
+    """Plain-torch forward of the flat-parameter MLP (no dropout) in p's dtype, for numerics tests."""
+    act = activation_fn(activation)
     off = 0
     h = x
     L = len(dims) - 1
@@ -686,5 +727,5 @@ def reference_mlp_forward(p: torch.Tensor, dims: Sequence[int], x: torch.Tensor)
         off += o
         h = h @ W.t() + b
         if l < L - 1:
-            h = torch.relu(h)
+            h = act(h)
     return h

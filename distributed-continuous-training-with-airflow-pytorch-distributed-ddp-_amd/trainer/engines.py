@@ -97,6 +97,11 @@ def spec_weighted(spec: Dict) -> bool:
     return spec.get("class_weight") is not None or float(spec.get("label_smoothing", 0.0)) != 0.0
 
 
+def spec_activation(spec: Dict) -> str:
+    """The hidden activation a fused_spec() asks for (models/mlp.py carries the key only when it is not ReLU)."""
+    return spec.get("activation", "relu")
+
+
 class _EngineBase:
     name = "base"
 
@@ -144,6 +149,9 @@ class FusedMLPEngine(_EngineBase):
         if spec_weighted(spec):
             # class weights / label smoothing: only the batch-tiled trainer computes that loss, at any batch it takes
             return spec["loss"] == "ce" and tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
+        if spec_activation(spec) != "relu":
+            # GELU / tanh-GELU / SiLU: only the batch-tiled trainer has them, at any batch it takes
+            return tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
         return FusedMLPKernel.supported(spec["dims"], batch_size)
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,
@@ -192,7 +200,11 @@ class FusedMLPEngine(_EngineBase):
         # class-weighted / label-smoothed CE (models/mlp.py): the batch-tiled trainer's plan whatever the batch, and
         # the two arguments on every train launch; validation through the tiled inference kernel
         self.weighted = spec_weighted(spec)
-        tiled = self.weighted or self.K > 1 or self.kind != "adam" or bool(self.clip) or tile_plan
+        # a non-ReLU hidden activation (models/mlp.py): the tile plan likewise, the kind on every train-mode and
+        # grad-mode launch (it is part of the model), validation through the tiled inference kernel.  Under DDP the step
+        # path is the tile plan's: grad-mode launch -> RCCL -> flat optimizer
+        self.activation = spec_activation(spec)
+        tiled = self.weighted or self.activation != "relu" or self.K > 1 or self.kind != "adam" or bool(self.clip) or tile_plan
         bmax = TILE_BMAX if tiled else (4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
         self.kernel = FusedMLPKernel(self.dims, bmax=bmax)
         if self.K > 1 and self.kernel.plan.trainer(self.B, accumulate=self.K) != "tile":
@@ -206,6 +218,8 @@ class FusedMLPEngine(_EngineBase):
         self.wloss = {}
         if self.weighted:
             self.wloss = dict(class_weight=self.class_weight, label_smoothing=float(spec.get("label_smoothing", 0.0)))
+        if self.activation != "relu":  # (rides with the loss options: every train, grad and infer launch gets them)
+            self.wloss["activation"] = self.activation
         self.p = self._flat_from_model().to(dev)
         self.m = torch.zeros_like(self.p)
         self.v = torch.zeros_like(self.p)
@@ -684,8 +698,8 @@ class FusedMLPEngine(_EngineBase):
         if r.numel() > self.val_idx.numel():
             self.val_idx = torch.zeros(r.numel(), dtype=torch.int32, device=self.device)
         self.val_idx[: r.numel()].copy_(r)
-        if self.weighted:
-            # mlp_eval_kernel knows no weights: one launch of the tiled inference kernel over the shard, the weighted
+        if self.weighted or self.activation != "relu":
+            # mlp_eval_kernel knows no weights and only ReLU: one launch of the tiled inference kernel over the shard, the weighted
             # mean sum_i num_i / sum_i w[y_i] of the whole shard, then the cross-rank mean as below
             stats = getattr(self, "_infer_stats", None)
             if stats is None:

@@ -155,6 +155,8 @@ def _native_launch(trainer, model, X, Y, local, want_logits: bool):
     if weighted:
         wl = dict(class_weight=None if cw is None else torch.as_tensor(cw, dtype=torch.float32).contiguous().to(dev),
                   label_smoothing=eps)
+    if spec.get("activation", "relu") != "relu":  # the model's hidden activation (absent: ReLU)
+        wl["activation"] = spec["activation"]
     kern.infer(_flat_params(model, dev), Xd, n, idx=idx, Y=Yd, loss=spec["loss"], logits_out=logits,
                stats_out=stats, norm=_norm_on(trainer, dev), **wl)
     if stats is None:

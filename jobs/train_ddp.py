@@ -53,6 +53,8 @@ def parse_args(argv=None):
                         "w0,w1,... (MLP family; default: none)")
     p.add_argument("--label-smoothing", type=float, default=cfg.model.label_smoothing,
                    help="cross-entropy label smoothing in [0, 1) (MLP family; default 0)")
+    p.add_argument("--activation", default=cfg.model.activation, choices=("relu", "gelu", "gelu_tanh", "silu"),
+                   help="hidden activation of the MLP family (default relu)")
     p.add_argument("--tracking-uri", default=cfg.tracking.tracking_uri)
     p.add_argument("--experiment", default=cfg.tracking.experiment_name)
     p.add_argument("--accelerator", default=cfg.train.accelerator)
@@ -118,6 +120,8 @@ def main(argv=None) -> int:
         loss_kw["class_weight"] = class_weight
     if a.label_smoothing:
         loss_kw["label_smoothing"] = a.label_smoothing
+    if a.activation != "relu":
+        loss_kw["activation"] = a.activation
     model = build_model(a.model, input_dim, lr=a.lr, **loss_kw, **model_optim_kwargs(a))
 
     world_size = int(os.environ.get("WORLD_SIZE", 1))
