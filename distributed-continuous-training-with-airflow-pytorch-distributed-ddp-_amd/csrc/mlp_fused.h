@@ -198,6 +198,22 @@ struct MlpActArgs : MlpClipArgs {
   int act_kind;
 };
 
+// A normalisation layer between every hidden Linear and its activation (the head stays a plain Linear): MLP_NORM_OFF is
+// every kernel as it always was; MLP_NORM_LAYER is torch's nn.LayerNorm(H, eps = 1e-5, elementwise_affine = True) over
+// the layer's H units - biased variance, u = gamma * (z - mean) * rstd + beta, then activation and dropout.  Batch-tiled
+// trainer and batch-tiled inference kernel only.  Its parameters follow all linears in the flat buffer:
+// gamma_1 [H1], beta_1 [H1] (, gamma_2 [H2], beta_2 [H2]), so every woff / boff stands and P grows by 2 (H1 + H2).
+enum MlpNorm { MLP_NORM_OFF = 0, MLP_NORM_LAYER = 1 };
+inline bool mlp_norm_ok(int kind) { return kind == MLP_NORM_OFF || kind == MLP_NORM_LAYER; }
+
+// MlpNormArgs: MlpActArgs with the norm kind behind the activation kind - what the host builds and hands to the
+// launchers.  No kernel takes it: the batch-tiled trainer's step kernel gets the kind as a template argument, like the
+// activation.  Part of the model, so grad-mode launches honour it.  mlp_select.h refuses a normed launch on every
+// other trainer.
+struct MlpNormArgs : MlpActArgs {
+  int norm_kind;
+};
+
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
 
 // One launch of the batch-tiled inference kernel (mlp_infer.hip): forward only, rows 0 .. n - 1 of the index
@@ -227,6 +243,13 @@ struct MlpInferArgs {
   float label_smooth;
   // the hidden layers' activation (MlpAct; appended, so every other field keeps its offset): 0 = ReLU
   int act_kind;
+};
+
+// MlpInferNormArgs: what the host hands to dct_mlp_infer - MlpInferArgs with LayerNorm in every hidden layer (MlpNorm;
+// p then carries the gamma / beta tail) behind it.  The kernel takes the MlpInferArgs prefix, whose size stands, and
+// the kind as a template argument.
+struct MlpInferNormArgs : MlpInferArgs {
+  int norm_kind;
 };
 
 // fills *sh for dims[0 .. L] and plans of up to bmax rows per step (mlp_block = -1: auto, until the plan stamps
@@ -272,13 +295,18 @@ int dct_mlp_tile_max_slots(void);
 // floats of MlpClipArgs::clip_ws (clipping by norm): gf[P + 1], part[ceil((P + 1) / 256)] and {norm, coef}, each on a
 // 16-byte boundary (0: not a tile shape)
 long long dct_mlp_tile_clip_ws_floats(const int* dims, int L);
+// the two workspace sizes and the parameter count of a model with MlpNormArgs::norm_kind = norm (MlpNorm), whose P
+// carries the gamma / beta tail; norm = 0: the values above (accum <= 1: one micro-batch) and the linears' count
+long long dct_mlp_tile_ws_floats_norm(const int* dims, int L, int B, int accum, int norm);
+long long dct_mlp_tile_clip_ws_floats_norm(const int* dims, int L, int norm);
+long long dct_mlp_tile_num_params(const int* dims, int L, int norm);
 // hipErrorInvalidValue also for an unknown clip_kind, a clip_val that is not a finite value > 0 while the kind is set,
 // and norm clipping without a clip_ws of that size (train mode; grad mode ignores the clip fields), and for an
-// act_kind that is no MlpAct (both modes)
-int dct_mlp_tile_train(const int* dims, int L, const dct::MlpActArgs* a, void* stream);
+// act_kind that is no MlpAct or a norm_kind that is no MlpNorm (both modes)
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpNormArgs* a, void* stream);
 // batch-tiled forward-only inference (mlp_infer.hip); grid <= 0: default.  It and dct_mlp_tile_train share one
 // forward and one host check (mlp_tile_fwd.h): the shapes of dct_mlp_tile_supported, p on a 16-byte boundary;
-// hipErrorInvalidValue also for an act_kind that is no MlpAct
-int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, void* stream);
+// hipErrorInvalidValue also for an act_kind that is no MlpAct or a norm_kind that is no MlpNorm
+int dct_mlp_infer(const int* dims, int L, const dct::MlpInferNormArgs* a, int grid, void* stream);
 long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n);
 }

@@ -78,7 +78,10 @@ __device__ __forceinline__ float pick4(const float (&v)[4], int i) {
 // instantiation is the kernel as it was
 // ACT: the hidden layers' activation (MlpInferArgs::act_kind, chosen on the host likewise): MLP_ACT_RELU is the kernel
 // as it was, the smooth kinds run the trainer's own act(z) (mlp_tile_fwd.h act_grad) in the two layers' epilogues
-template <int L, bool WL, int ACT = MLP_ACT_RELU>
+// NORM: LayerNorm in every hidden layer (MlpInferNormArgs::norm_kind, chosen on the host likewise; false is the kernel as it
+// was): the layers store the pre-norm z + b and the trainer's own norm_rows (mlp_tile_fwd.h) normalises the image in
+// place behind a barrier, A = act(gamma * xhat + beta) - xhat and rstd are not kept, the LDS carve does not grow
+template <int L, bool WL, int ACT = MLP_ACT_RELU, bool NORM = false>
 __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, long long T, long long S, int nslots) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds lo = lds_layout(L);
@@ -154,7 +157,12 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
       __syncthreads();
 
       // ---- layer 0: A1 = relu(X0 W0^T + b0)
-      if constexpr (ACT == MLP_ACT_RELU) layer0(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
+      if constexpr (NORM) {
+        layer0<1>(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
+        __syncthreads();
+        const int go = norm_off(tp, 0);
+        norm_rows(A1, nullptr, a.p + go, a.p + go + H1, H1, 0, tid, NormActEpilogue<ACT>{});
+      } else if constexpr (ACT == MLP_ACT_RELU) layer0(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
       else layer0<ACT>(A1, W0s, X0, D0, H1, tid, ActEpilogue<ACT>{});
       __syncthreads();
 
@@ -164,10 +172,16 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
         for (int c = 0; c < 2; ++c) {
           const int cb = wave + 4 * c;
           if (cb * 16 >= H2) break;
-          if constexpr (ACT == MLP_ACT_RELU) layer1_block(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
+          if constexpr (NORM) layer1_block<1>(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
+          else if constexpr (ACT == MLP_ACT_RELU) layer1_block(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
           else layer1_block<ACT>(A2, A1, wf[c], cb, b1v[c], H1, j, q, ActEpilogue<ACT>{});
         }
         __syncthreads();
+        if constexpr (NORM) {
+          const int go = norm_off(tp, 1);
+          norm_rows(A2, nullptr, a.p + go, a.p + go + H2, H2, 1, tid, NormActEpilogue<ACT>{});
+          __syncthreads();
+        }
       }
 
       // ---- head (all 8 lanes of a row hold its logits) + outputs + row loss
@@ -274,10 +288,10 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_infer_fold_kernel(const long long
   }
 }
 
-template <int L, bool WL, int ACT = MLP_ACT_RELU>
+template <int L, bool WL, int ACT = MLP_ACT_RELU, bool NORM = false>
 static hipError_t launch(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
   const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
-  auto fn = mlp_infer_kernel<L, WL, ACT>;
+  auto fn = mlp_infer_kernel<L, WL, ACT, NORM>;
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), bytes, st, tp, a, sl.T, sl.S, sl.nslots);
@@ -288,8 +302,10 @@ static hipError_t launch(const Plan& tp, const MlpInferArgs& a, const Slots& sl,
 }
 
 // a smooth activation's launch (instantiated behind the ReLU kernels, which keep their place in the code object)
-template <int ACT>
+template <int ACT, bool NORM = false>
 static hipError_t launch_act(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st);
+// a normed model's launch (behind all of them)
+static hipError_t launch_norm(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st);
 
 }  // namespace infer
 }  // namespace dct
@@ -303,9 +319,10 @@ long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n) {
   return (long long)dct::infer::slots_of(n).nslots * dct::infer::SLOT_WORDS * 8;
 }
 
-int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, void* stream) {
+int dct_mlp_infer(const int* dims, int L, const dct::MlpInferNormArgs* a, int grid, void* stream) {
   dct::tile::Plan tp;
-  if (!dct::tile::plan_launch(&tp, dims, L, a->p)) return (int)hipErrorInvalidValue;
+  if (!dct::mlp_norm_ok(a->norm_kind)) return (int)hipErrorInvalidValue;
+  if (!dct::tile::plan_launch(&tp, dims, L, a->p, a->norm_kind != 0)) return (int)hipErrorInvalidValue;
   if (a->n < 1 || !a->X || a->ldx < tp.D0) return (int)hipErrorInvalidValue;
   if ((a->norm_mean == nullptr) != (a->norm_std == nullptr)) return (int)hipErrorInvalidValue;
   if (a->loss_kind != 0 && a->loss_kind != 1) return (int)hipErrorInvalidValue;
@@ -320,6 +337,8 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, 
   }
   if (grid <= 0) grid = sl.nslots < 1024 ? sl.nslots : 1024;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // LayerNorm: every activation, ReLU included, on the normed instantiations
+  if (a->norm_kind) return (int)dct::infer::launch_norm(tp, *a, sl, grid, st);
   switch (a->act_kind) {
     case dct::MLP_ACT_GELU: return (int)dct::infer::launch_act<dct::MLP_ACT_GELU>(tp, *a, sl, grid, st);
     case dct::MLP_ACT_GELU_TANH: return (int)dct::infer::launch_act<dct::MLP_ACT_GELU_TANH>(tp, *a, sl, grid, st);
@@ -338,11 +357,20 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferArgs* a, int grid, 
 namespace dct {
 namespace infer {
 
-template <int ACT>
+template <int ACT, bool NORM>
 static hipError_t launch_act(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
   if (a.class_w || a.label_smooth != 0.f)
-    return tp.L == 2 ? launch<2, true, ACT>(tp, a, sl, grid, st) : launch<3, true, ACT>(tp, a, sl, grid, st);
-  return tp.L == 2 ? launch<2, false, ACT>(tp, a, sl, grid, st) : launch<3, false, ACT>(tp, a, sl, grid, st);
+    return tp.L == 2 ? launch<2, true, ACT, NORM>(tp, a, sl, grid, st) : launch<3, true, ACT, NORM>(tp, a, sl, grid, st);
+  return tp.L == 2 ? launch<2, false, ACT, NORM>(tp, a, sl, grid, st) : launch<3, false, ACT, NORM>(tp, a, sl, grid, st);
+}
+
+static hipError_t launch_norm(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
+  switch (a.act_kind) {
+    case MLP_ACT_GELU: return launch_act<MLP_ACT_GELU, true>(tp, a, sl, grid, st);
+    case MLP_ACT_GELU_TANH: return launch_act<MLP_ACT_GELU_TANH, true>(tp, a, sl, grid, st);
+    case MLP_ACT_SILU: return launch_act<MLP_ACT_SILU, true>(tp, a, sl, grid, st);
+    default: return launch_act<MLP_ACT_RELU, true>(tp, a, sl, grid, st);
+  }
 }
 
 }  // namespace infer

@@ -51,6 +51,12 @@ MlpLaunchKey mlp_launch_key(const MlpActArgs& a) {
   return k;
 }
 
+MlpLaunchKey mlp_launch_key(const MlpNormArgs& a) {
+  MlpLaunchKey k = mlp_launch_key(static_cast<const MlpActArgs&>(a));
+  k.norm = a.norm_kind;
+  return k;
+}
+
 static MlpChoice none(const char* why, bool plan_level) { return MlpChoice{MLP_NONE, false, why, plan_level}; }
 static MlpChoice take(MlpTrainer t, bool use_stage = false) { return MlpChoice{t, use_stage, nullptr, false}; }
 
@@ -73,6 +79,8 @@ MlpChoice mlp_select_trainer(const MlpShape& sh, bool use_wave, bool use_tile, c
     return none("gradient clipping needs the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.act != MLP_ACT_RELU)
     return none("GELU / tanh-GELU / SiLU need the batch-tiled trainer's plan (bmax 1024)", true);
+  if (k.norm != MLP_NORM_OFF)
+    return none("LayerNorm needs the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.weighted)
     return none("class weights / label smoothing need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.pending && !use_wave) return none("update-then-grad needs the single-wave kernel", true);

@@ -29,7 +29,9 @@
 //
 // Weights are read straight from the flat parameter buffer (L2 resident, <= 85 KB, on a 16-byte boundary: W1
 // is read as float4); activations and dZ of the tile live in LDS with the two narrow layers' weights (91.5 KB
-// for the 3-layer nets, 57.7 KB for the 2-layer ones).  No LDS-DMA loads.
+// for the 3-layer nets, 57.7 KB for the 2-layer ones; with LayerNorm one xhat image [32][132] per hidden layer and
+// 32 rstd per layer more: 125.6 KB and 74.9 KB, inside gfx950's 160 KB at one workgroup per CU, which MAX_SLOTS
+// already assumes).  No LDS-DMA loads.
 // The forward pieces (W1 fragment load, weight staging, layers 0 and 1, head logits), the shape rule (make_plan)
 // and the launch check are mlp_tile_fwd.h's, shared with the inference kernel (mlp_infer.hip); the gather, the
 // loss, the whole backward, the slots and the fold are here.
@@ -57,9 +59,9 @@ constexpr int FOLD_NT = 256;
 
 // LDS carve (floats)
 struct Lds {
-  int x0, w0, wl, a1, dz1, a2, dz2, dzl, lossr, lab, total;
+  int x0, w0, wl, a1, dz1, a2, dz2, dzl, lossr, lab, xh1, xh2, rs, total;
 };
-__host__ __device__ inline Lds lds_layout(int L) {
+__host__ __device__ inline Lds lds_layout(int L, bool norm = false) {
   Lds o;
   int off = 0;
   o.x0 = off; off += R * LDX;
@@ -72,6 +74,10 @@ __host__ __device__ inline Lds lds_layout(int L) {
   o.dzl = off; off += R * 4;
   o.lossr = off; off += R;
   o.lab = off; off += R;
+  // LayerNorm only, behind everything the plain carve has: xhat of the two hidden layers, rstd [2][32]
+  o.xh1 = off; if (norm) off += R * LDH;
+  o.xh2 = off; if (norm && L == 3) off += R * LDH;
+  o.rs = off; if (norm) off += 2 * R;
   o.total = off;
   return o;
 }
@@ -99,10 +105,21 @@ __device__ __forceinline__ float drop_apply(float z, uint32_t seed, uint32_t gst
 // Rows >= bs: their D is act'(b0 ..), finite and not zero - it is their g that is an exact zero (dlogits of a dead
 // row are 0, and so is every product and MFMA sum of them), so dZ = 0 * D = 0.  Units beyond H1 / H2 are never
 // written and never read: the widths are multiples of 16 and every loop and column block stops at them.
-template <int L, bool WL, bool ACC, int ACT = MLP_ACT_RELU>
+// NORM: nn.LayerNorm (eps 1e-5, affine) between every hidden Linear and its activation (MlpNormArgs::norm_kind, chosen
+// on the host likewise; false is the kernel as it was).  Forward, per hidden layer: the layer's epilogue stores the
+// pre-norm z + b, and behind a barrier norm_rows (mlp_tile_fwd.h, 8 lanes per row) normalises the image in place -
+// A = keep * scale * act(u), u = gamma * xhat + beta - and leaves xhat in the layer's own image XH, rstd in 32 floats
+// and D = keep * scale * act'(u) in the idle dZ image, for ReLU too (D = keep * scale * [u > 0]), so both backward
+// sites leave du = g * D in place as the smooth activations do.  Backward, behind each site's barrier (norm_backward):
+// the column sums dbeta = sum_r du, dgamma = sum_r du * xhat in ascending row order into the slot's tail words, a
+// barrier, then a row pass of the same 8 lanes: gw = du * gamma, s1 = sum gw / H, s2 = sum gw * xhat / H through the
+// xor tree, dz = rstd * (gw - s1 - xhat * s2) in place - and the dW / db code that follows reads dz as it always did.
+// Rows >= bs: the pre-norm is the bias vector, whose variance may be 0 - rstd = rsqrt(eps) and xhat = 0 are finite,
+// and g is an exact zero, so du, gw, s1, s2 and dz are exact zeros.  Every sum has a fixed order.
+template <int L, bool WL, bool ACC, int ACT = MLP_ACT_RELU, bool NORM = false>
 __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const Lds lo = lds_layout(L);
+  const Lds lo = lds_layout(L, NORM);
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int j = lane & 15, q = lane >> 4;
@@ -161,6 +178,56 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
     (LI == 0 ? dZ1 : dZ2)[r * LDH + o] = d * ks;
     return av * ks;
   };
+  // norm_rows' epilogue: the same on the normalised u, with ReLU's [u > 0] as its derivative, and xhat kept
+  float* XH1 = lds + lo.xh1;
+  float* XH2 = lds + lo.xh2;
+  float* RS = lds + lo.rs;
+  const auto norm_drop = [&](int LI, int r, int o, float u, float xhat) {
+    float d = u > 0.f ? 1.0f : 0.f, av = fmaxf(u, 0.f);
+    if constexpr (ACT != MLP_ACT_RELU) av = act_grad<ACT>(u, d);
+    const float ks = dropping ? drop_apply(1.0f, a.seed, gstep, LI, row0 + r, o, a.dropout, dscale) : 1.0f;
+    (LI == 0 ? dZ1 : dZ2)[r * LDH + o] = d * ks;
+    (LI == 0 ? XH1 : XH2)[r * LDH + o] = xhat;
+    return av * ks;
+  };
+  // LayerNorm backward of hidden layer LI with H units, whose du = g * D stands in dZ behind a barrier: the slot's
+  // dgamma / dbeta words (threads 0 .. H - 1 sum dbeta, H .. 2 H - 1 dgamma, rows ascending), then dz in place
+  const auto norm_backward = [&](int LI, int H, float* dZ, const float* XH) {
+    const int go = norm_off(tp, LI);
+    if (tid < 2 * H) {
+      const bool isg = tid >= H;
+      const int o = isg ? tid - H : tid;
+      float s = 0.f;
+      for (int r = 0; r < R; ++r) {
+        const float du = dZ[r * LDH + o];
+        s = isg ? fmaf(du, XH[r * LDH + o], s) : s + du;
+      }
+      slot[go + (isg ? 0 : H) + o] = s;
+    }
+    __syncthreads();
+    const int r = tid >> 3, part = tid & 7;
+    const float* gamma = a.p + go;
+    float* drow = dZ + r * LDH;
+    const float* xrow = XH + r * LDH;
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = part; k < H; k += 8) {
+      const float gw = drow[k] * gamma[k];
+      s1 += gw;
+      s2 = fmaf(gw, xrow[k], s2);
+    }
+    s1 += __shfl_xor(s1, 1);
+    s2 += __shfl_xor(s2, 1);
+    s1 += __shfl_xor(s1, 2);
+    s2 += __shfl_xor(s2, 2);
+    s1 += __shfl_xor(s1, 4);
+    s2 += __shfl_xor(s2, 4);
+    const float invH = 1.0f / (float)H;
+    s1 *= invH;
+    s2 *= invH;
+    const float rstd = RS[LI * R + r];
+    for (int k = part; k < H; k += 8) drow[k] = rstd * (drow[k] * gamma[k] - s1 - xrow[k] * s2);
+    __syncthreads();
+  };
 
   // ---- this wave's W1 fragments of the forward MFMA: issued first, so their L2 round trips overlap the
   // gather and layer 0 instead of chaining inside the k loop
@@ -183,7 +250,12 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
   __syncthreads();
 
   // ---- layer 0: A1 = dropout(relu(X0 W0^T + b0))
-  if constexpr (ACT == MLP_ACT_RELU) layer0(A1, W0s, X0, D0, H1, tid, drop);
+  if constexpr (NORM) {  // A1 = z + b0, then normalised in place: A1 = keep scale act(u), dZ1 = D, XH1 = xhat
+    layer0<1>(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
+    __syncthreads();
+    const int go = norm_off(tp, 0);
+    norm_rows(A1, RS, a.p + go, a.p + go + H1, H1, 0, tid, norm_drop);
+  } else if constexpr (ACT == MLP_ACT_RELU) layer0(A1, W0s, X0, D0, H1, tid, drop);
   else layer0<ACT>(A1, W0s, X0, D0, H1, tid, act_drop);  // A1 = keep scale act(z), dZ1 = D
   __syncthreads();
 
@@ -193,10 +265,16 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
     for (int c = 0; c < 2; ++c) {
       const int cb = wave + 4 * c;
       if (cb * 16 >= H2) break;
-      if constexpr (ACT == MLP_ACT_RELU) layer1_block(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, drop);
+      if constexpr (NORM) layer1_block<1>(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, NoEpilogue{});
+      else if constexpr (ACT == MLP_ACT_RELU) layer1_block(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, drop);
       else layer1_block<ACT>(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, act_drop);  // dZ2 = D
     }
     __syncthreads();
+    if constexpr (NORM) {  // A2 = z + b1 normalised in place, dZ2 = D, XH2 = xhat
+      const int go = norm_off(tp, 1);
+      norm_rows(A2, RS + R, a.p + go, a.p + go + H2, H2, 1, tid, norm_drop);
+      __syncthreads();
+    }
   }
 
   // ---- W1 fragments of the dZ1 MFMA (k = the H2 outputs), in flight across the head phases
@@ -249,7 +327,7 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
 #pragma unroll
     for (int c = 0; c < 4; ++c)
       if (c < C) g = fmaf(dZL[r * 4 + c], Wl[c * K + k], g);
-    if constexpr (ACT == MLP_ACT_RELU) {
+    if constexpr (ACT == MLP_ACT_RELU && !NORM) {
       const float av = Ah[r * LDH + k];
       dZh[r * LDH + k] = (av > 0.f) ? g * dscale : 0.f;
     } else {
@@ -278,6 +356,8 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
     }
   }
   __syncthreads();
+  // ---- LayerNorm backward of the last hidden layer: du -> dgamma, dbeta, dz
+  if constexpr (NORM) norm_backward(L - 2, K, dZh, (L == 3) ? XH2 : XH1);
 
   if (L == 3) {
     // ---- dZ1 = mask(A1) * (dZ2 W1) on the MFMA: k runs over the H2 outputs
@@ -307,7 +387,7 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r0 = 4 * q + i, r1 = r0 + 16;
-        if constexpr (ACT == MLP_ACT_RELU) {
+        if constexpr (ACT == MLP_ACT_RELU && !NORM) {
           dZ1[r0 * LDH + ic] = (A1[r0 * LDH + ic] > 0.f) ? acc0[i] * dscale : 0.f;
           dZ1[r1 * LDH + ic] = (A1[r1 * LDH + ic] > 0.f) ? acc1[i] * dscale : 0.f;
         } else {
@@ -336,6 +416,8 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
       slot[tp.boff[1] + tid] = g;
     }
     __syncthreads();
+    // ---- LayerNorm backward of layer 0
+    if constexpr (NORM) norm_backward(0, H1, dZ1, XH1);
   }
 
   // ---- dW0 = dZ1^T X0, db0 (VALU)
@@ -678,13 +760,13 @@ static void launch_fold_clipped(int grid, const Plan& tp, const MlpClipArgs& a, 
 }
 
 // CLIPPED: a train-mode launch with a clip kind set - the same step kernel, launch_fold_clipped behind it
-// ACT: the step kernel's activation; the folds behind it do not know it
-template <int L, bool WL, bool ACC, bool CLIPPED = false, int ACT = MLP_ACT_RELU>
+// ACT, NORM: the step kernel's activation and LayerNorm; the folds behind it know neither (tp.P counts the norm's words)
+template <int L, bool WL, bool ACC, bool CLIPPED = false, int ACT = MLP_ACT_RELU, bool NORM = false>
 static hipError_t launch_steps(const Plan& tp, const std::conditional_t<CLIPPED, MlpClipArgs, MlpArgs>& a0,
                                unsigned int* done, hipStream_t st) {
   const int T = (a0.B + R - 1) / R;
-  const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
-  auto fn = mlp_tile_step_kernel<L, WL, ACC, ACT>;
+  const size_t bytes = (size_t)lds_layout(L, NORM).total * sizeof(float);
+  auto fn = mlp_tile_step_kernel<L, WL, ACC, ACT, NORM>;
   const int AK = ACC ? a0.accum : 1;  // micro-batches per optimizer step: the index list advances by AK * B rows
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
@@ -710,6 +792,9 @@ static hipError_t train_clipped(const Plan& tp, const MlpClipArgs& a, int L, boo
 // the smooth activations' dispatch (likewise behind it, and behind the clipped ones)
 static hipError_t train_act(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
                             hipStream_t st);
+// the normed models' dispatch (behind all of them)
+static hipError_t train_norm(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                             hipStream_t st);
 
 }  // namespace tile
 
@@ -769,9 +854,29 @@ long long dct_mlp_tile_clip_ws_floats(const int* dims, int L) {
   return dct::tile::make_plan(&tp, dims, L) ? dct::tile::clip_ws_layout(tp).total : 0;
 }
 
-int dct_mlp_tile_train(const int* dims, int L, const dct::MlpActArgs* a, void* stream) {
+long long dct_mlp_tile_ws_floats_norm(const int* dims, int L, int B, int accum, int norm) {
+  if (!norm) return dct_mlp_tile_ws_floats_accum(dims, L, B, accum);
   dct::tile::Plan tp;
-  if (!dct::tile::plan_launch(&tp, dims, L, a->p)) return (int)hipErrorInvalidValue;
+  if (!dct::tile::make_plan(&tp, dims, L, true) || !dct::mlp_tile_window_ok(B, accum)) return 0;
+  const long long T = (B + dct::tile::R - 1) / dct::tile::R;
+  return (accum > 1 ? accum : 1) * T * tp.Pp + 4;
+}
+
+long long dct_mlp_tile_clip_ws_floats_norm(const int* dims, int L, int norm) {
+  dct::tile::Plan tp;
+  return dct::tile::make_plan(&tp, dims, L, norm != 0) ? dct::tile::clip_ws_layout(tp).total : 0;
+}
+
+long long dct_mlp_tile_num_params(const int* dims, int L, int norm) {
+  dct::tile::Plan tp;
+  return dct::tile::make_plan(&tp, dims, L, norm != 0) ? tp.P : 0;
+}
+
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpNormArgs* a, void* stream) {
+  dct::tile::Plan tp;
+  if (!dct::mlp_norm_ok(a->norm_kind)) return (int)hipErrorInvalidValue;
+  const int norm = a->norm_kind;
+  if (!dct::tile::plan_launch(&tp, dims, L, a->p, norm != 0)) return (int)hipErrorInvalidValue;
   if (!dct::mlp_act_ok(a->act_kind)) return (int)hipErrorInvalidValue;
   if (a->B < 1 || a->B > dct::tile::BMAX || a->steps < 1 || a->n_items < 1) return (int)hipErrorInvalidValue;
   if (a->mode == 1 && a->steps != 1) return (int)hipErrorInvalidValue;
@@ -782,7 +887,7 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpActArgs* a, void* s
   if (!dct::mlp_tile_optimizer_ok(*a)) return (int)hipErrorInvalidValue;
   if (!(a->label_smooth >= 0.f && a->label_smooth < 1.f)) return (int)hipErrorInvalidValue;
   if ((a->class_w || a->label_smooth != 0.f) && a->loss_kind != 0) return (int)hipErrorInvalidValue;  // CE only
-  if (!a->tile_ws || a->tile_ws_floats < dct_mlp_tile_ws_floats_accum(dims, L, a->B, accum))
+  if (!a->tile_ws || a->tile_ws_floats < dct_mlp_tile_ws_floats_norm(dims, L, a->B, accum, norm))
     return (int)hipErrorInvalidValue;
   unsigned int* done = reinterpret_cast<unsigned int*>(a->tile_ws + (a->tile_ws_floats - 4));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -790,8 +895,10 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpActArgs* a, void* s
   if (!dct::mlp_tile_clip_ok(*a)) return (int)hipErrorInvalidValue;
   const bool clipped = a->mode == 0 && a->clip_kind != dct::MLP_CLIP_OFF;
   if (clipped && a->clip_kind == dct::MLP_CLIP_NORM &&
-      (!a->clip_ws || ((uintptr_t)a->clip_ws & 15) || a->clip_ws_floats < dct_mlp_tile_clip_ws_floats(dims, L)))
+      (!a->clip_ws || ((uintptr_t)a->clip_ws & 15) || a->clip_ws_floats < dct_mlp_tile_clip_ws_floats_norm(dims, L, norm)))
     return (int)hipErrorInvalidValue;
+  // LayerNorm: its own step-kernel instantiations for every activation, in train and grad mode alike
+  if (norm) return (int)dct::tile::train_norm(tp, *a, L, wl, accum > 1, done, st);
   // a smooth activation: its own step-kernel instantiations in train and grad mode alike, every fold as it is
   if (a->act_kind != dct::MLP_ACT_RELU) return (int)dct::tile::train_act(tp, *a, L, wl, accum > 1, done, st);
   if (clipped) {
@@ -833,28 +940,28 @@ static hipError_t train_clipped(const Plan& tp, const MlpClipArgs& a, int L, boo
                 : launch_steps<3, false, true, true>(tp, a, done, st);
 }
 
-template <int ACT, bool CLIPPED>
+template <int ACT, bool CLIPPED, bool NORM = false>
 static hipError_t train_act_steps(const Plan& tp, const MlpClipArgs& a, int L, bool wl, bool acc, unsigned int* done,
                                   hipStream_t st) {
   if (!acc) {
     if (wl)
-      return L == 2 ? launch_steps<2, true, false, CLIPPED, ACT>(tp, a, done, st)
-                    : launch_steps<3, true, false, CLIPPED, ACT>(tp, a, done, st);
-    return L == 2 ? launch_steps<2, false, false, CLIPPED, ACT>(tp, a, done, st)
-                  : launch_steps<3, false, false, CLIPPED, ACT>(tp, a, done, st);
+      return L == 2 ? launch_steps<2, true, false, CLIPPED, ACT, NORM>(tp, a, done, st)
+                    : launch_steps<3, true, false, CLIPPED, ACT, NORM>(tp, a, done, st);
+    return L == 2 ? launch_steps<2, false, false, CLIPPED, ACT, NORM>(tp, a, done, st)
+                  : launch_steps<3, false, false, CLIPPED, ACT, NORM>(tp, a, done, st);
   }
   if (wl)
-    return L == 2 ? launch_steps<2, true, true, CLIPPED, ACT>(tp, a, done, st)
-                  : launch_steps<3, true, true, CLIPPED, ACT>(tp, a, done, st);
-  return L == 2 ? launch_steps<2, false, true, CLIPPED, ACT>(tp, a, done, st)
-                : launch_steps<3, false, true, CLIPPED, ACT>(tp, a, done, st);
+    return L == 2 ? launch_steps<2, true, true, CLIPPED, ACT, NORM>(tp, a, done, st)
+                  : launch_steps<3, true, true, CLIPPED, ACT, NORM>(tp, a, done, st);
+  return L == 2 ? launch_steps<2, false, true, CLIPPED, ACT, NORM>(tp, a, done, st)
+                : launch_steps<3, false, true, CLIPPED, ACT, NORM>(tp, a, done, st);
 }
 
-template <int ACT>
+template <int ACT, bool NORM = false>
 static hipError_t train_act_kind(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
                                  hipStream_t st) {
-  if (a.mode == 0 && a.clip_kind != MLP_CLIP_OFF) return train_act_steps<ACT, true>(tp, a, L, wl, acc, done, st);
-  return train_act_steps<ACT, false>(tp, a, L, wl, acc, done, st);
+  if (a.mode == 0 && a.clip_kind != MLP_CLIP_OFF) return train_act_steps<ACT, true, NORM>(tp, a, L, wl, acc, done, st);
+  return train_act_steps<ACT, false, NORM>(tp, a, L, wl, acc, done, st);
 }
 
 static hipError_t train_act(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
@@ -863,6 +970,17 @@ static hipError_t train_act(const Plan& tp, const MlpActArgs& a, int L, bool wl,
     case MLP_ACT_GELU: return train_act_kind<MLP_ACT_GELU>(tp, a, L, wl, acc, done, st);
     case MLP_ACT_GELU_TANH: return train_act_kind<MLP_ACT_GELU_TANH>(tp, a, L, wl, acc, done, st);
     case MLP_ACT_SILU: return train_act_kind<MLP_ACT_SILU>(tp, a, L, wl, acc, done, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+static hipError_t train_norm(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                             hipStream_t st) {
+  switch (a.act_kind) {
+    case MLP_ACT_RELU: return train_act_kind<MLP_ACT_RELU, true>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_GELU: return train_act_kind<MLP_ACT_GELU, true>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_GELU_TANH: return train_act_kind<MLP_ACT_GELU_TANH, true>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_SILU: return train_act_kind<MLP_ACT_SILU, true>(tp, a, L, wl, acc, done, st);
     default: return hipErrorInvalidValue;
   }
 }

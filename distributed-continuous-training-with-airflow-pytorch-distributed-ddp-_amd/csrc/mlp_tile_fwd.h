@@ -4,7 +4,9 @@
 // layer 1 on v_mfma_f32_16x16x4_f32 (exact fp32), head logits.  The gather, the loss and the LDS carve stay with
 // each kernel.  Layers 0 and 1 hand every post-ReLU value to an epilogue epi(layer, row in the tile, unit, z):
 // the trainer's dropout, the inference kernel's identity.  With a smooth activation (GELU, tanh-GELU, SiLU) they hand
-// over the pre-activation instead and the epilogue applies act_grad / ActEpilogue below.
+// over the pre-activation instead and the epilogue applies act_grad / ActEpilogue below.  With LayerNorm (make_plan's
+// norm) the layers store the pre-norm z + b through NoEpilogue and norm_rows normalises the image in place, handing
+// u = gamma * xhat + beta and xhat to its own epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,9 +28,14 @@ struct Plan {
   int woff[3], boff[3];  // torch flat offsets (layer 2 unused when L == 2; the head is layer L - 1)
   int P, Pp;    // parameters, slot stride of the trainer's workspace (floats)
 };
+// With LayerNorm the flat buffer carries gamma_1 [H1], beta_1 [H1] (, gamma_2 [H2], beta_2 [H2]) behind the head's bias:
+// P and Pp count them, woff / boff do not move, and the tail needs no field of its own.
+__host__ __device__ inline int norm_off(const Plan& tp, int layer) {  // gamma of hidden layer 0 / 1; beta = + H
+  return tp.boff[tp.L - 1] + tp.C + (layer == 0 ? 0 : 2 * tp.H1);
+}
 
 // Shapes: 2 or 3 linear layers, D0 1..32, hidden widths multiples of 16 in 16..128, C 2..4.
-static inline bool make_plan(Plan* tp, const int* dims, int L) {
+static inline bool make_plan(Plan* tp, const int* dims, int L, bool norm = false) {
   if (L != 2 && L != 3) return false;
   const int D0 = dims[0], C = dims[L];
   if (D0 < 1 || D0 > 32 || C < 2 || C > 4) return false;
@@ -48,6 +55,7 @@ static inline bool make_plan(Plan* tp, const int* dims, int L) {
     tp->boff[l] = flat;
     flat += dims[l + 1];
   }
+  if (norm) flat += 2 * (tp->H1 + tp->H2);
   tp->P = flat;
   tp->Pp = (flat + 2 + 3) & ~3;  // [P] gradients, the loss sum, the weighted loss's sum of w[y]
   return true;
@@ -55,8 +63,8 @@ static inline bool make_plan(Plan* tp, const int* dims, int L) {
 
 // What both launchers ask before anything else: a shape make_plan takes, and parameters on a 16-byte boundary -
 // load_w1_frags reads W1 as float4 (woff[1] = (D0 + 1) * H1 floats keeps the alignment of p).
-static inline bool plan_launch(Plan* tp, const int* dims, int L, const float* p) {
-  return make_plan(tp, dims, L) && p && reinterpret_cast<uintptr_t>(p) % 16 == 0;
+static inline bool plan_launch(Plan* tp, const int* dims, int L, const float* p, bool norm = false) {
+  return make_plan(tp, dims, L, norm) && p && reinterpret_cast<uintptr_t>(p) % 16 == 0;
 }
 
 struct NoEpilogue {
@@ -177,6 +185,55 @@ __device__ __forceinline__ void layer1_block(float* A2, const float* A1, const f
     A2[r1 * LDH + o] = epi(1, r1, o, ACT == 0 ? fmaxf(acc1[i] + bv, 0.f) : acc1[i] + bv);
   }
 }
+
+// LayerNorm of one hidden layer's image (VALU, 8 lanes per row in head_logits' thread-to-row mapping; the caller's
+// barriers stand before and behind it): A [32][LDH] holds the pre-norm z + b of the layer's H units.  Lane `part` of
+// row r strides units part, part + 8, ..: the mean first, then the centred sum of squares (two passes, as torch), each
+// closed by the 3-step xor tree, so all 8 lanes hold the same bits of mean and rstd = rsqrt(biased var + eps).  The
+// same lanes then sweep the row once more, xhat = (z - mean) rstd, u = gamma xhat + beta, and store
+// A = epi(LI, r, unit, u, xhat): the activation (and what the trainer keeps for its backward).  gamma / beta: the flat
+// buffer (L2 resident).  rs (may be null): rstd of the 32 rows.  A row of equal values has var = 0 and rstd =
+// rsqrt(eps), finite.  Every element is read and written by one thread only.
+template <class Epi>
+__device__ __forceinline__ void norm_rows(float* A, float* rs, const float* gamma, const float* beta, int H, int LI,
+                                          int tid, Epi epi) {
+  const int r = tid >> 3, part = tid & 7;
+  float* row = A + r * LDH;
+  const float invH = 1.0f / (float)H;
+  float s = 0.f;
+  for (int k = part; k < H; k += 8) s += row[k];
+  s += __shfl_xor(s, 1);
+  s += __shfl_xor(s, 2);
+  s += __shfl_xor(s, 4);
+  const float mean = s * invH;
+  float v = 0.f;
+  for (int k = part; k < H; k += 8) {
+    const float d = row[k] - mean;
+    v = fmaf(d, d, v);
+  }
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 4);
+  const float rstd = rsqrtf(fmaf(v, invH, 1e-5f));
+  if (rs && part == 0) rs[r] = rstd;
+  for (int k = part; k < H; k += 8) {
+    const float xhat = (row[k] - mean) * rstd;
+    row[k] = epi(LI, r, k, fmaf(gamma[k], xhat, beta[k]), xhat);
+  }
+}
+
+// the inference kernel's epilogue of norm_rows: act(u) alone (ACT = 0: ReLU)
+template <int ACT>
+struct NormActEpilogue {
+  __device__ __forceinline__ float operator()(int, int, int, float u, float) const {
+    if constexpr (ACT == 0) {
+      return fmaxf(u, 0.f);
+    } else {
+      float d;
+      return act_grad<ACT>(u, d);
+    }
+  }
+};
 
 // Head (VALU, 8 lanes per row): z = the logits of row tid >> 3 (0 beyond C), in all 8 lanes after the xor tree.
 __device__ __forceinline__ void head_logits(float (&z)[4], const float* Ah, const float* Wl, int C, int K, int tid) {

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.fused_mlp import check_activation, check_class_weight, check_label_smoothing, check_optimizer
+from ..ops.fused_mlp import check_activation, check_class_weight, check_norm, check_label_smoothing, check_optimizer
 from ..trainer.module import TrainModule
 
 # configure_optimizers()'s options and their defaults, which reproduce the reference's Adam(lr): a model records only
@@ -40,9 +40,14 @@ class MLPClassifier(TrainModule):
                  loss: str = "ce", lr: float = 0.01, class_weight: Optional[Sequence[float]] = None,
                  label_smoothing: float = 0.0, optimizer: str = "adam", weight_decay: float = 0.0,
                  momentum: float = 0.0, nesterov: bool = False, betas: Sequence[float] = (0.9, 0.999),
-                 eps: float = 1e-8, dampening: float = 0.0, activation: str = "relu"):
+                 eps: float = 1e-8, dampening: float = 0.0, activation: str = "relu", norm: Optional[str] = None):
         super().__init__()
         self.save_hyperparameters()
+        # a normalisation layer between every hidden Linear and its activation (None, or "layer": nn.LayerNorm(H, eps=1e-5)
+        # with its affine gamma / beta): recorded only when set
+        self.norm = check_norm(norm)
+        if self.norm is None:
+            self.hparams.pop("norm", None)
         # the hidden layers' activation (every hidden layer the same, the head linear): recorded only when it is not
         # the ReLU a model always had
         self.activation = check_activation(activation)
@@ -85,13 +90,26 @@ class MLPClassifier(TrainModule):
             if i < len(dims) - 2:
                 layers += [activation_module(self.activation), nn.Dropout(dropout)]  # (same slot: net.<3i> keys)
         self.net = nn.Sequential(*layers)
+        # the norms live in a list of their own, registered after net: the net.<3i> keys are a contract with score.py and
+        # existing checkpoints, and parameters() order is all linears, then gamma_1, beta_1 (, gamma_2, beta_2) - the
+        # flat order of the fused kernels.  Without a norm the module has no such attribute's keys at all.
+        if self.norm is not None:
+            self.norms = nn.ModuleList(nn.LayerNorm(h, eps=1e-5) for h in dims[1:-1])
         self.dims = dims
         self.dropout_p = float(dropout)
         self.loss_kind = loss
         self.lr = lr
 
     def forward(self, x):
-        return self.net(x)
+        if self.norm is None:
+            return self.net(x)
+        i = 0
+        for m in self.net:  # Linear -> LayerNorm -> activation -> Dropout in every hidden layer, the head plain
+            x = m(x)
+            if isinstance(m, nn.Linear) and i < len(self.norms):
+                x = self.norms[i](x)
+                i += 1
+        return x
 
     def compute_loss(self, logits, y):
         if self.loss_kind == "ce":
@@ -140,19 +158,27 @@ class MLPClassifier(TrainModule):
             spec["label_smoothing"] = self.label_smoothing
         if self.activation != "relu":
             spec["activation"] = self.activation
+        if self.norm is not None:
+            spec["norm"] = self.norm
         return spec
 
     def linear_layers(self) -> List[nn.Linear]:
         return [m for m in self.net if isinstance(m, nn.Linear)]
+
+    def norm_layers(self) -> List[nn.LayerNorm]:
+        """The hidden layers' norms in layer order ([] without one): their weight / bias follow all linears in
+        parameters() and in the fused kernels' flat buffer."""
+        return list(self.norms) if self.norm is not None else []
 
 
 class WeatherClassifier(MLPClassifier):
     """Reference model: Linear(D,64)-ReLU-Dropout(0.2)-Linear(64,2), CE, Adam(lr=0.01)."""
 
     def __init__(self, input_dim: int, class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0,
-                 activation: str = "relu", **optim):
+                 activation: str = "relu", norm: Optional[str] = None, **optim):
         super().__init__(input_dim=input_dim, hidden=(64,), num_classes=2, dropout=0.2, loss="ce", lr=0.01,
-                         class_weight=class_weight, label_smoothing=label_smoothing, activation=activation, **optim)
+                         class_weight=class_weight, label_smoothing=label_smoothing, activation=activation, norm=norm,
+                         **optim)
         # the reference records exactly {"input_dim": D} (save_hyperparameters at :53); the loss and optimizer options
         # join it only when set
         hp = {"input_dim": int(input_dim)}
@@ -163,17 +189,19 @@ class WeatherClassifier(MLPClassifier):
             hp["label_smoothing"] = self.label_smoothing
         if self.activation != "relu":
             hp["activation"] = self.activation
+        if self.norm is not None:
+            hp["norm"] = self.norm
         self._set_hparams(hp)
 
 
 def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None, num_classes: int = 2,
               dropout: float = 0.2, loss: str = "ce", lr: float = 0.01,
               class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0,
-              activation: str = "relu", **optim) -> MLPClassifier:
+              activation: str = "relu", norm: Optional[str] = None, **optim) -> MLPClassifier:
     """``optim``: MLPClassifier's optimizer options (OPTIM_DEFAULTS' keys)."""
     if name == "weather":
         return WeatherClassifier(input_dim, class_weight=class_weight, label_smoothing=label_smoothing,
-                                 activation=activation, **optim)
+                                 activation=activation, norm=norm, **optim)
     # name -> (hidden widths, dropout, loss, lr); BASELINE.json configs 1-4
     presets = {
         "weather-mlp-3x128": ((128, 128), 0.2, "ce", 0.01),
@@ -182,4 +210,5 @@ def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None,
     if name in presets and hidden is None:
         hidden, dropout, loss, lr = presets[name]
     return MLPClassifier(input_dim, hidden=hidden or (64,), num_classes=num_classes, dropout=dropout, loss=loss, lr=lr,
-                         class_weight=class_weight, label_smoothing=label_smoothing, activation=activation, **optim)
+                         class_weight=class_weight, label_smoothing=label_smoothing, activation=activation, norm=norm,
+                         **optim)

@@ -23,8 +23,10 @@ CLIP_KINDS = {"norm": 1, "value": 2}  # csrc/mlp_fused.h MlpClip
 XG_POLL = 3
 
 
-def mlp_num_params(dims: Sequence[int]) -> int:
-    return sum(dims[i] * dims[i + 1] + dims[i + 1] for i in range(len(dims) - 1))
+def mlp_num_params(dims: Sequence[int], norm=None) -> int:
+    """Flat parameters of the MLP: all linears, then (``norm="layer"``) gamma and beta of every hidden layer."""
+    n = sum(dims[i] * dims[i + 1] + dims[i + 1] for i in range(len(dims) - 1))
+    return n + (2 * sum(dims[1:-1]) if check_norm(norm) is not None else 0)
 
 
 TILE_BMAX = 1024  # largest per-rank batch of the batch-tiled trainer (csrc/mlp_tile.hip)
@@ -85,6 +87,17 @@ def check_activation(activation) -> str:
     if activation not in ACTIVATIONS:
         raise ValueError(f"activation must be one of {ACTIVATIONS}, got {activation!r}")
     return activation
+
+
+NORMS = (None, "layer")  # csrc/mlp_fused.h MlpNorm
+
+
+def check_norm(norm) -> Optional[str]:
+    """The hidden layers' normalisation of a model or a launch: ``None``, or ``"layer"`` - ``nn.LayerNorm(H, eps=1e-5)``
+    with its affine parameters between every hidden Linear and its activation; ValueError for anything else."""
+    if norm not in NORMS:
+        raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
+    return norm
 
 
 def activation_fn(activation):
@@ -231,7 +244,7 @@ class FusedMLPKernel:
         self._infer_ws_buf = None  # slot workspace of the inference kernel's statistics (csrc/mlp_infer.hip)
         self._clip_ws = None  # norm clipping: folded gradient, partial sums and {norm, coef} (csrc/mlp_tile.hip)
 
-    def _tile_args(self, device, batch: int = 0, accumulate: int = 1) -> dict:
+    def _tile_args(self, device, batch: int = 0, accumulate: int = 1, norm=None) -> dict:
         """The batch-tiled trainer's slot workspace (partial gradients per tile + the fold's arrival
         counter, zero between launches), allocated once for batches up to ``bmax``; a launch whose accumulation
         window needs more slots than that gets a larger one (launches bound earlier keep theirs alive)."""
@@ -240,6 +253,9 @@ class FusedMLPKernel:
         n = int(native().mlp_tile_ws_floats(self.dims, max(self.bmax, 16)))
         if accumulate > 1:
             n = max(n, int(native().mlp_tile_ws_floats_accum(self.dims, int(batch), int(accumulate))))
+        if norm is not None:  # (the slots of a normed model are longer by its gamma / beta words)
+            n = max(int(native().mlp_tile_ws_floats_norm(self.dims, max(self.bmax, 16), 1, norm)),
+                    int(native().mlp_tile_ws_floats_norm(self.dims, int(batch), int(accumulate), norm)))
         if self._tile_ws is None or self._tile_ws.device != device or self._tile_ws.numel() < n:
             self._tile_ws = torch.zeros(n, dtype=torch.float32, device=device)
         return dict(tile_ws=ptr(self._tile_ws), tile_ws_floats=self._tile_ws.numel())
@@ -273,7 +289,16 @@ class FusedMLPKernel:
                              "(any batch 1..1024) for an architecture it takes")
         return dict(activation=activation)
 
-    def _check_clip(self, clip_val, clip_algorithm: str, batch: int, device, train: bool) -> dict:
+    def _check_norm(self, norm, batch: int) -> dict:
+        """The native argument of a launch of a model with LayerNorm ({} without), in train and in grad mode alike."""
+        if check_norm(norm) is None:
+            return {}
+        if self.plan.trainer(int(batch), norm=norm) != "tile":
+            raise ValueError(f"norm={norm!r} needs the batch-tiled trainer: a plan of bmax 1024 "
+                             "(any batch 1..1024) for an architecture it takes")
+        return dict(norm=norm)
+
+    def _check_clip(self, clip_val, clip_algorithm: str, batch: int, device, train: bool, norm=None) -> dict:
         """The native arguments of a launch that clips its gradient ({} when off, and for a grad-mode launch, which
         ignores clipping).  By norm the launch gets this kernel's workspace, allocated once (launches bound earlier
         keep it alive; a captured launch sequence needs its address fixed)."""
@@ -287,8 +312,8 @@ class FusedMLPKernel:
                              "(any batch 1..1024) for an architecture it takes")
         args = dict(clip_kind=CLIP_KINDS[clip_algorithm], clip_val=clip_val)
         if clip_algorithm == "norm":
-            if self._clip_ws is None or self._clip_ws.device != device:
-                n = int(native().mlp_tile_clip_ws_floats(self.dims))
+            n = int(native().mlp_tile_clip_ws_floats_norm(self.dims, norm or ""))
+            if self._clip_ws is None or self._clip_ws.device != device or self._clip_ws.numel() != n:
                 self._clip_ws = torch.zeros(n, dtype=torch.float32, device=device)
                 self._clip_ws[n - 4: n - 2] = torch.tensor([float("nan"), 1.0])  # (no norm computed yet)
             args.update(clip_ws=ptr(self._clip_ws), clip_ws_floats=self._clip_ws.numel())
@@ -357,8 +382,8 @@ class FusedMLPKernel:
         return bool(native().mlp_supported([int(d) for d in dims], int(batch)))
 
     # ------------------------------------------------------------------ checks
-    def _check_params(self, *ts):
-        P = mlp_num_params(self.dims)
+    def _check_params(self, *ts, norm=None):
+        P = mlp_num_params(self.dims, norm)
         for t in ts:
             if t is None:
                 continue
@@ -409,8 +434,14 @@ class FusedMLPKernel:
               lr_tab: Optional[torch.Tensor] = None, class_weight: Optional[torch.Tensor] = None,
               label_smoothing: float = 0.0, accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0,
               dampening: float = 0.0, nesterov: bool = False, clip_val: Optional[float] = None,
-              clip_algorithm: str = "norm", activation: str = "relu"):
+              clip_algorithm: str = "norm", activation: str = "relu", norm: Optional[str] = None):
         """Run ``steps`` fused optimizer steps (mode 0) or one gradient step (grad_out given).
+
+        ``norm``: ``None``, or on the batch-tiled trainer's plan ``"layer"`` - ``nn.LayerNorm(H, eps=1e-5)`` with affine
+        parameters between every hidden Linear and its activation.  ``p`` (and ``m``, ``v``, ``grad_out``) then carry
+        ``gamma_1, beta_1[, gamma_2, beta_2]`` behind all linears (``mlp_num_params(dims, norm)`` words, torch's
+        ``parameters()`` order); the optimizer and its weight decay treat them like every other word.  Part of the
+        model: a grad-mode launch honours it too.
 
         ``activation``: the hidden layers' ``"relu"``, or on the batch-tiled trainer's plan ``"gelu"``, ``"gelu_tanh"``
         or ``"silu"`` (every hidden layer the same, the head linear).  It is part of the model: a grad-mode launch
@@ -451,7 +482,7 @@ class FusedMLPKernel:
         opt_args = self._check_optimizer(optimizer, batch, weight_decay, momentum, dampening, nesterov, mode == 0)
         if need_mv:
             m, v = self._moments_of(opt_args, m, v)
-        self._check_params(p, m if need_mv else None, v if need_mv else None)
+        self._check_params(p, m if need_mv else None, v if need_mv else None, norm=norm)
         if pending is not None and not (pending.is_cuda and pending.dtype == torch.int32):
             raise ValueError("pending must be a cuda int32 flag")
         self._check_data(X, Y, idx, n_items)
@@ -459,14 +490,15 @@ class FusedMLPKernel:
             raise ValueError(f"batch {batch} > kernel bmax {self.bmax}")
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
-        clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, mode == 0)
+        norm_args = self._check_norm(norm, batch)
+        clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, mode == 0, norm)
         act_args = self._check_activation(activation, batch)
         if steps < 1 or (cursor is None and (steps - 1) * batch * accumulate >= n_items):
             raise ValueError("steps do not match the index list")
         if cursor is not None and (mode != 1 or not (cursor.is_cuda and cursor.dtype == torch.int32)):
             raise ValueError("cursor (cuda int32) is only valid with grad_out")
         if mode == 1:
-            P = mlp_num_params(self.dims)
+            P = mlp_num_params(self.dims, norm)
             if not (grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.numel() >= P + 1):
                 raise ValueError("grad_out must be cuda fp32 with P+1 entries (grads + loss)")
         if stage is not None and not (stage.is_cuda and stage.dtype == torch.int32 and stage.numel() >= 64 * 3):
@@ -493,8 +525,8 @@ class FusedMLPKernel:
             int(seed) & 0xFFFFFFFF, int(step_base) & 0xFFFFFFFF, ptr(loss_out), mode, LOSS_KINDS[loss],
             ptr(step_counter), ptr(cursor), ptr(prof), ptr(pending), ptr(stage),
             stream if stream is not None else stream_handle(),
-            **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab), **wl_args,
-            **acc_args, **opt_args, **clip_args, **act_args,
+            **xg_args, **self._tile_args(p.device, batch, accumulate, norm), lr_tab=_table_ptr(lr_tab), **wl_args,
+            **acc_args, **opt_args, **clip_args, **act_args, **norm_args,
         )
 
     def prepare_train(self, p, m, v, X, Y, idx, n_items: int, batch: int, lr: float, betas=(0.9, 0.999),
@@ -505,7 +537,8 @@ class FusedMLPKernel:
                       class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
                       accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0, dampening: float = 0.0,
                       nesterov: bool = False, clip_val: Optional[float] = None,
-                      clip_algorithm: str = "norm", activation: str = "relu") -> "BoundTrain":
+                      clip_algorithm: str = "norm", activation: str = "relu",
+                      norm: Optional[str] = None) -> "BoundTrain":
         """Validate the operands of persistent train-mode launches ONCE and bind them natively.
 
         ``BoundTrain.run(first_step, steps)`` then launches steps [first_step, first_step+steps)
@@ -513,16 +546,17 @@ class FusedMLPKernel:
         positional native call (no keyword parsing, no tensor checks), which is what the short
         timed windows of the benchmark contract see.  ``accumulate`` as in ``train``: the steps are
         optimizer steps of ``accumulate`` micro-batches each.  ``optimizer`` / ``momentum`` / ``dampening`` /
-        ``nesterov``, ``clip_val`` / ``clip_algorithm`` and ``activation`` as in ``train``."""
+        ``nesterov``, ``clip_val`` / ``clip_algorithm``, ``activation`` and ``norm`` as in ``train``."""
         if not 1 <= batch <= self.bmax:
             raise ValueError(f"batch {batch} outside 1..{self.bmax}")
         opt_args = self._check_optimizer(optimizer, batch, weight_decay, momentum, dampening, nesterov, True)
         m, v = self._moments_of(opt_args, m, v)
-        self._check_params(p, m, v)
+        self._check_params(p, m, v, norm=norm)
         self._check_data(X, Y, idx, n_items)
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
-        clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, True)
+        norm_args = self._check_norm(norm, batch)
+        clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, True, norm)
         act_args = self._check_activation(activation, batch)
         if step_counter is None or not (step_counter.is_cuda and step_counter.dtype == torch.int32):
             raise ValueError("step_counter must be a cuda int32 scalar tensor (launches are step-relative)")
@@ -547,8 +581,8 @@ class FusedMLPKernel:
             ptr(p), ptr(m), ptr(v), ptr(X), X.stride(0), ptr(Y), ptr(idx), int(n_items), int(batch), float(lr),
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(dropout),
             int(seed) & 0xFFFFFFFF, ptr(loss_out), 0 if loss_out is None else loss_out.numel(), LOSS_KINDS[loss],
-            ptr(step_counter), **xg_args, **self._tile_args(p.device, batch, accumulate), lr_tab=_table_ptr(lr_tab),
-            **wl_args, **acc_args, **opt_args, **clip_args, **act_args)
+            ptr(step_counter), **xg_args, **self._tile_args(p.device, batch, accumulate, norm),
+            lr_tab=_table_ptr(lr_tab), **wl_args, **acc_args, **opt_args, **clip_args, **act_args, **norm_args)
         return BoundTrain(launch, (p, m, v, X, Y, idx, loss_out, step_counter, xg, xg_ticks, self._tile_ws, lr_tab,
                                    class_weight, self._clip_ws),
                           p.device.index or 0)
@@ -618,7 +652,7 @@ class FusedMLPKernel:
               pred_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, norm=None,
               grid: Optional[int] = None, stream: Optional[int] = None,
               class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
-              activation: str = "relu"):
+              activation: str = "relu", hidden_norm: Optional[str] = None):
         """One forward-only launch over rows ``idx[0 .. n)`` of ``X`` (``idx=None``: rows ``0 .. n - 1``).
 
         Per-row outputs, each optional: ``logits_out`` / ``probs_out`` fp32 [n, C], ``pred_out`` int32 [n] (argmax,
@@ -632,10 +666,12 @@ class FusedMLPKernel:
         ``class_weight`` (cuda fp32 [C]) / ``label_smoothing`` as in ``train`` (CE only): word 0 is then the numerator
         ``sum_i num_i`` of torch's weighted mean; ``weighted_infer_stats`` divides it by ``W``.
 
-        ``activation``: the model's hidden activation, as in ``train``."""
+        ``activation``: the model's hidden activation, as in ``train``.  ``hidden_norm``: ``train``'s ``norm`` (the
+        keyword ``norm`` is the input normalisation here): ``"layer"`` for a model with LayerNorm in its hidden layers,
+        whose ``p`` carries the gamma / beta tail."""
         if not self.infer_supported(self.dims):
             raise ValueError(f"the inference kernel does not take the architecture {self.dims}")
-        self._check_params(p)
+        self._check_params(p, norm=hidden_norm)
         if p.data_ptr() % 16:
             raise ValueError("the flat parameter buffer must lie on a 16-byte boundary")
         n = int(n)
@@ -670,6 +706,8 @@ class FusedMLPKernel:
         wl_args = self._check_wloss(class_weight, label_smoothing, loss, p.device)
         if check_activation(activation) != "relu":
             wl_args = dict(wl_args, activation=activation)
+        if hidden_norm is not None:
+            wl_args = dict(wl_args, hidden_norm=hidden_norm)
         ws = self._infer_ws(p.device, n) if Y is not None else None
         native().mlp_infer(self.dims, ptr(p), ptr(X), X.stride(0), ptr(idx), ptr(Y), n, ptr(mean), ptr(std),
                            LOSS_KINDS[loss], ptr(logits_out), ptr(probs_out), ptr(pred_out), ptr(ws),
@@ -713,9 +751,12 @@ class BoundTrain:
 
 # ---------------------------------------------------------------------------- reference
 def reference_mlp_forward(p: torch.Tensor, dims: Sequence[int], x: torch.Tensor,
-                          activation: str = "relu") -> torch.Tensor:
+                          activation: str = "relu", norm=None) -> torch.Tensor:
     """Plain-torch forward of the flat-parameter MLP (no dropout) in p's dtype, for numerics tests."""
+    import torch.nn.functional as F
+
     act = activation_fn(activation)
+    tail = mlp_num_params(dims)  # (norm="layer": gamma_l, beta_l of the hidden layers behind all linears)
     off = 0
     h = x
     L = len(dims) - 1
@@ -727,5 +768,8 @@ def reference_mlp_forward(p: torch.Tensor, dims: Sequence[int], x: torch.Tensor,
         off += o
         h = h @ W.t() + b
         if l < L - 1:
+            if check_norm(norm) is not None:
+                h = F.layer_norm(h, (o,), p[tail: tail + o], p[tail + o: tail + 2 * o], 1e-5)
+                tail += 2 * o
             h = act(h)
     return h

@@ -102,6 +102,11 @@ def spec_activation(spec: Dict) -> str:
     return spec.get("activation", "relu")
 
 
+def spec_norm(spec: Dict):
+    """The hidden layers' norm a fused_spec() asks for (models/mlp.py carries the key only when set): None or "layer"."""
+    return spec.get("norm")
+
+
 class _EngineBase:
     name = "base"
 
@@ -151,6 +156,9 @@ class FusedMLPEngine(_EngineBase):
             return spec["loss"] == "ce" and tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
         if spec_activation(spec) != "relu":
             # GELU / tanh-GELU / SiLU: only the batch-tiled trainer has them, at any batch it takes
+            return tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
+        if spec_norm(spec) is not None:
+            # LayerNorm in the hidden layers: only the batch-tiled trainer has it, at any batch it takes
             return tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
         return FusedMLPKernel.supported(spec["dims"], batch_size)
 
@@ -204,13 +212,16 @@ class FusedMLPEngine(_EngineBase):
         # grad-mode launch (it is part of the model), validation through the tiled inference kernel.  Under DDP the step
         # path is the tile plan's: grad-mode launch -> RCCL -> flat optimizer
         self.activation = spec_activation(spec)
-        tiled = self.weighted or self.activation != "relu" or self.K > 1 or self.kind != "adam" or bool(self.clip) or tile_plan
+        # LayerNorm in the hidden layers (models/mlp.py): the tile plan likewise and on every launch; the flat buffers
+        # carry gamma / beta of every hidden layer behind all linears, which is parameters() order
+        self.norm = spec_norm(spec)
+        tiled = self.weighted or self.activation != "relu" or self.norm is not None or self.K > 1 or self.kind != "adam" or bool(self.clip) or tile_plan
         bmax = TILE_BMAX if tiled else (4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
         self.kernel = FusedMLPKernel(self.dims, bmax=bmax)
         if self.K > 1 and self.kernel.plan.trainer(self.B, accumulate=self.K) != "tile":
             raise ValueError(f"accumulate_grad_batches={self.K} at batch {self.B}: over the batch-tiled trainer's "
                              "slot cap (accumulate * ceil(batch / 32) <= 256)")
-        self.P = mlp_num_params(self.dims)
+        self.P = mlp_num_params(self.dims, self.norm)
         dev = ctx.device
         self.device = dev
         cw = spec.get("class_weight")
@@ -220,6 +231,10 @@ class FusedMLPEngine(_EngineBase):
             self.wloss = dict(class_weight=self.class_weight, label_smoothing=float(spec.get("label_smoothing", 0.0)))
         if self.activation != "relu":  # (rides with the loss options: every train, grad and infer launch gets them)
             self.wloss["activation"] = self.activation
+        self.iloss = dict(self.wloss)  # the same options of an infer launch, where `norm` is the input normalisation
+        if self.norm is not None:
+            self.wloss["norm"] = self.norm
+            self.iloss["hidden_norm"] = self.norm
         self.p = self._flat_from_model().to(dev)
         self.m = torch.zeros_like(self.p)
         self.v = torch.zeros_like(self.p)
@@ -300,6 +315,9 @@ class FusedMLPEngine(_EngineBase):
         out = []
         for lin in self.model.linear_layers():
             out += [lin.weight, lin.bias]
+        if self.norm is not None:  # the tail: gamma_l, beta_l of every hidden layer
+            for ln in self.model.norm_layers():
+                out += [ln.weight, ln.bias]
         return out
 
     def _flat_from_model(self) -> torch.Tensor:
@@ -698,15 +716,15 @@ class FusedMLPEngine(_EngineBase):
         if r.numel() > self.val_idx.numel():
             self.val_idx = torch.zeros(r.numel(), dtype=torch.int32, device=self.device)
         self.val_idx[: r.numel()].copy_(r)
-        if self.weighted or self.activation != "relu":
-            # mlp_eval_kernel knows no weights and only ReLU: one launch of the tiled inference kernel over the shard, the weighted
+        if self.weighted or self.activation != "relu" or self.norm is not None:
+            # mlp_eval_kernel knows no weights, no LayerNorm and only ReLU: one launch of the tiled inference kernel over the shard, the weighted
             # mean sum_i num_i / sum_i w[y_i] of the whole shard, then the cross-rank mean as below
             stats = getattr(self, "_infer_stats", None)
             if stats is None:
                 C = self.dims[-1]
                 stats = self._infer_stats = torch.zeros(2 + C * C, dtype=torch.int64, device=self.device)
             self.kernel.infer(self.p, self.X, r.numel(), idx=self.val_idx, Y=self.Y, loss=self.loss, stats_out=stats,
-                              **self.wloss)
+                              **self.iloss)
             vl, correct, _ = weighted_infer_stats(*self.kernel.infer_stats(stats), self.class_weight)
             vals = self.ctx.all_reduce_mean(torch.tensor([vl, correct / r.numel()], dtype=torch.float64)).tolist()
             return vals[0], vals[1]

@@ -131,6 +131,9 @@ def _flat_params(model, device) -> torch.Tensor:
     parts = []
     for lin in model.linear_layers():
         parts += [lin.weight, lin.bias]
+    if model.fused_spec().get("norm") is not None:  # gamma_l, beta_l of the hidden layers behind all linears
+        for ln in model.norm_layers():
+            parts += [ln.weight, ln.bias]
     return torch.cat([t.detach().float().reshape(-1).cpu() for t in parts]).to(device)
 
 
@@ -157,6 +160,8 @@ def _native_launch(trainer, model, X, Y, local, want_logits: bool):
                   label_smoothing=eps)
     if spec.get("activation", "relu") != "relu":  # the model's hidden activation (absent: ReLU)
         wl["activation"] = spec["activation"]
+    if spec.get("norm") is not None:  # LayerNorm in the hidden layers (`norm` below is the input normalisation)
+        wl["hidden_norm"] = spec["norm"]
     kern.infer(_flat_params(model, dev), Xd, n, idx=idx, Y=Yd, loss=spec["loss"], logits_out=logits,
                stats_out=stats, norm=_norm_on(trainer, dev), **wl)
     if stats is None:
