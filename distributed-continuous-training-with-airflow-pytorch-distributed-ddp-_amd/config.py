@@ -53,7 +53,8 @@ class ModelConfig:
     class_weight: Any = None
     label_smoothing: float = 0.0
     activation: str = "relu"  # hidden activation of the MLP family: relu | gelu | gelu_tanh | silu
-    norm: Any = None  # normalisation between a hidden Linear and its activation (MLP family): None | "layer"
+    norm: Any = None  # normalisation between a hidden Linear and its activation (MLP family): None | "layer" | "rms"
+    residual: bool = False  # skip connection around the second of two hidden layers of equal width (MLP family)
     # TabTransformer-only knobs
     d_model: int = 64
     n_heads: int = 4

@@ -91,7 +91,8 @@ static int activation_kind(const std::string& name) {
 static int norm_kind_of(const std::string& name) {
   if (name.empty() || name == "none") return dct::MLP_NORM_OFF;
   if (name == "layer") return dct::MLP_NORM_LAYER;
-  throw std::invalid_argument("norm must be None or 'layer', got '" + name + "'");
+  if (name == "rms") return dct::MLP_NORM_RMS;
+  throw std::invalid_argument("norm must be None, 'layer' or 'rms', got '" + name + "'");
 }
 
 // The key of a described launch (MlpPlan.trainer): what mlp_launch_key would derive from its arguments,
@@ -99,7 +100,8 @@ static int norm_kind_of(const std::string& name) {
 static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, int rank, int loss_kind, bool prof,
                                    bool cursor, bool stage, bool pending, bool aligned, bool weighted,
                                    int accumulate, const std::string& optimizer = "adam", bool clipped = false,
-                                   const std::string& activation = "relu", const std::string& norm = "") {
+                                   const std::string& activation = "relu", const std::string& norm = "",
+                                   bool residual = false) {
   dct::MlpLaunchKey k{};
   k.B = batch; k.mode = mode; k.steps = steps; k.loss_kind = loss_kind;
   k.xg_world = world; k.xg_rank = rank;
@@ -114,11 +116,12 @@ static dct::MlpLaunchKey query_key(int batch, int mode, int steps, int world, in
   k.clipped = mode == 0 && clipped;
   k.act = activation_kind(activation);
   k.norm = norm_kind_of(norm);
+  k.residual = residual;
   return k;
 }
 
 // Validated arguments of a training launch (the kernels trust their arguments).
-static dct::MlpNormArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t grad_out,
+static dct::MlpResArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t grad_out,
                                     uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items, int B, int steps,
                                     int t0, float lr, float b1, float b2, float eps, float wd, float dropout,
                                     uint32_t seed, uint32_t step_base, uintptr_t loss_out, int mode, int loss_kind,
@@ -128,16 +131,18 @@ static dct::MlpNormArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintpt
                                     float label_smooth = 0.f, int accum = 1, const std::string& optimizer = "adam",
                                     float momentum = 0.f, float dampening = 0.f, bool nesterov = false,
                                     int clip_kind = 0, float clip_val = 0.f,
-                                    const std::string& activation = "relu", const std::string& norm = "") {
+                                    const std::string& activation = "relu", const std::string& norm = "",
+                                   bool residual = false) {
   if (!plan.supported) throw std::runtime_error("MLP too large for the fused kernel");
   if (steps < 1 || n_items < 1 || B < 1) throw std::invalid_argument("empty launch");
   if (accum < 1) throw std::invalid_argument("accumulate must be >= 1");
   // (with accumulation a step is a window of accum batches)
   if (!cursor && (int64_t)(steps - 1) * B * accum >= n_items) throw std::invalid_argument("more steps than batches");
-  dct::MlpNormArgs a{};
+  dct::MlpResArgs a{};
   a.accum = accum;
   a.act_kind = activation_kind(activation);  // part of the model: train and grad mode alike
   a.norm_kind = norm_kind_of(norm);          // likewise
+  a.residual = residual ? 1 : 0;             // likewise
   a.p = P<float>(p);
   a.m = P<float>(mo);
   a.v = P<float>(vo);
@@ -214,7 +219,7 @@ static dct::MlpNormArgs make_train_args(const MlpPlan& plan, uintptr_t p, uintpt
   return a;
 }
 
-static void launch_train(const MlpPlan& plan, dct::MlpNormArgs& a, uintptr_t stream) {
+static void launch_train(const MlpPlan& plan, dct::MlpResArgs& a, uintptr_t stream) {
   const dct::MlpShape* sh = plan.sh();
   void* st = reinterpret_cast<void*>(stream);
   const dct::MlpChoice c = plan.select(dct::mlp_launch_key(a));
@@ -249,7 +254,7 @@ static void launch_train(const MlpPlan& plan, dct::MlpNormArgs& a, uintptr_t str
 // keyword arguments and the Python-side operand checks.
 struct MlpLaunch {
   MlpPlan plan;
-  dct::MlpNormArgs base{};
+  dct::MlpResArgs base{};
   int64_t n_items = 0;   // index entries bound at base.idx
   int64_t loss_len = 0;  // loss slots bound at base.loss_out (0 = none)
   void run(int first_step, int steps, uintptr_t stream) const {
@@ -258,7 +263,7 @@ struct MlpLaunch {
     const int64_t off = (int64_t)first_step * rows;
     if (off + (int64_t)(steps - 1) * rows >= n_items) throw std::invalid_argument("MlpLaunch.run: past the index list");
     if (base.loss_out && first_step + steps > loss_len) throw std::invalid_argument("MlpLaunch.run: past the loss buffer");
-    dct::MlpNormArgs a = base;
+    dct::MlpResArgs a = base;
     a.idx = base.idx + off;
     a.n_items = (int)(n_items - off);
     a.steps = steps;
@@ -343,30 +348,31 @@ PYBIND11_MODULE(_dct_native, m) {
       // optimizer step (> 1: the batch-tiled trainer's plan only, within its slot cap); `optimizer`: "adam", "adamw"
       // or "sgd" (a train-mode launch of the last two: the batch-tiled trainer's plan only); `clipped`: a train-mode
       // launch that clips its gradient (by norm or by value: the batch-tiled trainer's plan only); `activation`:
-      // "relu", "gelu", "gelu_tanh" or "silu" (the last three: the batch-tiled trainer's plan only); `norm`: "" or
-      // "layer" (LayerNorm in every hidden layer: the batch-tiled trainer's plan only).  No device needed.
+      // "relu", "gelu", "gelu_tanh" or "silu" (the last three: the batch-tiled trainer's plan only); `norm`: "",
+      // "layer" or "rms" (LayerNorm / RMSNorm in every hidden layer: the batch-tiled trainer's plan only); `residual`: a
+      // skip connection around the second of two hidden layers of equal width (likewise).  No device needed.
 #define MLP_QUERY_ARGS                                                                                              \
   py::arg("batch"), py::arg("mode") = 0, py::arg("steps") = 1, py::arg("world") = 1, py::arg("rank") = 0,           \
       py::arg("loss_kind") = 0, py::arg("prof") = false, py::arg("cursor") = false, py::arg("stage") = false,       \
       py::arg("pending") = false, py::arg("aligned") = true, py::arg("weighted") = false,                           \
       py::arg("accumulate") = 1, py::arg("optimizer") = "adam", py::arg("clipped") = false,              \
-      py::arg("activation") = "relu", py::arg("norm") = ""
+      py::arg("activation") = "relu", py::arg("norm") = "", py::arg("residual") = false
       .def("trainer", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
                          bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted,
                          int accumulate, const std::string& optimizer, bool clipped, const std::string& activation,
-                         const std::string& norm) {
+                         const std::string& norm, bool residual) {
         return std::string(dct::mlp_trainer_name(
             plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
-                                  weighted, accumulate, optimizer, clipped, activation, norm))
+                                  weighted, accumulate, optimizer, clipped, activation, norm, residual))
                 .trainer));
       }, MLP_QUERY_ARGS)
       // whether that launch reads its staged-batch buffer (the wave kernels and mlp_block5's grad mode do)
       .def("uses_stage", [](const MlpPlan& plan, int batch, int mode, int steps, int world, int rank, int loss_kind,
                             bool prof, bool cursor, bool stage, bool pending, bool aligned, bool weighted,
                             int accumulate, const std::string& optimizer, bool clipped, const std::string& activation,
-                         const std::string& norm) {
+                         const std::string& norm, bool residual) {
         return plan.select(query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending, aligned,
-                                     weighted, accumulate, optimizer, clipped, activation, norm))
+                                     weighted, accumulate, optimizer, clipped, activation, norm, residual))
             .use_stage;
       }, MLP_QUERY_ARGS)
       // one trainer's own predicate on that launch, whatever the selector would choose first (tests): "block5",
@@ -374,9 +380,9 @@ PYBIND11_MODULE(_dct_native, m) {
       .def("takes", [](const MlpPlan& plan, const std::string& which, int batch, int mode, int steps, int world,
                        int rank, int loss_kind, bool prof, bool cursor, bool stage, bool pending, bool aligned,
                        bool weighted, int accumulate, const std::string& optimizer, bool clipped,
-                       const std::string& activation, const std::string& norm) {
+                       const std::string& activation, const std::string& norm, bool residual) {
         const dct::MlpLaunchKey k = query_key(batch, mode, steps, world, rank, loss_kind, prof, cursor, stage, pending,
-                                              aligned, weighted, accumulate, optimizer, clipped, activation, norm);
+                                              aligned, weighted, accumulate, optimizer, clipped, activation, norm, residual);
         const dct::MlpShape& sh = *plan.sh();
         if (which == "block5") return dct::mlp_block5_takes(sh, k);
         if (which == "block5_xg") return dct::mlp_block5_xg_shape_ok(sh, k);
@@ -396,14 +402,14 @@ PYBIND11_MODULE(_dct_native, m) {
              uintptr_t xg_status, int64_t xg_timeout, int xg_poll, uintptr_t tile_ws, int64_t tile_ws_floats,
              uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate, const std::string& optimizer,
              float momentum, float dampening, bool nesterov, int clip_kind, float clip_val, uintptr_t clip_ws,
-             int64_t clip_ws_floats, const std::string& activation, const std::string& norm) {
+             int64_t clip_ws_floats, const std::string& activation, const std::string& norm, bool residual) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
-            dct::MlpNormArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
+            dct::MlpResArgs a = make_train_args(plan, p, mo, vo, grad_out, X, ldx, Y, idx, n_items, B, steps, t0, lr,
                                                  b1, b2, eps, wd, dropout, seed, step_base, loss_out, mode, loss_kind,
                                                  step_counter, cursor, prof, pending, stage, xg_recv, xg_peers,
                                                  xg_world, xg_rank, xg_status, xg_timeout, xg_poll, class_w,
                                                  label_smooth, accumulate, optimizer, momentum, dampening, nesterov,
-                                                 clip_kind, clip_val, activation, norm);
+                                                 clip_kind, clip_val, activation, norm, residual);
             a.clip_ws = P<float>(clip_ws);
             a.clip_ws_floats = clip_ws_floats;
             a.tile_ws = P<float>(tile_ws);
@@ -423,7 +429,7 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("optimizer") = "adam", py::arg("momentum") = 0.f, py::arg("dampening") = 0.f,
           py::arg("nesterov") = false, py::arg("clip_kind") = 0, py::arg("clip_val") = 0.f,
           py::arg("clip_ws") = (uintptr_t)0, py::arg("clip_ws_floats") = 0, py::arg("activation") = "relu",
-          py::arg("norm") = "")
+          py::arg("norm") = "", py::arg("residual") = false)
       .def(
           "prepare_train",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t mo, uintptr_t vo, uintptr_t X, int ldx, uintptr_t Y,
@@ -433,14 +439,14 @@ PYBIND11_MODULE(_dct_native, m) {
              int64_t xg_timeout, int xg_poll, uintptr_t xg_ticks, uintptr_t tile_ws, int64_t tile_ws_floats,
              uintptr_t lr_tab, uintptr_t class_w, float label_smooth, int accumulate, const std::string& optimizer,
              float momentum, float dampening, bool nesterov, int clip_kind, float clip_val, uintptr_t clip_ws,
-             int64_t clip_ws_floats, const std::string& activation, const std::string& norm) {
+             int64_t clip_ws_floats, const std::string& activation, const std::string& norm, bool residual) {
             if (lr_tab & 15) throw std::invalid_argument("lr_tab must be 16-byte aligned");
             auto l = std::make_unique<MlpLaunch>(MlpLaunch{plan});
             l->base = make_train_args(plan, p, mo, vo, 0, X, ldx, Y, idx, n_items, B, 1, 0, lr, b1, b2, eps, wd,
                                       dropout, seed, 0, loss_out, 0, loss_kind, step_counter, 0, 0, 0, 0, xg_recv,
                                       xg_peers, xg_world, xg_rank, xg_status, xg_timeout, xg_poll, class_w,
                                       label_smooth, accumulate, optimizer, momentum, dampening, nesterov, clip_kind,
-                                      clip_val, activation, norm);
+                                      clip_val, activation, norm, residual);
             l->base.clip_ws = P<float>(clip_ws);
             l->base.clip_ws_floats = clip_ws_floats;
             l->base.xg_ticks = P<unsigned long long>(xg_ticks);
@@ -461,7 +467,7 @@ PYBIND11_MODULE(_dct_native, m) {
           py::arg("accumulate") = 1, py::arg("optimizer") = "adam", py::arg("momentum") = 0.f,
           py::arg("dampening") = 0.f, py::arg("nesterov") = false, py::arg("clip_kind") = 0,
           py::arg("clip_val") = 0.f, py::arg("clip_ws") = (uintptr_t)0, py::arg("clip_ws_floats") = 0,
-          py::arg("activation") = "relu", py::arg("norm") = "")
+          py::arg("activation") = "relu", py::arg("norm") = "", py::arg("residual") = false)
       .def(
           "eval",
           [](const MlpPlan& plan, uintptr_t p, uintptr_t X, int ldx, uintptr_t Y, uintptr_t idx, int n_items,
@@ -1097,8 +1103,8 @@ PYBIND11_MODULE(_dct_native, m) {
   m.def("mlp_tile_clip_ws_floats", [](const std::vector<int>& dims) {
     return (int64_t)dct_mlp_tile_clip_ws_floats(dims.data(), (int)dims.size() - 1);
   }, py::arg("dims"));
-  // the two workspaces and the flat parameter count of a model with LayerNorm in its hidden layers (norm = "layer"),
-  // whose P carries the gamma / beta tail; norm = "": the sizes above and the linears' count (0: not a tile shape)
+  // the two workspaces and the flat parameter count of a model with LayerNorm / RMSNorm in its hidden layers (norm = "layer" /
+  // "rms"), whose P carries the gamma / beta (rms: gamma) tail; norm = "": the sizes above and the linears' count (0: not a tile shape)
   m.def("mlp_tile_ws_floats_norm", [](const std::vector<int>& dims, int B, int accumulate, const std::string& norm) {
     return (int64_t)dct_mlp_tile_ws_floats_norm(dims.data(), (int)dims.size() - 1, B, accumulate, norm_kind_of(norm));
   }, py::arg("dims"), py::arg("batch"), py::arg("accumulate") = 1, py::arg("norm") = "");
@@ -1127,9 +1133,10 @@ PYBIND11_MODULE(_dct_native, m) {
         [](const std::vector<int>& dims, uintptr_t p, uintptr_t X, int ldx, uintptr_t idx, uintptr_t Y, int64_t n,
            uintptr_t norm_mean, uintptr_t norm_std, int loss_kind, uintptr_t logits_out, uintptr_t probs_out,
            uintptr_t pred_out, uintptr_t ws, int64_t ws_bytes, uintptr_t stats, int grid, uintptr_t stream,
-           uintptr_t class_w, float label_smooth, const std::string& activation, const std::string& hidden_norm) {
+           uintptr_t class_w, float label_smooth, const std::string& activation, const std::string& hidden_norm,
+           bool residual) {
           if (dims.size() < 2) throw std::invalid_argument("mlp_infer: dims");
-          dct::MlpInferNormArgs a{};
+          dct::MlpInferResArgs a{};
           a.p = P<const float>(p);
           a.X = P<const float>(X);
           a.ldx = ldx;
@@ -1149,6 +1156,7 @@ PYBIND11_MODULE(_dct_native, m) {
           a.label_smooth = label_smooth;
           a.act_kind = activation_kind(activation);
           a.norm_kind = norm_kind_of(hidden_norm);
+          a.residual = residual ? 1 : 0;
           check(dct_mlp_infer(dims.data(), (int)dims.size() - 1, &a, grid, reinterpret_cast<void*>(stream)),
                 "mlp_infer");
         },
@@ -1156,7 +1164,7 @@ PYBIND11_MODULE(_dct_native, m) {
         py::arg("norm_mean"), py::arg("norm_std"), py::arg("loss_kind"), py::arg("logits_out"), py::arg("probs_out"),
         py::arg("pred_out"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stats"), py::arg("grid"), py::arg("stream"),
         py::arg("class_w") = (uintptr_t)0, py::arg("label_smooth") = 0.f, py::arg("activation") = "relu",
-        py::arg("hidden_norm") = "");
+        py::arg("hidden_norm") = "", py::arg("residual") = false);
   m.def("mlp_xg_slab_granules", [](const std::vector<int>& dims) {
     return (int64_t)dct_mlp_xg_slab_granules(dims.data(), (int)dims.size() - 1);
   });

@@ -203,8 +203,10 @@ struct MlpActArgs : MlpClipArgs {
 // the layer's H units - biased variance, u = gamma * (z - mean) * rstd + beta, then activation and dropout.  Batch-tiled
 // trainer and batch-tiled inference kernel only.  Its parameters follow all linears in the flat buffer:
 // gamma_1 [H1], beta_1 [H1] (, gamma_2 [H2], beta_2 [H2]), so every woff / boff stands and P grows by 2 (H1 + H2).
-enum MlpNorm { MLP_NORM_OFF = 0, MLP_NORM_LAYER = 1 };
-inline bool mlp_norm_ok(int kind) { return kind == MLP_NORM_OFF || kind == MLP_NORM_LAYER; }
+// MLP_NORM_RMS is torch's nn.RMSNorm(H, eps = 1e-5): u = gamma * z * rsqrt(mean_k z_k^2 + eps), no mean pass and no beta;
+// its tail is gamma_1 [H1] (, gamma_2 [H2]) and P grows by H1 + H2.
+enum MlpNorm { MLP_NORM_OFF = 0, MLP_NORM_LAYER = 1, MLP_NORM_RMS = 2 };
+inline bool mlp_norm_ok(int kind) { return kind >= MLP_NORM_OFF && kind <= MLP_NORM_RMS; }
 
 // MlpNormArgs: MlpActArgs with the norm kind behind the activation kind - what the host builds and hands to the
 // launchers.  No kernel takes it: the batch-tiled trainer's step kernel gets the kind as a template argument, like the
@@ -213,6 +215,18 @@ inline bool mlp_norm_ok(int kind) { return kind == MLP_NORM_OFF || kind == MLP_N
 struct MlpNormArgs : MlpActArgs {
   int norm_kind;
 };
+
+// MlpResArgs: MlpNormArgs with the skip connection behind the norm kind - what the host builds and hands to the
+// launchers; no kernel takes it (a template argument of the batch-tiled trainer's step kernel, like the two kinds).
+// residual != 0: h2 = h1 + Dropout(act(Norm(Linear(h1)))) around the second hidden layer of a net with two hidden
+// layers of equal width (layer 0 and the head unchanged); any other shape is hipErrorInvalidValue.  Part of the model,
+// so grad-mode launches honour it.  mlp_select.h refuses such a launch on every other trainer.
+struct MlpResArgs : MlpNormArgs {
+  int residual;
+};
+inline bool mlp_residual_ok(const int* dims, int L, int residual) {
+  return !residual || (L == 3 && dims[1] == dims[2]);
+}
 
 constexpr int XG_MAXW = 8;  // ranks of the in-kernel exchange (one node)
 
@@ -250,6 +264,10 @@ struct MlpInferArgs {
 // the kind as a template argument.
 struct MlpInferNormArgs : MlpInferArgs {
   int norm_kind;
+};
+// MlpInferResArgs: the same with MlpResArgs::residual behind the norm kind (a template argument of the kernel too)
+struct MlpInferResArgs : MlpInferNormArgs {
+  int residual;
 };
 
 // fills *sh for dims[0 .. L] and plans of up to bmax rows per step (mlp_block = -1: auto, until the plan stamps
@@ -302,11 +320,12 @@ long long dct_mlp_tile_clip_ws_floats_norm(const int* dims, int L, int norm);
 long long dct_mlp_tile_num_params(const int* dims, int L, int norm);
 // hipErrorInvalidValue also for an unknown clip_kind, a clip_val that is not a finite value > 0 while the kind is set,
 // and norm clipping without a clip_ws of that size (train mode; grad mode ignores the clip fields), and for an
-// act_kind that is no MlpAct or a norm_kind that is no MlpNorm (both modes)
-int dct_mlp_tile_train(const int* dims, int L, const dct::MlpNormArgs* a, void* stream);
+// act_kind that is no MlpAct, a norm_kind that is no MlpNorm or a residual on a shape that is not two hidden layers of
+// equal width (both modes)
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpResArgs* a, void* stream);
 // batch-tiled forward-only inference (mlp_infer.hip); grid <= 0: default.  It and dct_mlp_tile_train share one
 // forward and one host check (mlp_tile_fwd.h): the shapes of dct_mlp_tile_supported, p on a 16-byte boundary;
-// hipErrorInvalidValue also for an act_kind that is no MlpAct or a norm_kind that is no MlpNorm
-int dct_mlp_infer(const int* dims, int L, const dct::MlpInferNormArgs* a, int grid, void* stream);
+// hipErrorInvalidValue also for an act_kind that is no MlpAct, a norm_kind that is no MlpNorm or such a residual
+int dct_mlp_infer(const int* dims, int L, const dct::MlpInferResArgs* a, int grid, void* stream);
 long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n);
 }

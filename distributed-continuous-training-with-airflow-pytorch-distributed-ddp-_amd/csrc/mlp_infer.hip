@@ -80,9 +80,14 @@ __device__ __forceinline__ float pick4(const float (&v)[4], int i) {
 // as it was, the smooth kinds run the trainer's own act(z) (mlp_tile_fwd.h act_grad) in the two layers' epilogues
 // NORM: LayerNorm in every hidden layer (MlpInferNormArgs::norm_kind, chosen on the host likewise; false is the kernel as it
 // was): the layers store the pre-norm z + b and the trainer's own norm_rows (mlp_tile_fwd.h) normalises the image in
-// place behind a barrier, A = act(gamma * xhat + beta) - xhat and rstd are not kept, the LDS carve does not grow
-template <int L, bool WL, int ACT = MLP_ACT_RELU, bool NORM = false>
+// place behind a barrier, A = act(gamma * xhat + beta) - xhat and rstd are not kept, the LDS carve does not grow;
+// MLP_NORM_RMS: the same through rms_rows, A = act(gamma * xhat)
+// RES: the skip connection around the second hidden layer (MlpInferResArgs::residual, L == 3): layer 1's epilogue -
+// layer1_block's, or the norm's row pass - stores A2 = A1 + act(.).  A2 is an image of its own in this carve (lo.a2
+// behind lo.a1 when L == 3), so the add reads A1 where the MFMA's operand is read and writes elsewhere
+template <int L, bool WL, int ACT = MLP_ACT_RELU, int NORM = MLP_NORM_OFF, bool RES = false>
 __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, long long T, long long S, int nslots) {
+  static_assert(!RES || L == 3, "the skip connection spans the second of two hidden layers");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds lo = lds_layout(L);
   const int tid = threadIdx.x;
@@ -157,7 +162,11 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
       __syncthreads();
 
       // ---- layer 0: A1 = relu(X0 W0^T + b0)
-      if constexpr (NORM) {
+      if constexpr (NORM == MLP_NORM_RMS) {
+        layer0<1>(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
+        __syncthreads();
+        rms_rows(A1, nullptr, a.p + norm_off(tp, 0, NORM), H1, 0, tid, NormActEpilogue<ACT>{});
+      } else if constexpr (NORM != MLP_NORM_OFF) {
         layer0<1>(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
         __syncthreads();
         const int go = norm_off(tp, 0);
@@ -172,14 +181,21 @@ __global__ __launch_bounds__(NT) void mlp_infer_kernel(Plan tp, MlpInferArgs a, 
         for (int c = 0; c < 2; ++c) {
           const int cb = wave + 4 * c;
           if (cb * 16 >= H2) break;
-          if constexpr (NORM) layer1_block<1>(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
+          if constexpr (NORM != MLP_NORM_OFF) layer1_block<1>(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
+          else if constexpr (RES) layer1_block<1>(A2, A1, wf[c], cb, b1v[c], H1, j, q, ResEpilogue<ACT>{A1});
           else if constexpr (ACT == MLP_ACT_RELU) layer1_block(A2, A1, wf[c], cb, b1v[c], H1, j, q, NoEpilogue{});
           else layer1_block<ACT>(A2, A1, wf[c], cb, b1v[c], H1, j, q, ActEpilogue<ACT>{});
         }
         __syncthreads();
-        if constexpr (NORM) {
+        if constexpr (NORM == MLP_NORM_RMS) {
+          const float* g2 = a.p + norm_off(tp, 1, NORM);
+          if constexpr (RES) rms_rows(A2, nullptr, g2, H2, 1, tid, ResEpilogue<ACT>{A1});
+          else rms_rows(A2, nullptr, g2, H2, 1, tid, NormActEpilogue<ACT>{});
+          __syncthreads();
+        } else if constexpr (NORM != MLP_NORM_OFF) {
           const int go = norm_off(tp, 1);
-          norm_rows(A2, nullptr, a.p + go, a.p + go + H2, H2, 1, tid, NormActEpilogue<ACT>{});
+          if constexpr (RES) norm_rows(A2, nullptr, a.p + go, a.p + go + H2, H2, 1, tid, ResEpilogue<ACT>{A1});
+          else norm_rows(A2, nullptr, a.p + go, a.p + go + H2, H2, 1, tid, NormActEpilogue<ACT>{});
           __syncthreads();
         }
       }
@@ -288,10 +304,10 @@ __global__ __launch_bounds__(FOLD_NT) void mlp_infer_fold_kernel(const long long
   }
 }
 
-template <int L, bool WL, int ACT = MLP_ACT_RELU, bool NORM = false>
+template <int L, bool WL, int ACT = MLP_ACT_RELU, int NORM = MLP_NORM_OFF, bool RES = false>
 static hipError_t launch(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
   const size_t bytes = (size_t)lds_layout(L).total * sizeof(float);
-  auto fn = mlp_infer_kernel<L, WL, ACT, NORM>;
+  auto fn = mlp_infer_kernel<L, WL, ACT, NORM, RES>;
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), bytes, st, tp, a, sl.T, sl.S, sl.nslots);
@@ -302,10 +318,11 @@ static hipError_t launch(const Plan& tp, const MlpInferArgs& a, const Slots& sl,
 }
 
 // a smooth activation's launch (instantiated behind the ReLU kernels, which keep their place in the code object)
-template <int ACT, bool NORM = false>
+template <int ACT, int NORM = MLP_NORM_OFF, bool RES = false>
 static hipError_t launch_act(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st);
-// a normed model's launch (behind all of them)
-static hipError_t launch_norm(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st);
+// a normed model's launch (behind all of them; LayerNorm first), and behind it that of a model with a skip connection
+static hipError_t launch_norm(const Plan& tp, const MlpInferNormArgs& a, const Slots& sl, int grid, hipStream_t st);
+static hipError_t launch_res(const Plan& tp, const MlpInferNormArgs& a, const Slots& sl, int grid, hipStream_t st);
 
 }  // namespace infer
 }  // namespace dct
@@ -319,10 +336,11 @@ long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n) {
   return (long long)dct::infer::slots_of(n).nslots * dct::infer::SLOT_WORDS * 8;
 }
 
-int dct_mlp_infer(const int* dims, int L, const dct::MlpInferNormArgs* a, int grid, void* stream) {
+int dct_mlp_infer(const int* dims, int L, const dct::MlpInferResArgs* a, int grid, void* stream) {
   dct::tile::Plan tp;
   if (!dct::mlp_norm_ok(a->norm_kind)) return (int)hipErrorInvalidValue;
-  if (!dct::tile::plan_launch(&tp, dims, L, a->p, a->norm_kind != 0)) return (int)hipErrorInvalidValue;
+  if (!dct::tile::plan_launch(&tp, dims, L, a->p, a->norm_kind)) return (int)hipErrorInvalidValue;
+  if (!dct::mlp_residual_ok(dims, L, a->residual)) return (int)hipErrorInvalidValue;
   if (a->n < 1 || !a->X || a->ldx < tp.D0) return (int)hipErrorInvalidValue;
   if ((a->norm_mean == nullptr) != (a->norm_std == nullptr)) return (int)hipErrorInvalidValue;
   if (a->loss_kind != 0 && a->loss_kind != 1) return (int)hipErrorInvalidValue;
@@ -337,7 +355,8 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferNormArgs* a, int gr
   }
   if (grid <= 0) grid = sl.nslots < 1024 ? sl.nslots : 1024;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // LayerNorm: every activation, ReLU included, on the normed instantiations
+  if (a->residual) return (int)dct::infer::launch_res(tp, *a, sl, grid, st);
+  // LayerNorm / RMSNorm: every activation, ReLU included, on the normed instantiations
   if (a->norm_kind) return (int)dct::infer::launch_norm(tp, *a, sl, grid, st);
   switch (a->act_kind) {
     case dct::MLP_ACT_GELU: return (int)dct::infer::launch_act<dct::MLP_ACT_GELU>(tp, *a, sl, grid, st);
@@ -357,19 +376,40 @@ int dct_mlp_infer(const int* dims, int L, const dct::MlpInferNormArgs* a, int gr
 namespace dct {
 namespace infer {
 
-template <int ACT, bool NORM>
+template <int ACT, int NORM, bool RES>
 static hipError_t launch_act(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
-  if (a.class_w || a.label_smooth != 0.f)
-    return tp.L == 2 ? launch<2, true, ACT, NORM>(tp, a, sl, grid, st) : launch<3, true, ACT, NORM>(tp, a, sl, grid, st);
-  return tp.L == 2 ? launch<2, false, ACT, NORM>(tp, a, sl, grid, st) : launch<3, false, ACT, NORM>(tp, a, sl, grid, st);
+  const bool wl = a.class_w || a.label_smooth != 0.f;
+  if constexpr (RES) {  // two hidden layers: no 2-layer instantiation exists
+    if (tp.L != 3) return hipErrorInvalidValue;
+    return wl ? launch<3, true, ACT, NORM, true>(tp, a, sl, grid, st) : launch<3, false, ACT, NORM, true>(tp, a, sl, grid, st);
+  } else {
+    if (wl)
+      return tp.L == 2 ? launch<2, true, ACT, NORM>(tp, a, sl, grid, st) : launch<3, true, ACT, NORM>(tp, a, sl, grid, st);
+    return tp.L == 2 ? launch<2, false, ACT, NORM>(tp, a, sl, grid, st) : launch<3, false, ACT, NORM>(tp, a, sl, grid, st);
+  }
 }
 
-static hipError_t launch_norm(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
+// every activation of one (norm kind, skip) pair
+template <int NORM, bool RES>
+static hipError_t launch_model(const Plan& tp, const MlpInferArgs& a, const Slots& sl, int grid, hipStream_t st) {
   switch (a.act_kind) {
-    case MLP_ACT_GELU: return launch_act<MLP_ACT_GELU, true>(tp, a, sl, grid, st);
-    case MLP_ACT_GELU_TANH: return launch_act<MLP_ACT_GELU_TANH, true>(tp, a, sl, grid, st);
-    case MLP_ACT_SILU: return launch_act<MLP_ACT_SILU, true>(tp, a, sl, grid, st);
-    default: return launch_act<MLP_ACT_RELU, true>(tp, a, sl, grid, st);
+    case MLP_ACT_GELU: return launch_act<MLP_ACT_GELU, NORM, RES>(tp, a, sl, grid, st);
+    case MLP_ACT_GELU_TANH: return launch_act<MLP_ACT_GELU_TANH, NORM, RES>(tp, a, sl, grid, st);
+    case MLP_ACT_SILU: return launch_act<MLP_ACT_SILU, NORM, RES>(tp, a, sl, grid, st);
+    default: return launch_act<MLP_ACT_RELU, NORM, RES>(tp, a, sl, grid, st);
+  }
+}
+
+static hipError_t launch_norm(const Plan& tp, const MlpInferNormArgs& a, const Slots& sl, int grid, hipStream_t st) {
+  if (a.norm_kind == MLP_NORM_LAYER) return launch_model<MLP_NORM_LAYER, false>(tp, a, sl, grid, st);
+  return launch_model<MLP_NORM_RMS, false>(tp, a, sl, grid, st);
+}
+
+static hipError_t launch_res(const Plan& tp, const MlpInferNormArgs& a, const Slots& sl, int grid, hipStream_t st) {
+  switch (a.norm_kind) {
+    case MLP_NORM_OFF: return launch_model<MLP_NORM_OFF, true>(tp, a, sl, grid, st);
+    case MLP_NORM_LAYER: return launch_model<MLP_NORM_LAYER, true>(tp, a, sl, grid, st);
+    default: return launch_model<MLP_NORM_RMS, true>(tp, a, sl, grid, st);
   }
 }
 

@@ -57,6 +57,12 @@ MlpLaunchKey mlp_launch_key(const MlpNormArgs& a) {
   return k;
 }
 
+MlpLaunchKey mlp_launch_key(const MlpResArgs& a) {
+  MlpLaunchKey k = mlp_launch_key(static_cast<const MlpNormArgs&>(a));
+  k.residual = a.residual != 0;
+  return k;
+}
+
 static MlpChoice none(const char* why, bool plan_level) { return MlpChoice{MLP_NONE, false, why, plan_level}; }
 static MlpChoice take(MlpTrainer t, bool use_stage = false) { return MlpChoice{t, use_stage, nullptr, false}; }
 
@@ -69,6 +75,8 @@ MlpChoice mlp_select_trainer(const MlpShape& sh, bool use_wave, bool use_tile, c
     if (!mlp_tile_batch_ok(k.B)) return none("batch outside the batch-tiled trainer's range", false);
     if (k.accum && !mlp_tile_window_ok(k.B, k.accum))
       return none("accumulation window over the batch-tiled trainer's slot cap (accum * ceil(B / 32) <= 256)", false);
+    if (k.residual && !mlp_residual_ok(sh.dims, sh.L, 1))
+      return none("a skip connection needs two hidden layers of equal width", true);
     return take(MLP_TILE);
   }
   if (k.accum)
@@ -80,7 +88,9 @@ MlpChoice mlp_select_trainer(const MlpShape& sh, bool use_wave, bool use_tile, c
   if (k.act != MLP_ACT_RELU)
     return none("GELU / tanh-GELU / SiLU need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.norm != MLP_NORM_OFF)
-    return none("LayerNorm needs the batch-tiled trainer's plan (bmax 1024)", true);
+    return none("LayerNorm / RMSNorm need the batch-tiled trainer's plan (bmax 1024)", true);
+  if (k.residual)
+    return none("a skip connection needs the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.weighted)
     return none("class weights / label smoothing need the batch-tiled trainer's plan (bmax 1024)", true);
   if (k.pending && !use_wave) return none("update-then-grad needs the single-wave kernel", true);

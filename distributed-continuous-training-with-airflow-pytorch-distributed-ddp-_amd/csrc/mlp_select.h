@@ -36,13 +36,16 @@ struct MlpLaunchKey {
                     // gradient between its fold and its optimizer; grad-mode launches ignore the clip fields
   int act;          // MlpActArgs::act_kind (0 = ReLU): only the batch-tiled trainer has the smooth activations, in
                     // train and in grad mode alike (the kind is part of the model)
-  int norm;         // MlpNormArgs::norm_kind (0 = none): only the batch-tiled trainer has LayerNorm, in train and in
-                    // grad mode alike
+  int norm;         // MlpNormArgs::norm_kind (0 = none): only the batch-tiled trainer has LayerNorm / RMSNorm, in train
+                    // and in grad mode alike
+  bool residual;    // MlpResArgs::residual: only the batch-tiled trainer has the skip connection, for two hidden layers
+                    // of equal width, in train and in grad mode alike
 };
 MlpLaunchKey mlp_launch_key(const MlpArgs& a);  // the only place pointers become bools (clipped: false)
 MlpLaunchKey mlp_launch_key(const MlpClipArgs& a);  // the same, with `clipped` from the clip fields
 MlpLaunchKey mlp_launch_key(const MlpActArgs& a);   // the same, with `act` from the activation kind
 MlpLaunchKey mlp_launch_key(const MlpNormArgs& a);  // the same, with `norm` from the norm kind
+MlpLaunchKey mlp_launch_key(const MlpResArgs& a);   // the same, with `residual`
 
 struct MlpChoice {
   MlpTrainer trainer;

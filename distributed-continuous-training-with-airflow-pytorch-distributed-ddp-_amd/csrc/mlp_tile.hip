@@ -116,10 +116,23 @@ __device__ __forceinline__ float drop_apply(float z, uint32_t seed, uint32_t gst
 // xor tree, dz = rstd * (gw - s1 - xhat * s2) in place - and the dW / db code that follows reads dz as it always did.
 // Rows >= bs: the pre-norm is the bias vector, whose variance may be 0 - rstd = rsqrt(eps) and xhat = 0 are finite,
 // and g is an exact zero, so du, gw, s1, s2 and dz are exact zeros.  Every sum has a fixed order.
-template <int L, bool WL, bool ACC, int ACT = MLP_ACT_RELU, bool NORM = false>
+// NORM == MLP_NORM_RMS: nn.RMSNorm (eps 1e-5) in the same places, in LayerNorm's carve: rms_rows (one pass for sum z^2,
+// u = gamma * xhat, xhat = z * rstd) keeps xhat and rstd where norm_rows keeps them, and rms_backward writes the
+// dgamma column sums alone and dz = rstd * (gw - xhat * s2).  gamma_2 sits H1 words behind gamma_1 (norm_off).
+// RES: the skip connection h2 = h1 + Dropout(act(Norm(Linear(h1)))) of a net with two hidden layers of equal width
+// (MlpResArgs::residual, chosen on the host likewise; L == 3 only).  Forward: layer 1's epilogue - layer1_block's, or
+// the norm's row pass - adds A1[r][o] to what it stores into A2; A1 is only read there, also while other waves still
+// read it as their MFMA operand, and A2 is an image of its own.  Backward: A2 is a sum, so its sign is no ReLU mask -
+// every RES instantiation takes the D-image path of the smooth activations in both layers, ReLU with D = keep *
+// scale * [. > 0].  The skip hands the head's gradient G[r][k] = sum_c dZL[r][c] * Wl[c][k] to A1 beside the branch's:
+// the dZ1 MFMA epilogue recomputes G from dZL and Wl, both still in LDS (C <= 4 FMAs per element, no image and no
+// barrier more), dZ1 = (dZ2 W1 + G) * D1.  Rows >= bs: dZL = 0, so G is an exact zero.  dW1 = dZ2^T A1 and the head's
+// dW = dZL^T A2 are as they were.
+template <int L, bool WL, bool ACC, int ACT = MLP_ACT_RELU, int NORM = MLP_NORM_OFF, bool RES = false>
 __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs a) {
+  static_assert(!RES || L == 3, "the skip connection spans the second of two hidden layers");
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const Lds lo = lds_layout(L, NORM);
+  const Lds lo = lds_layout(L, NORM != MLP_NORM_OFF);
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int j = lane & 15, q = lane >> 4;
@@ -188,7 +201,19 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
     const float ks = dropping ? drop_apply(1.0f, a.seed, gstep, LI, row0 + r, o, a.dropout, dscale) : 1.0f;
     (LI == 0 ? dZ1 : dZ2)[r * LDH + o] = d * ks;
     (LI == 0 ? XH1 : XH2)[r * LDH + o] = xhat;
+    if constexpr (RES) {
+      if (LI == 1) return A1[r * LDH + o] + av * ks;  // the skip
+    }
     return av * ks;
+  };
+  // the plain layers' epilogue behind a skip connection (RES without a norm), on the pre-activation: act_drop with
+  // ReLU's D = keep * scale * [z > 0] too, and layer 1 adds its input
+  const auto res_drop = [&](int LI, int r, int o, float z) {
+    float d = z > 0.f ? 1.0f : 0.f, av = fmaxf(z, 0.f);
+    if constexpr (ACT != MLP_ACT_RELU) av = act_grad<ACT>(z, d);
+    const float ks = dropping ? drop_apply(1.0f, a.seed, gstep, LI, row0 + r, o, a.dropout, dscale) : 1.0f;
+    (LI == 0 ? dZ1 : dZ2)[r * LDH + o] = d * ks;
+    return LI == 1 ? A1[r * LDH + o] + av * ks : av * ks;
   };
   // LayerNorm backward of hidden layer LI with H units, whose du = g * D stands in dZ behind a barrier: the slot's
   // dgamma / dbeta words (threads 0 .. H - 1 sum dbeta, H .. 2 H - 1 dgamma, rows ascending), then dz in place
@@ -228,6 +253,32 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
     for (int k = part; k < H; k += 8) drow[k] = rstd * (drow[k] * gamma[k] - s1 - xrow[k] * s2);
     __syncthreads();
   };
+  // (res_drop above and rms_backward here repeat norm_drop / norm_backward rather than parametrise them: LayerNorm's
+  // own lambdas stay as they were written)
+  // RMSNorm backward, likewise: the slot's dgamma words alone (threads 0 .. H - 1, rows ascending), then
+  // dz = rstd * (gw - xhat * s2), s2 = sum(gw * xhat) / H, in place
+  const auto rms_backward = [&](int LI, int H, float* dZ, const float* XH) {
+    const int go = norm_off(tp, LI, MLP_NORM_RMS);
+    if (tid < H) {
+      float s = 0.f;
+      for (int r = 0; r < R; ++r) s = fmaf(dZ[r * LDH + tid], XH[r * LDH + tid], s);
+      slot[go + tid] = s;
+    }
+    __syncthreads();
+    const int r = tid >> 3, part = tid & 7;
+    const float* gamma = a.p + go;
+    float* drow = dZ + r * LDH;
+    const float* xrow = XH + r * LDH;
+    float s2 = 0.f;
+    for (int k = part; k < H; k += 8) s2 = fmaf(drow[k] * gamma[k], xrow[k], s2);
+    s2 += __shfl_xor(s2, 1);
+    s2 += __shfl_xor(s2, 2);
+    s2 += __shfl_xor(s2, 4);
+    s2 *= 1.0f / (float)H;
+    const float rstd = RS[LI * R + r];
+    for (int k = part; k < H; k += 8) drow[k] = rstd * (drow[k] * gamma[k] - xrow[k] * s2);
+    __syncthreads();
+  };
 
   // ---- this wave's W1 fragments of the forward MFMA: issued first, so their L2 round trips overlap the
   // gather and layer 0 instead of chaining inside the k loop
@@ -250,12 +301,17 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
   __syncthreads();
 
   // ---- layer 0: A1 = dropout(relu(X0 W0^T + b0))
-  if constexpr (NORM) {  // A1 = z + b0, then normalised in place: A1 = keep scale act(u), dZ1 = D, XH1 = xhat
+  if constexpr (NORM == MLP_NORM_RMS) {  // the same through rms_rows
+    layer0<1>(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
+    __syncthreads();
+    rms_rows(A1, RS, a.p + norm_off(tp, 0, NORM), H1, 0, tid, norm_drop);
+  } else if constexpr (NORM != MLP_NORM_OFF) {  // A1 = z + b0, then normalised in place: A1 = keep scale act(u), dZ1 = D, XH1 = xhat
     layer0<1>(A1, W0s, X0, D0, H1, tid, NoEpilogue{});
     __syncthreads();
     const int go = norm_off(tp, 0);
     norm_rows(A1, RS, a.p + go, a.p + go + H1, H1, 0, tid, norm_drop);
-  } else if constexpr (ACT == MLP_ACT_RELU) layer0(A1, W0s, X0, D0, H1, tid, drop);
+  } else if constexpr (RES) layer0<1>(A1, W0s, X0, D0, H1, tid, res_drop);  // dZ1 = D for ReLU too
+  else if constexpr (ACT == MLP_ACT_RELU) layer0(A1, W0s, X0, D0, H1, tid, drop);
   else layer0<ACT>(A1, W0s, X0, D0, H1, tid, act_drop);  // A1 = keep scale act(z), dZ1 = D
   __syncthreads();
 
@@ -265,12 +321,16 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
     for (int c = 0; c < 2; ++c) {
       const int cb = wave + 4 * c;
       if (cb * 16 >= H2) break;
-      if constexpr (NORM) layer1_block<1>(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, NoEpilogue{});
+      if constexpr (NORM != MLP_NORM_OFF) layer1_block<1>(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, NoEpilogue{});
+      else if constexpr (RES) layer1_block<1>(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, res_drop);  // A2 = A1 + .
       else if constexpr (ACT == MLP_ACT_RELU) layer1_block(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, drop);
       else layer1_block<ACT>(A2, A1, wf[c], cb, a.p[tp.boff[1] + cb * 16 + j], H1, j, q, act_drop);  // dZ2 = D
     }
     __syncthreads();
-    if constexpr (NORM) {  // A2 = z + b1 normalised in place, dZ2 = D, XH2 = xhat
+    if constexpr (NORM == MLP_NORM_RMS) {
+      rms_rows(A2, RS + R, a.p + norm_off(tp, 1, NORM), H2, 1, tid, norm_drop);
+      __syncthreads();
+    } else if constexpr (NORM != MLP_NORM_OFF) {  // A2 = z + b1 normalised in place, dZ2 = D, XH2 = xhat
       const int go = norm_off(tp, 1);
       norm_rows(A2, RS + R, a.p + go, a.p + go + H2, H2, 1, tid, norm_drop);
       __syncthreads();
@@ -327,7 +387,7 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
 #pragma unroll
     for (int c = 0; c < 4; ++c)
       if (c < C) g = fmaf(dZL[r * 4 + c], Wl[c * K + k], g);
-    if constexpr (ACT == MLP_ACT_RELU && !NORM) {
+    if constexpr (ACT == MLP_ACT_RELU && NORM == MLP_NORM_OFF && !RES) {
       const float av = Ah[r * LDH + k];
       dZh[r * LDH + k] = (av > 0.f) ? g * dscale : 0.f;
     } else {
@@ -357,7 +417,8 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
   }
   __syncthreads();
   // ---- LayerNorm backward of the last hidden layer: du -> dgamma, dbeta, dz
-  if constexpr (NORM) norm_backward(L - 2, K, dZh, (L == 3) ? XH2 : XH1);
+  if constexpr (NORM == MLP_NORM_RMS) rms_backward(L - 2, K, dZh, (L == 3) ? XH2 : XH1);
+  else if constexpr (NORM != MLP_NORM_OFF) norm_backward(L - 2, K, dZh, (L == 3) ? XH2 : XH1);
 
   if (L == 3) {
     // ---- dZ1 = mask(A1) * (dZ2 W1) on the MFMA: k runs over the H2 outputs
@@ -387,9 +448,19 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r0 = 4 * q + i, r1 = r0 + 16;
-        if constexpr (ACT == MLP_ACT_RELU && !NORM) {
+        if constexpr (ACT == MLP_ACT_RELU && NORM == MLP_NORM_OFF && !RES) {
           dZ1[r0 * LDH + ic] = (A1[r0 * LDH + ic] > 0.f) ? acc0[i] * dscale : 0.f;
           dZ1[r1 * LDH + ic] = (A1[r1 * LDH + ic] > 0.f) ? acc1[i] * dscale : 0.f;
+        } else if constexpr (RES) {  // + the skip's G = dZL Wl (K = H2 = H1, so ic < K)
+          float g0 = 0.f, g1 = 0.f;
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (c < C) {
+              g0 = fmaf(dZL[r0 * 4 + c], Wl[c * K + ic], g0);
+              g1 = fmaf(dZL[r1 * 4 + c], Wl[c * K + ic], g1);
+            }
+          dZ1[r0 * LDH + ic] = (acc0[i] + g0) * dZ1[r0 * LDH + ic];
+          dZ1[r1 * LDH + ic] = (acc1[i] + g1) * dZ1[r1 * LDH + ic];
         } else {
           dZ1[r0 * LDH + ic] = acc0[i] * dZ1[r0 * LDH + ic];  // layer 0's D, in place
           dZ1[r1 * LDH + ic] = acc1[i] * dZ1[r1 * LDH + ic];
@@ -417,7 +488,8 @@ __global__ __launch_bounds__(NT) void mlp_tile_step_kernel(Plan tp, MlpStepArgs 
     }
     __syncthreads();
     // ---- LayerNorm backward of layer 0
-    if constexpr (NORM) norm_backward(0, H1, dZ1, XH1);
+    if constexpr (NORM == MLP_NORM_RMS) rms_backward(0, H1, dZ1, XH1);
+    else if constexpr (NORM != MLP_NORM_OFF) norm_backward(0, H1, dZ1, XH1);
   }
 
   // ---- dW0 = dZ1^T X0, db0 (VALU)
@@ -760,13 +832,15 @@ static void launch_fold_clipped(int grid, const Plan& tp, const MlpClipArgs& a, 
 }
 
 // CLIPPED: a train-mode launch with a clip kind set - the same step kernel, launch_fold_clipped behind it
-// ACT, NORM: the step kernel's activation and LayerNorm; the folds behind it know neither (tp.P counts the norm's words)
-template <int L, bool WL, bool ACC, bool CLIPPED = false, int ACT = MLP_ACT_RELU, bool NORM = false>
+// ACT, NORM, RES: the step kernel's activation, norm kind and skip connection; the folds behind it know none of them
+// (tp.P counts the norm's words)
+template <int L, bool WL, bool ACC, bool CLIPPED = false, int ACT = MLP_ACT_RELU, int NORM = MLP_NORM_OFF,
+          bool RES = false>
 static hipError_t launch_steps(const Plan& tp, const std::conditional_t<CLIPPED, MlpClipArgs, MlpArgs>& a0,
                                unsigned int* done, hipStream_t st) {
   const int T = (a0.B + R - 1) / R;
-  const size_t bytes = (size_t)lds_layout(L, NORM).total * sizeof(float);
-  auto fn = mlp_tile_step_kernel<L, WL, ACC, ACT, NORM>;
+  const size_t bytes = (size_t)lds_layout(L, NORM != MLP_NORM_OFF).total * sizeof(float);
+  auto fn = mlp_tile_step_kernel<L, WL, ACC, ACT, NORM, RES>;
   const int AK = ACC ? a0.accum : 1;  // micro-batches per optimizer step: the index list advances by AK * B rows
   hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return e;
@@ -792,9 +866,12 @@ static hipError_t train_clipped(const Plan& tp, const MlpClipArgs& a, int L, boo
 // the smooth activations' dispatch (likewise behind it, and behind the clipped ones)
 static hipError_t train_act(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
                             hipStream_t st);
-// the normed models' dispatch (behind all of them)
-static hipError_t train_norm(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
+// the normed models' dispatch (behind all of them), LayerNorm first
+static hipError_t train_norm(const Plan& tp, const MlpNormArgs& a, int L, bool wl, bool acc, unsigned int* done,
                              hipStream_t st);
+// the dispatch of the models with a skip connection (behind those): every norm kind, L == 3
+static hipError_t train_res(const Plan& tp, const MlpNormArgs& a, bool wl, bool acc, unsigned int* done,
+                            hipStream_t st);
 
 }  // namespace tile
 
@@ -857,26 +934,27 @@ long long dct_mlp_tile_clip_ws_floats(const int* dims, int L) {
 long long dct_mlp_tile_ws_floats_norm(const int* dims, int L, int B, int accum, int norm) {
   if (!norm) return dct_mlp_tile_ws_floats_accum(dims, L, B, accum);
   dct::tile::Plan tp;
-  if (!dct::tile::make_plan(&tp, dims, L, true) || !dct::mlp_tile_window_ok(B, accum)) return 0;
+  if (!dct::mlp_norm_ok(norm) || !dct::tile::make_plan(&tp, dims, L, norm) || !dct::mlp_tile_window_ok(B, accum)) return 0;
   const long long T = (B + dct::tile::R - 1) / dct::tile::R;
   return (accum > 1 ? accum : 1) * T * tp.Pp + 4;
 }
 
 long long dct_mlp_tile_clip_ws_floats_norm(const int* dims, int L, int norm) {
   dct::tile::Plan tp;
-  return dct::tile::make_plan(&tp, dims, L, norm != 0) ? dct::tile::clip_ws_layout(tp).total : 0;
+  return dct::mlp_norm_ok(norm) && dct::tile::make_plan(&tp, dims, L, norm) ? dct::tile::clip_ws_layout(tp).total : 0;
 }
 
 long long dct_mlp_tile_num_params(const int* dims, int L, int norm) {
   dct::tile::Plan tp;
-  return dct::tile::make_plan(&tp, dims, L, norm != 0) ? tp.P : 0;
+  return dct::mlp_norm_ok(norm) && dct::tile::make_plan(&tp, dims, L, norm) ? tp.P : 0;
 }
 
-int dct_mlp_tile_train(const int* dims, int L, const dct::MlpNormArgs* a, void* stream) {
+int dct_mlp_tile_train(const int* dims, int L, const dct::MlpResArgs* a, void* stream) {
   dct::tile::Plan tp;
   if (!dct::mlp_norm_ok(a->norm_kind)) return (int)hipErrorInvalidValue;
   const int norm = a->norm_kind;
-  if (!dct::tile::plan_launch(&tp, dims, L, a->p, norm != 0)) return (int)hipErrorInvalidValue;
+  if (!dct::tile::plan_launch(&tp, dims, L, a->p, norm)) return (int)hipErrorInvalidValue;
+  if (!dct::mlp_residual_ok(dims, L, a->residual)) return (int)hipErrorInvalidValue;
   if (!dct::mlp_act_ok(a->act_kind)) return (int)hipErrorInvalidValue;
   if (a->B < 1 || a->B > dct::tile::BMAX || a->steps < 1 || a->n_items < 1) return (int)hipErrorInvalidValue;
   if (a->mode == 1 && a->steps != 1) return (int)hipErrorInvalidValue;
@@ -897,7 +975,9 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpNormArgs* a, void* 
   if (clipped && a->clip_kind == dct::MLP_CLIP_NORM &&
       (!a->clip_ws || ((uintptr_t)a->clip_ws & 15) || a->clip_ws_floats < dct_mlp_tile_clip_ws_floats_norm(dims, L, norm)))
     return (int)hipErrorInvalidValue;
-  // LayerNorm: its own step-kernel instantiations for every activation, in train and grad mode alike
+  // a skip connection: its own step-kernel instantiations for every norm kind and activation
+  if (a->residual) return (int)dct::tile::train_res(tp, *a, wl, accum > 1, done, st);
+  // LayerNorm / RMSNorm: their own step-kernel instantiations for every activation, in train and grad mode alike
   if (norm) return (int)dct::tile::train_norm(tp, *a, L, wl, accum > 1, done, st);
   // a smooth activation: its own step-kernel instantiations in train and grad mode alike, every fold as it is
   if (a->act_kind != dct::MLP_ACT_RELU) return (int)dct::tile::train_act(tp, *a, L, wl, accum > 1, done, st);
@@ -940,9 +1020,17 @@ static hipError_t train_clipped(const Plan& tp, const MlpClipArgs& a, int L, boo
                 : launch_steps<3, false, true, true>(tp, a, done, st);
 }
 
-template <int ACT, bool CLIPPED, bool NORM = false>
+template <int ACT, bool CLIPPED, int NORM = MLP_NORM_OFF, bool RES = false>
 static hipError_t train_act_steps(const Plan& tp, const MlpClipArgs& a, int L, bool wl, bool acc, unsigned int* done,
                                   hipStream_t st) {
+  if constexpr (RES) {  // two hidden layers: no 2-layer instantiation exists
+    if (L != 3) return hipErrorInvalidValue;
+    if (!acc)
+      return wl ? launch_steps<3, true, false, CLIPPED, ACT, NORM, true>(tp, a, done, st)
+                : launch_steps<3, false, false, CLIPPED, ACT, NORM, true>(tp, a, done, st);
+    return wl ? launch_steps<3, true, true, CLIPPED, ACT, NORM, true>(tp, a, done, st)
+              : launch_steps<3, false, true, CLIPPED, ACT, NORM, true>(tp, a, done, st);
+  } else {
   if (!acc) {
     if (wl)
       return L == 2 ? launch_steps<2, true, false, CLIPPED, ACT, NORM>(tp, a, done, st)
@@ -955,13 +1043,15 @@ static hipError_t train_act_steps(const Plan& tp, const MlpClipArgs& a, int L, b
                   : launch_steps<3, true, true, CLIPPED, ACT, NORM>(tp, a, done, st);
   return L == 2 ? launch_steps<2, false, true, CLIPPED, ACT, NORM>(tp, a, done, st)
                 : launch_steps<3, false, true, CLIPPED, ACT, NORM>(tp, a, done, st);
+  }
 }
 
-template <int ACT, bool NORM = false>
+template <int ACT, int NORM = MLP_NORM_OFF, bool RES = false>
 static hipError_t train_act_kind(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
                                  hipStream_t st) {
-  if (a.mode == 0 && a.clip_kind != MLP_CLIP_OFF) return train_act_steps<ACT, true, NORM>(tp, a, L, wl, acc, done, st);
-  return train_act_steps<ACT, false, NORM>(tp, a, L, wl, acc, done, st);
+  if (a.mode == 0 && a.clip_kind != MLP_CLIP_OFF)
+    return train_act_steps<ACT, true, NORM, RES>(tp, a, L, wl, acc, done, st);
+  return train_act_steps<ACT, false, NORM, RES>(tp, a, L, wl, acc, done, st);
 }
 
 static hipError_t train_act(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
@@ -974,14 +1064,31 @@ static hipError_t train_act(const Plan& tp, const MlpActArgs& a, int L, bool wl,
   }
 }
 
-static hipError_t train_norm(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
-                             hipStream_t st) {
+// every activation of one (norm kind, skip) pair
+template <int NORM, bool RES>
+static hipError_t train_model(const Plan& tp, const MlpActArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                              hipStream_t st) {
   switch (a.act_kind) {
-    case MLP_ACT_RELU: return train_act_kind<MLP_ACT_RELU, true>(tp, a, L, wl, acc, done, st);
-    case MLP_ACT_GELU: return train_act_kind<MLP_ACT_GELU, true>(tp, a, L, wl, acc, done, st);
-    case MLP_ACT_GELU_TANH: return train_act_kind<MLP_ACT_GELU_TANH, true>(tp, a, L, wl, acc, done, st);
-    case MLP_ACT_SILU: return train_act_kind<MLP_ACT_SILU, true>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_RELU: return train_act_kind<MLP_ACT_RELU, NORM, RES>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_GELU: return train_act_kind<MLP_ACT_GELU, NORM, RES>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_GELU_TANH: return train_act_kind<MLP_ACT_GELU_TANH, NORM, RES>(tp, a, L, wl, acc, done, st);
+    case MLP_ACT_SILU: return train_act_kind<MLP_ACT_SILU, NORM, RES>(tp, a, L, wl, acc, done, st);
     default: return hipErrorInvalidValue;
+  }
+}
+
+static hipError_t train_norm(const Plan& tp, const MlpNormArgs& a, int L, bool wl, bool acc, unsigned int* done,
+                             hipStream_t st) {
+  if (a.norm_kind == MLP_NORM_LAYER) return train_model<MLP_NORM_LAYER, false>(tp, a, L, wl, acc, done, st);
+  return train_model<MLP_NORM_RMS, false>(tp, a, L, wl, acc, done, st);
+}
+
+static hipError_t train_res(const Plan& tp, const MlpNormArgs& a, bool wl, bool acc, unsigned int* done,
+                            hipStream_t st) {
+  switch (a.norm_kind) {
+    case MLP_NORM_OFF: return train_model<MLP_NORM_OFF, true>(tp, a, 3, wl, acc, done, st);
+    case MLP_NORM_LAYER: return train_model<MLP_NORM_LAYER, true>(tp, a, 3, wl, acc, done, st);
+    default: return train_model<MLP_NORM_RMS, true>(tp, a, 3, wl, acc, done, st);
   }
 }
 

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mlp_fused.h"
+
 namespace dct {
 namespace tile {
 
@@ -29,13 +31,17 @@ struct Plan {
   int P, Pp;    // parameters, slot stride of the trainer's workspace (floats)
 };
 // With LayerNorm the flat buffer carries gamma_1 [H1], beta_1 [H1] (, gamma_2 [H2], beta_2 [H2]) behind the head's bias:
-// P and Pp count them, woff / boff do not move, and the tail needs no field of its own.
-__host__ __device__ inline int norm_off(const Plan& tp, int layer) {  // gamma of hidden layer 0 / 1; beta = + H
-  return tp.boff[tp.L - 1] + tp.C + (layer == 0 ? 0 : 2 * tp.H1);
+// P and Pp count them, woff / boff do not move, and the tail needs no field of its own.  With RMSNorm (norm = 2,
+// MLP_NORM_RMS) there is no beta: gamma_1 [H1] (, gamma_2 [H2]).
+__host__ __device__ inline int norm_words(int norm) {  // vectors per hidden layer of an MlpNorm kind
+  return norm == MLP_NORM_OFF ? 0 : (norm == MLP_NORM_RMS ? 1 : 2);
+}
+__host__ __device__ inline int norm_off(const Plan& tp, int layer, int norm = MLP_NORM_LAYER) {  // gamma of hidden layer 0 / 1
+  return tp.boff[tp.L - 1] + tp.C + (layer == 0 ? 0 : norm_words(norm) * tp.H1);  // (LayerNorm: beta = + H)
 }
 
-// Shapes: 2 or 3 linear layers, D0 1..32, hidden widths multiples of 16 in 16..128, C 2..4.
-static inline bool make_plan(Plan* tp, const int* dims, int L, bool norm = false) {
+// Shapes: 2 or 3 linear layers, D0 1..32, hidden widths multiples of 16 in 16..128, C 2..4.  norm: the MlpNorm kind.
+static inline bool make_plan(Plan* tp, const int* dims, int L, int norm = 0) {
   if (L != 2 && L != 3) return false;
   const int D0 = dims[0], C = dims[L];
   if (D0 < 1 || D0 > 32 || C < 2 || C > 4) return false;
@@ -55,7 +61,7 @@ static inline bool make_plan(Plan* tp, const int* dims, int L, bool norm = false
     tp->boff[l] = flat;
     flat += dims[l + 1];
   }
-  if (norm) flat += 2 * (tp->H1 + tp->H2);
+  flat += norm_words(norm) * (tp->H1 + tp->H2);
   tp->P = flat;
   tp->Pp = (flat + 2 + 3) & ~3;  // [P] gradients, the loss sum, the weighted loss's sum of w[y]
   return true;
@@ -63,7 +69,7 @@ static inline bool make_plan(Plan* tp, const int* dims, int L, bool norm = false
 
 // What both launchers ask before anything else: a shape make_plan takes, and parameters on a 16-byte boundary -
 // load_w1_frags reads W1 as float4 (woff[1] = (D0 + 1) * H1 floats keeps the alignment of p).
-static inline bool plan_launch(Plan* tp, const int* dims, int L, const float* p, bool norm = false) {
+static inline bool plan_launch(Plan* tp, const int* dims, int L, const float* p, int norm = 0) {
   return make_plan(tp, dims, L, norm) && p && reinterpret_cast<uintptr_t>(p) % 16 == 0;
 }
 
@@ -222,7 +228,30 @@ __device__ __forceinline__ void norm_rows(float* A, float* rs, const float* gamm
   }
 }
 
-// the inference kernel's epilogue of norm_rows: act(u) alone (ACT = 0: ReLU)
+// RMSNorm of one hidden layer's image: norm_rows without the mean - the same 8 lanes per row make ONE pass for
+// sum z^2, close it by the same xor tree, rstd = rsqrt(sum / H + eps), and sweep the row once more: xhat = z rstd,
+// u = gamma xhat, A = epi(LI, r, unit, u, xhat).  An all-zero row has rstd = rsqrt(eps), finite, and xhat = u = 0.
+template <class Epi>
+__device__ __forceinline__ void rms_rows(float* A, float* rs, const float* gamma, int H, int LI, int tid, Epi epi) {
+  const int r = tid >> 3, part = tid & 7;
+  float* row = A + r * LDH;
+  float v = 0.f;
+  for (int k = part; k < H; k += 8) {
+    const float z = row[k];
+    v = fmaf(z, z, v);
+  }
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 4);
+  const float rstd = rsqrtf(fmaf(v, 1.0f / (float)H, 1e-5f));
+  if (rs && part == 0) rs[r] = rstd;
+  for (int k = part; k < H; k += 8) {
+    const float xhat = row[k] * rstd;
+    row[k] = epi(LI, r, k, gamma[k] * xhat, xhat);
+  }
+}
+
+// the inference kernel's epilogue of norm_rows / rms_rows: act(u) alone (ACT = 0: ReLU)
 template <int ACT>
 struct NormActEpilogue {
   __device__ __forceinline__ float operator()(int, int, int, float u, float) const {
@@ -232,6 +261,15 @@ struct NormActEpilogue {
       float d;
       return act_grad<ACT>(u, d);
     }
+  }
+};
+
+// the same behind a skip connection (layer 1 only): skip[r][unit] + act(u), skip = the layer's input image A1
+template <int ACT>
+struct ResEpilogue {
+  const float* skip;
+  __device__ __forceinline__ float operator()(int, int r, int o, float u, float = 0.f) const {
+    return skip[r * LDH + o] + NormActEpilogue<ACT>{}(0, r, o, u, 0.f);
   }
 };
 

@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.fused_mlp import check_activation, check_class_weight, check_norm, check_label_smoothing, check_optimizer
+from ..ops.fused_mlp import (check_activation, check_class_weight, check_label_smoothing, check_norm, check_optimizer,
+                             check_residual)
 from ..trainer.module import TrainModule
 
 # configure_optimizers()'s options and their defaults, which reproduce the reference's Adam(lr): a model records only
@@ -35,19 +36,40 @@ def activation_module(activation: str) -> nn.Module:
             "silu": nn.SiLU}[check_activation(activation)]()
 
 
+class RMSNorm(nn.Module):
+    """``weight * x / sqrt(mean_k(x_k^2) + eps)`` over the last dimension: ``torch.nn.RMSNorm(width, eps=eps)``, whose
+    one parameter it names alike, written out so that no torch version is assumed."""
+
+    def __init__(self, width: int, eps: float = 1e-5):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(int(width)))
+        self.eps = float(eps)
+
+    def forward(self, x):
+        return self.weight * (x * torch.rsqrt(x.pow(2).mean(dim=-1, keepdim=True) + self.eps))
+
+
 class MLPClassifier(TrainModule):
     def __init__(self, input_dim: int, hidden: Sequence[int] = (64,), num_classes: int = 2, dropout: float = 0.2,
                  loss: str = "ce", lr: float = 0.01, class_weight: Optional[Sequence[float]] = None,
                  label_smoothing: float = 0.0, optimizer: str = "adam", weight_decay: float = 0.0,
                  momentum: float = 0.0, nesterov: bool = False, betas: Sequence[float] = (0.9, 0.999),
-                 eps: float = 1e-8, dampening: float = 0.0, activation: str = "relu", norm: Optional[str] = None):
+                 eps: float = 1e-8, dampening: float = 0.0, activation: str = "relu", norm: Optional[str] = None,
+                 residual: bool = False):
         super().__init__()
         self.save_hyperparameters()
-        # a normalisation layer between every hidden Linear and its activation (None, or "layer": nn.LayerNorm(H, eps=1e-5)
-        # with its affine gamma / beta): recorded only when set
+        # a normalisation layer between every hidden Linear and its activation (None, "layer": nn.LayerNorm(H, eps=1e-5)
+        # with its affine gamma / beta, or "rms": RMSNorm(H, eps=1e-5) with gamma alone): recorded only when set
         self.norm = check_norm(norm)
         if self.norm is None:
             self.hparams.pop("norm", None)
+        # a skip connection around the second of two hidden layers of equal width, h2 = h1 + Dropout(act(Norm(Linear(h1))));
+        # layer 0 and the head are unchanged.  Recorded only when set
+        self.residual = check_residual(residual, hidden)
+        if self.residual:
+            self.hparams["residual"] = True
+        else:
+            self.hparams.pop("residual", None)
         # the hidden layers' activation (every hidden layer the same, the head linear): recorded only when it is not
         # the ReLU a model always had
         self.activation = check_activation(activation)
@@ -92,23 +114,31 @@ class MLPClassifier(TrainModule):
         self.net = nn.Sequential(*layers)
         # the norms live in a list of their own, registered after net: the net.<3i> keys are a contract with score.py and
         # existing checkpoints, and parameters() order is all linears, then gamma_1, beta_1 (, gamma_2, beta_2) - the
-        # flat order of the fused kernels.  Without a norm the module has no such attribute's keys at all.
+        # flat order of the fused kernels ("rms": gamma_1 (, gamma_2), keys norms.<i>.weight alone).  Without a norm
+        # the module has no such attribute's keys at all.
         if self.norm is not None:
-            self.norms = nn.ModuleList(nn.LayerNorm(h, eps=1e-5) for h in dims[1:-1])
+            cls = RMSNorm if self.norm == "rms" else nn.LayerNorm
+            self.norms = nn.ModuleList(cls(h, eps=1e-5) for h in dims[1:-1])
         self.dims = dims
         self.dropout_p = float(dropout)
         self.loss_kind = loss
         self.lr = lr
 
     def forward(self, x):
-        if self.norm is None:
+        if self.norm is None and not self.residual:
             return self.net(x)
-        i = 0
-        for m in self.net:  # Linear -> LayerNorm -> activation -> Dropout in every hidden layer, the head plain
+        norms = self.norm_layers()
+        i, skip = 0, None
+        for m in self.net:  # Linear -> norm -> activation -> Dropout in every hidden layer, the head plain
+            if self.residual and i == 1 and isinstance(m, nn.Linear):
+                skip = x  # h1, the second hidden layer's input
             x = m(x)
-            if isinstance(m, nn.Linear) and i < len(self.norms):
-                x = self.norms[i](x)
+            if isinstance(m, nn.Linear):
+                if i < len(norms):
+                    x = norms[i](x)
                 i += 1
+            elif skip is not None and isinstance(m, nn.Dropout):
+                x, skip = skip + x, None
         return x
 
     def compute_loss(self, logits, y):
@@ -160,14 +190,16 @@ class MLPClassifier(TrainModule):
             spec["activation"] = self.activation
         if self.norm is not None:
             spec["norm"] = self.norm
+        if self.residual:
+            spec["residual"] = True
         return spec
 
     def linear_layers(self) -> List[nn.Linear]:
         return [m for m in self.net if isinstance(m, nn.Linear)]
 
-    def norm_layers(self) -> List[nn.LayerNorm]:
-        """The hidden layers' norms in layer order ([] without one): their weight / bias follow all linears in
-        parameters() and in the fused kernels' flat buffer."""
+    def norm_layers(self) -> List[nn.Module]:
+        """The hidden layers' norms in layer order ([] without one): their weight / bias (RMSNorm: weight alone) follow
+        all linears in parameters() and in the fused kernels' flat buffer."""
         return list(self.norms) if self.norm is not None else []
 
 
@@ -175,10 +207,11 @@ class WeatherClassifier(MLPClassifier):
     """Reference model: Linear(D,64)-ReLU-Dropout(0.2)-Linear(64,2), CE, Adam(lr=0.01)."""
 
     def __init__(self, input_dim: int, class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0,
-                 activation: str = "relu", norm: Optional[str] = None, **optim):
+                 activation: str = "relu", norm: Optional[str] = None, residual: bool = False, **optim):
+        # (residual: MLPClassifier's keyword - this model's one hidden layer takes no skip connection, so True raises)
         super().__init__(input_dim=input_dim, hidden=(64,), num_classes=2, dropout=0.2, loss="ce", lr=0.01,
                          class_weight=class_weight, label_smoothing=label_smoothing, activation=activation, norm=norm,
-                         **optim)
+                         residual=residual, **optim)
         # the reference records exactly {"input_dim": D} (save_hyperparameters at :53); the loss and optimizer options
         # join it only when set
         hp = {"input_dim": int(input_dim)}
@@ -197,11 +230,12 @@ class WeatherClassifier(MLPClassifier):
 def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None, num_classes: int = 2,
               dropout: float = 0.2, loss: str = "ce", lr: float = 0.01,
               class_weight: Optional[Sequence[float]] = None, label_smoothing: float = 0.0,
-              activation: str = "relu", norm: Optional[str] = None, **optim) -> MLPClassifier:
+              activation: str = "relu", norm: Optional[str] = None, residual: bool = False,
+              **optim) -> MLPClassifier:
     """``optim``: MLPClassifier's optimizer options (OPTIM_DEFAULTS' keys)."""
     if name == "weather":
         return WeatherClassifier(input_dim, class_weight=class_weight, label_smoothing=label_smoothing,
-                                 activation=activation, norm=norm, **optim)
+                                 activation=activation, norm=norm, residual=residual, **optim)
     # name -> (hidden widths, dropout, loss, lr); BASELINE.json configs 1-4
     presets = {
         "weather-mlp-3x128": ((128, 128), 0.2, "ce", 0.01),
@@ -211,4 +245,4 @@ def build_mlp(name: str, input_dim: int, hidden: Optional[Sequence[int]] = None,
         hidden, dropout, loss, lr = presets[name]
     return MLPClassifier(input_dim, hidden=hidden or (64,), num_classes=num_classes, dropout=dropout, loss=loss, lr=lr,
                          class_weight=class_weight, label_smoothing=label_smoothing, activation=activation, norm=norm,
-                         **optim)
+                         residual=residual, **optim)

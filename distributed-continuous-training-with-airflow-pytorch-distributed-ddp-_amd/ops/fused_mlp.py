@@ -24,9 +24,10 @@ XG_POLL = 3
 
 
 def mlp_num_params(dims: Sequence[int], norm=None) -> int:
-    """Flat parameters of the MLP: all linears, then (``norm="layer"``) gamma and beta of every hidden layer."""
+    """Flat parameters of the MLP: all linears, then (``norm="layer"``) gamma and beta of every hidden layer, or
+    (``norm="rms"``) gamma alone."""
     n = sum(dims[i] * dims[i + 1] + dims[i + 1] for i in range(len(dims) - 1))
-    return n + (2 * sum(dims[1:-1]) if check_norm(norm) is not None else 0)
+    return n + {None: 0, "layer": 2, "rms": 1}[check_norm(norm)] * sum(dims[1:-1])
 
 
 TILE_BMAX = 1024  # largest per-rank batch of the batch-tiled trainer (csrc/mlp_tile.hip)
@@ -89,15 +90,27 @@ def check_activation(activation) -> str:
     return activation
 
 
-NORMS = (None, "layer")  # csrc/mlp_fused.h MlpNorm
+NORMS = (None, "layer", "rms")  # csrc/mlp_fused.h MlpNorm
 
 
 def check_norm(norm) -> Optional[str]:
-    """The hidden layers' normalisation of a model or a launch: ``None``, or ``"layer"`` - ``nn.LayerNorm(H, eps=1e-5)``
-    with its affine parameters between every hidden Linear and its activation; ValueError for anything else."""
+    """The hidden layers' normalisation of a model or a launch: ``None``, ``"layer"`` - ``nn.LayerNorm(H, eps=1e-5)``
+    with its affine parameters between every hidden Linear and its activation - or ``"rms"`` - ``nn.RMSNorm(H,
+    eps=1e-5)``, ``gamma * z / sqrt(mean(z^2) + eps)`` without a beta, in the same place; ValueError for anything else."""
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
     return norm
+
+
+def check_residual(residual, hidden) -> bool:
+    """The skip connection of a model or a launch, ``h2 = h1 + Dropout(act(Norm(Linear(h1))))``: ``hidden`` (the hidden
+    widths) must then be two equal widths; ValueError otherwise."""
+    if not residual:
+        return False
+    hidden = [int(h) for h in hidden]
+    if len(hidden) != 2 or hidden[0] != hidden[1]:
+        raise ValueError(f"residual=True needs two hidden layers of equal width, got hidden={tuple(hidden)}")
+    return True
 
 
 def activation_fn(activation):
@@ -289,14 +302,18 @@ class FusedMLPKernel:
                              "(any batch 1..1024) for an architecture it takes")
         return dict(activation=activation)
 
-    def _check_norm(self, norm, batch: int) -> dict:
-        """The native argument of a launch of a model with LayerNorm ({} without), in train and in grad mode alike."""
-        if check_norm(norm) is None:
-            return {}
-        if self.plan.trainer(int(batch), norm=norm) != "tile":
-            raise ValueError(f"norm={norm!r} needs the batch-tiled trainer: a plan of bmax 1024 "
-                             "(any batch 1..1024) for an architecture it takes")
-        return dict(norm=norm)
+    def _check_norm(self, norm, batch: int, residual: bool = False) -> dict:
+        """The native arguments of a launch of a model with a hidden norm and / or a skip connection ({} without
+        either), in train and in grad mode alike."""
+        args = {}
+        if check_norm(norm) is not None:
+            args["norm"] = norm
+        if check_residual(residual, self.dims[1:-1]):
+            args["residual"] = True
+        if args and self.plan.trainer(int(batch), **args) != "tile":
+            raise ValueError(f"norm={norm!r} / residual={bool(residual)} need the batch-tiled trainer: a plan of bmax "
+                             "1024 (any batch 1..1024) for an architecture it takes")
+        return args
 
     def _check_clip(self, clip_val, clip_algorithm: str, batch: int, device, train: bool, norm=None) -> dict:
         """The native arguments of a launch that clips its gradient ({} when off, and for a grad-mode launch, which
@@ -434,14 +451,19 @@ class FusedMLPKernel:
               lr_tab: Optional[torch.Tensor] = None, class_weight: Optional[torch.Tensor] = None,
               label_smoothing: float = 0.0, accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0,
               dampening: float = 0.0, nesterov: bool = False, clip_val: Optional[float] = None,
-              clip_algorithm: str = "norm", activation: str = "relu", norm: Optional[str] = None):
+              clip_algorithm: str = "norm", activation: str = "relu", norm: Optional[str] = None,
+              residual: bool = False):
         """Run ``steps`` fused optimizer steps (mode 0) or one gradient step (grad_out given).
 
         ``norm``: ``None``, or on the batch-tiled trainer's plan ``"layer"`` - ``nn.LayerNorm(H, eps=1e-5)`` with affine
         parameters between every hidden Linear and its activation.  ``p`` (and ``m``, ``v``, ``grad_out``) then carry
         ``gamma_1, beta_1[, gamma_2, beta_2]`` behind all linears (``mlp_num_params(dims, norm)`` words, torch's
-        ``parameters()`` order); the optimizer and its weight decay treat them like every other word.  Part of the
-        model: a grad-mode launch honours it too.
+        ``parameters()`` order); the optimizer and its weight decay treat them like every other word.  ``"rms"``:
+        ``nn.RMSNorm(H, eps=1e-5)`` there, the tail ``gamma_1[, gamma_2]``.  Part of the model: a grad-mode launch
+        honours it too.
+
+        ``residual``: on that plan, for two hidden layers of equal width, ``h2 = h1 + Dropout(act(Norm(Linear(h1))))``;
+        layer 0 and the head as they are.  Part of the model likewise.
 
         ``activation``: the hidden layers' ``"relu"``, or on the batch-tiled trainer's plan ``"gelu"``, ``"gelu_tanh"``
         or ``"silu"`` (every hidden layer the same, the head linear).  It is part of the model: a grad-mode launch
@@ -490,7 +512,7 @@ class FusedMLPKernel:
             raise ValueError(f"batch {batch} > kernel bmax {self.bmax}")
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
-        norm_args = self._check_norm(norm, batch)
+        norm_args = self._check_norm(norm, batch, residual)
         clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, mode == 0, norm)
         act_args = self._check_activation(activation, batch)
         if steps < 1 or (cursor is None and (steps - 1) * batch * accumulate >= n_items):
@@ -538,7 +560,7 @@ class FusedMLPKernel:
                       accumulate: int = 1, optimizer: str = "adam", momentum: float = 0.0, dampening: float = 0.0,
                       nesterov: bool = False, clip_val: Optional[float] = None,
                       clip_algorithm: str = "norm", activation: str = "relu",
-                      norm: Optional[str] = None) -> "BoundTrain":
+                      norm: Optional[str] = None, residual: bool = False) -> "BoundTrain":
         """Validate the operands of persistent train-mode launches ONCE and bind them natively.
 
         ``BoundTrain.run(first_step, steps)`` then launches steps [first_step, first_step+steps)
@@ -546,7 +568,7 @@ class FusedMLPKernel:
         positional native call (no keyword parsing, no tensor checks), which is what the short
         timed windows of the benchmark contract see.  ``accumulate`` as in ``train``: the steps are
         optimizer steps of ``accumulate`` micro-batches each.  ``optimizer`` / ``momentum`` / ``dampening`` /
-        ``nesterov``, ``clip_val`` / ``clip_algorithm``, ``activation`` and ``norm`` as in ``train``."""
+        ``nesterov``, ``clip_val`` / ``clip_algorithm``, ``activation``, ``norm`` and ``residual`` as in ``train``."""
         if not 1 <= batch <= self.bmax:
             raise ValueError(f"batch {batch} outside 1..{self.bmax}")
         opt_args = self._check_optimizer(optimizer, batch, weight_decay, momentum, dampening, nesterov, True)
@@ -555,7 +577,7 @@ class FusedMLPKernel:
         self._check_data(X, Y, idx, n_items)
         wl_args = self._check_wloss_train(class_weight, label_smoothing, loss, p.device, batch)
         acc_args = self._check_accumulate(accumulate, batch)
-        norm_args = self._check_norm(norm, batch)
+        norm_args = self._check_norm(norm, batch, residual)
         clip_args = self._check_clip(clip_val, clip_algorithm, batch, p.device, True, norm)
         act_args = self._check_activation(activation, batch)
         if step_counter is None or not (step_counter.is_cuda and step_counter.dtype == torch.int32):
@@ -652,7 +674,7 @@ class FusedMLPKernel:
               pred_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, norm=None,
               grid: Optional[int] = None, stream: Optional[int] = None,
               class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
-              activation: str = "relu", hidden_norm: Optional[str] = None):
+              activation: str = "relu", hidden_norm: Optional[str] = None, residual: bool = False):
         """One forward-only launch over rows ``idx[0 .. n)`` of ``X`` (``idx=None``: rows ``0 .. n - 1``).
 
         Per-row outputs, each optional: ``logits_out`` / ``probs_out`` fp32 [n, C], ``pred_out`` int32 [n] (argmax,
@@ -667,7 +689,8 @@ class FusedMLPKernel:
         ``sum_i num_i`` of torch's weighted mean; ``weighted_infer_stats`` divides it by ``W``.
 
         ``activation``: the model's hidden activation, as in ``train``.  ``hidden_norm``: ``train``'s ``norm`` (the
-        keyword ``norm`` is the input normalisation here): ``"layer"`` for a model with LayerNorm in its hidden layers,
+        keyword ``norm`` is the input normalisation here): ``"layer"`` / ``"rms"`` for a model with LayerNorm / RMSNorm in its hidden
+        layers; ``residual``: its skip connection.  A normed model is one
         whose ``p`` carries the gamma / beta tail."""
         if not self.infer_supported(self.dims):
             raise ValueError(f"the inference kernel does not take the architecture {self.dims}")
@@ -708,6 +731,8 @@ class FusedMLPKernel:
             wl_args = dict(wl_args, activation=activation)
         if hidden_norm is not None:
             wl_args = dict(wl_args, hidden_norm=hidden_norm)
+        if check_residual(residual, self.dims[1:-1]):
+            wl_args = dict(wl_args, residual=True)
         ws = self._infer_ws(p.device, n) if Y is not None else None
         native().mlp_infer(self.dims, ptr(p), ptr(X), X.stride(0), ptr(idx), ptr(Y), n, ptr(mean), ptr(std),
                            LOSS_KINDS[loss], ptr(logits_out), ptr(probs_out), ptr(pred_out), ptr(ws),
@@ -751,12 +776,13 @@ class BoundTrain:
 
 # ---------------------------------------------------------------------------- reference
 def reference_mlp_forward(p: torch.Tensor, dims: Sequence[int], x: torch.Tensor,
-                          activation: str = "relu", norm=None) -> torch.Tensor:
+                          activation: str = "relu", norm=None, residual: bool = False) -> torch.Tensor:
     """Plain-torch forward of the flat-parameter MLP (no dropout) in p's dtype, for numerics tests."""
     import torch.nn.functional as F
 
     act = activation_fn(activation)
-    tail = mlp_num_params(dims)  # (norm="layer": gamma_l, beta_l of the hidden layers behind all linears)
+    tail = mlp_num_params(dims)  # (norm="layer": gamma_l, beta_l of the hidden layers behind all linears; "rms": gamma_l)
+    check_residual(residual, dims[1:-1])
     off = 0
     h = x
     L = len(dims) - 1
@@ -766,10 +792,15 @@ def reference_mlp_forward(p: torch.Tensor, dims: Sequence[int], x: torch.Tensor,
         off += i * o
         b = p[off: off + o]
         off += o
-        h = h @ W.t() + b
+        skip, h = h, h @ W.t() + b
         if l < L - 1:
-            if check_norm(norm) is not None:
+            if check_norm(norm) == "rms":
+                h = p[tail: tail + o] * h * torch.rsqrt(h.pow(2).mean(-1, keepdim=True) + 1e-5)
+                tail += o
+            elif norm is not None:
                 h = F.layer_norm(h, (o,), p[tail: tail + o], p[tail + o: tail + 2 * o], 1e-5)
                 tail += 2 * o
             h = act(h)
+            if residual and l == 1:
+                h = skip + h
     return h

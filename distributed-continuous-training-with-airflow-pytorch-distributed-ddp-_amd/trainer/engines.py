@@ -103,8 +103,14 @@ def spec_activation(spec: Dict) -> str:
 
 
 def spec_norm(spec: Dict):
-    """The hidden layers' norm a fused_spec() asks for (models/mlp.py carries the key only when set): None or "layer"."""
+    """The hidden layers' norm a fused_spec() asks for (models/mlp.py carries the key only when set): None, "layer" or
+    "rms"."""
     return spec.get("norm")
+
+
+def spec_residual(spec: Dict) -> bool:
+    """Whether a fused_spec() asks for the skip connection (the key likewise only when set)."""
+    return bool(spec.get("residual", False))
 
 
 class _EngineBase:
@@ -157,8 +163,9 @@ class FusedMLPEngine(_EngineBase):
         if spec_activation(spec) != "relu":
             # GELU / tanh-GELU / SiLU: only the batch-tiled trainer has them, at any batch it takes
             return tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
-        if spec_norm(spec) is not None:
-            # LayerNorm in the hidden layers: only the batch-tiled trainer has it, at any batch it takes
+        if spec_norm(spec) is not None or spec_residual(spec):
+            # LayerNorm / RMSNorm in the hidden layers, a skip connection: only the batch-tiled trainer has them, at any
+            # batch it takes
             return tile_supported(spec["dims"]) and 1 <= batch_size <= TILE_BMAX
         return FusedMLPKernel.supported(spec["dims"], batch_size)
 
@@ -215,7 +222,8 @@ class FusedMLPEngine(_EngineBase):
         # LayerNorm in the hidden layers (models/mlp.py): the tile plan likewise and on every launch; the flat buffers
         # carry gamma / beta of every hidden layer behind all linears, which is parameters() order
         self.norm = spec_norm(spec)
-        tiled = self.weighted or self.activation != "relu" or self.norm is not None or self.K > 1 or self.kind != "adam" or bool(self.clip) or tile_plan
+        self.residual = spec_residual(spec)  # (the skip connection: the tile plan and every launch likewise)
+        tiled = self.weighted or self.activation != "relu" or self.norm is not None or self.residual or self.K > 1 or self.kind != "adam" or bool(self.clip) or tile_plan
         bmax = TILE_BMAX if tiled else (4 if self.B <= 4 else (16 if self.B <= 16 else 1024))
         self.kernel = FusedMLPKernel(self.dims, bmax=bmax)
         if self.K > 1 and self.kernel.plan.trainer(self.B, accumulate=self.K) != "tile":
@@ -235,6 +243,8 @@ class FusedMLPEngine(_EngineBase):
         if self.norm is not None:
             self.wloss["norm"] = self.norm
             self.iloss["hidden_norm"] = self.norm
+        if self.residual:
+            self.wloss["residual"] = self.iloss["residual"] = True
         self.p = self._flat_from_model().to(dev)
         self.m = torch.zeros_like(self.p)
         self.v = torch.zeros_like(self.p)
@@ -315,9 +325,9 @@ class FusedMLPEngine(_EngineBase):
         out = []
         for lin in self.model.linear_layers():
             out += [lin.weight, lin.bias]
-        if self.norm is not None:  # the tail: gamma_l, beta_l of every hidden layer
+        if self.norm is not None:  # the tail: gamma_l, beta_l of every hidden layer (RMSNorm: gamma_l alone)
             for ln in self.model.norm_layers():
-                out += [ln.weight, ln.bias]
+                out += list(ln.parameters())
         return out
 
     def _flat_from_model(self) -> torch.Tensor:
@@ -716,7 +726,7 @@ class FusedMLPEngine(_EngineBase):
         if r.numel() > self.val_idx.numel():
             self.val_idx = torch.zeros(r.numel(), dtype=torch.int32, device=self.device)
         self.val_idx[: r.numel()].copy_(r)
-        if self.weighted or self.activation != "relu" or self.norm is not None:
+        if self.weighted or self.activation != "relu" or self.norm is not None or self.residual:
             # mlp_eval_kernel knows no weights, no LayerNorm and only ReLU: one launch of the tiled inference kernel over the shard, the weighted
             # mean sum_i num_i / sum_i w[y_i] of the whole shard, then the cross-rank mean as below
             stats = getattr(self, "_infer_stats", None)

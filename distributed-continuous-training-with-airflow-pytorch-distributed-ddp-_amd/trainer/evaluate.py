@@ -131,9 +131,9 @@ def _flat_params(model, device) -> torch.Tensor:
     parts = []
     for lin in model.linear_layers():
         parts += [lin.weight, lin.bias]
-    if model.fused_spec().get("norm") is not None:  # gamma_l, beta_l of the hidden layers behind all linears
+    if model.fused_spec().get("norm") is not None:  # gamma_l, beta_l (RMSNorm: gamma_l) of the hidden layers behind all linears
         for ln in model.norm_layers():
-            parts += [ln.weight, ln.bias]
+            parts += list(ln.parameters())
     return torch.cat([t.detach().float().reshape(-1).cpu() for t in parts]).to(device)
 
 
@@ -162,6 +162,8 @@ def _native_launch(trainer, model, X, Y, local, want_logits: bool):
         wl["activation"] = spec["activation"]
     if spec.get("norm") is not None:  # LayerNorm in the hidden layers (`norm` below is the input normalisation)
         wl["hidden_norm"] = spec["norm"]
+    if spec.get("residual"):  # the skip connection around the second hidden layer
+        wl["residual"] = True
     kern.infer(_flat_params(model, dev), Xd, n, idx=idx, Y=Yd, loss=spec["loss"], logits_out=logits,
                stats_out=stats, norm=_norm_on(trainer, dev), **wl)
     if stats is None:

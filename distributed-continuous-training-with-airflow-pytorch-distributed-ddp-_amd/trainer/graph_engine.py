@@ -77,8 +77,8 @@ class GraphMLPEngine:
             return False  # the step kernels' loss knows no class weights / label smoothing: the autograd engine's does
         if spec.get("activation", "relu") != "relu":
             return False  # a GELU / SiLU model trains on the batch-tiled trainer (or autograd), never here
-        if spec.get("norm") is not None:
-            return False  # nor a model with LayerNorm in its hidden layers
+        if spec.get("norm") is not None or spec.get("residual"):
+            return False  # nor a model with a norm in its hidden layers or a skip connection
         return spec["dropout"] == 0.0 and spec["dims"][0] % 8 == 0 and batch_size >= 1
 
     def __init__(self, model, ctx: DistContext, batch_size: int, seed: int, adam: Dict,

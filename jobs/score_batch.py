@@ -44,7 +44,7 @@ def model_from_checkpoint(path: str) -> MLPClassifier:
         raise ValueError(f"{path}: not an MLP-family checkpoint (hyper_parameters {sorted(hp)}): "
                          "score_batch scores the MLP family only")
     kw = {k: hp[k] for k in ("hidden", "num_classes", "dropout", "loss", "class_weight", "label_smoothing",
-                               "activation", "norm") if k in hp}
+                               "activation", "norm", "residual") if k in hp}
     return MLPClassifier(int(hp["input_dim"]), **kw)
 
 

@@ -55,8 +55,10 @@ def parse_args(argv=None):
                    help="cross-entropy label smoothing in [0, 1) (MLP family; default 0)")
     p.add_argument("--activation", default=cfg.model.activation, choices=("relu", "gelu", "gelu_tanh", "silu"),
                    help="hidden activation of the MLP family (default relu)")
-    p.add_argument("--norm", default=cfg.model.norm, choices=("layer",),
+    p.add_argument("--norm", default=cfg.model.norm, choices=("layer", "rms"),
                    help="normalisation between every hidden Linear and its activation (MLP family; default: none)")
+    p.add_argument("--residual", action="store_true", default=cfg.model.residual,
+                   help="skip connection around the second of two hidden layers of equal width (MLP family)")
     p.add_argument("--tracking-uri", default=cfg.tracking.tracking_uri)
     p.add_argument("--experiment", default=cfg.tracking.experiment_name)
     p.add_argument("--accelerator", default=cfg.train.accelerator)
@@ -126,6 +128,8 @@ def main(argv=None) -> int:
         loss_kw["activation"] = a.activation
     if a.norm is not None:
         loss_kw["norm"] = a.norm
+    if a.residual:
+        loss_kw["residual"] = True
     model = build_model(a.model, input_dim, lr=a.lr, **loss_kw, **model_optim_kwargs(a))
 
     world_size = int(os.environ.get("WORLD_SIZE", 1))
