@@ -270,6 +270,14 @@ struct MlpInferResArgs : MlpInferNormArgs {
   int residual;
 };
 
+// One launch of the wide bf16 inference kernel (mlp_wide_infer.hip): MlpInferArgs - the same gather, outputs, loss
+// fields and statistics words, the workspace of dct_mlp_wide_infer_ws_bytes - with the bf16 copy of p behind it.  p
+// gives the fp32 biases, wb the weights (element i of wb is element i of p rounded to bf16; 16-byte aligned).
+// act_kind: MLP_ACT_RELU or MLP_ACT_GELU.
+struct MlpWideInferArgs : MlpInferArgs {
+  const uint16_t* wb;
+};
+
 // fills *sh for dims[0 .. L] and plans of up to bmax rows per step (mlp_block = -1: auto, until the plan stamps
 // its knob copy); -1 when L is outside 2 .. MLP_MAXL, else 0 with sh->supported set
 int mlp_make_shape(MlpShape* sh, const int* dims, int L, int bmax);
@@ -328,4 +336,10 @@ int dct_mlp_tile_train(const int* dims, int L, const dct::MlpResArgs* a, void* s
 // hipErrorInvalidValue also for an act_kind that is no MlpAct, a norm_kind that is no MlpNorm or such a residual
 int dct_mlp_infer(const int* dims, int L, const dct::MlpInferResArgs* a, int grid, void* stream);
 long long dct_mlp_infer_ws_bytes(const int* dims, int L, long long n);
+// fused bf16 forward-only inference for the wide MLPs (mlp_wide_infer.hip): 2..4 linear layers, D0 a multiple of 32
+// in 32..1024, hidden widths multiples of 128 in 128..1024, 2..8 classes, ReLU or erf-GELU; anything else is
+// hipErrorInvalidValue.  grid <= 0: default.  Statistics as dct_mlp_infer's, in 2 + C * C words.
+int dct_mlp_wide_infer_supported(const int* dims, int L, int act_kind);
+long long dct_mlp_wide_infer_ws_bytes(const int* dims, int L, long long n);
+int dct_mlp_wide_infer(const int* dims, int L, const dct::MlpWideInferArgs* a, int grid, void* stream);
 }

@@ -660,43 +660,19 @@ class FusedMLPKernel:
         D0 1..32, hidden widths multiples of 16 in 16..128, 2..4 classes.  No GPU needed."""
         return bool(native().mlp_infer_supported([int(d) for d in dims]))
 
-    def _infer_ws(self, device, n: int) -> torch.Tensor:
+    def _infer_ws(self, device, n: int, wide: bool = False) -> torch.Tensor:
         """The statistics' slot workspace (at most 4096 slots), allocated once and grown on demand."""
-        need = int(native().mlp_infer_ws_bytes(self.dims, int(n))) // 8
+        ws_bytes = native().mlp_wide_infer_ws_bytes if wide else native().mlp_infer_ws_bytes
+        need = int(ws_bytes(self.dims, int(n))) // 8
         ws = self._infer_ws_buf
         if ws is None or ws.device != device or ws.numel() < need:
             ws = torch.empty(need, dtype=torch.int64, device=device)
             self._infer_ws_buf = ws
         return ws
 
-    def infer(self, p, X, n: int, idx: Optional[torch.Tensor] = None, Y: Optional[torch.Tensor] = None,
-              loss: str = "ce", logits_out: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
-              pred_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, norm=None,
-              grid: Optional[int] = None, stream: Optional[int] = None,
-              class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
-              activation: str = "relu", hidden_norm: Optional[str] = None, residual: bool = False):
-        """One forward-only launch over rows ``idx[0 .. n)`` of ``X`` (``idx=None``: rows ``0 .. n - 1``).
-
-        Per-row outputs, each optional: ``logits_out`` / ``probs_out`` fp32 [n, C], ``pred_out`` int32 [n] (argmax,
-        lowest index on ties).  ``norm=(mean, std)``: cuda fp32 [D0] each, the gather computes ``(x - mean) / std``
-        (the caller replaces a zero std by 1).  With labels ``Y`` (int32, indexed like X's rows) the launch also
-        writes ``stats_out``, ONE cuda int64 buffer of ``2 + C * C`` words: word 0 holds the bits of the fp64 loss sum
-        (``stats_out[:1].view(torch.float64)``), word 1 the correct count, words ``2 + y * C + pred`` the confusion
-        matrix (rows = label, columns = prediction); ``infer_stats`` unpacks it.  The statistics depend on the inputs
-        and ``n`` only - not on ``grid``, not on the run.  Without ``Y`` nothing is written to ``stats_out``.
-
-        ``class_weight`` (cuda fp32 [C]) / ``label_smoothing`` as in ``train`` (CE only): word 0 is then the numerator
-        ``sum_i num_i`` of torch's weighted mean; ``weighted_infer_stats`` divides it by ``W``.
-
-        ``activation``: the model's hidden activation, as in ``train``.  ``hidden_norm``: ``train``'s ``norm`` (the
-        keyword ``norm`` is the input normalisation here): ``"layer"`` / ``"rms"`` for a model with LayerNorm / RMSNorm in its hidden
-        layers; ``residual``: its skip connection.  A normed model is one
-        whose ``p`` carries the gamma / beta tail."""
-        if not self.infer_supported(self.dims):
-            raise ValueError(f"the inference kernel does not take the architecture {self.dims}")
-        self._check_params(p, norm=hidden_norm)
-        if p.data_ptr() % 16:
-            raise ValueError("the flat parameter buffer must lie on a 16-byte boundary")
+    def _check_infer_io(self, X, n, idx, Y, stats_out, logits_out, probs_out, pred_out, norm):
+        """The data, output and input-normalisation arguments of an ``infer`` / ``wide_infer`` launch, checked:
+        (n, mean, std)."""
         n = int(n)
         C = self.dims[-1]
         if n < 1:
@@ -726,6 +702,37 @@ class FusedMLPKernel:
             for t in (mean, std):
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self.dims[0]):
                     raise ValueError(f"norm = (mean, std) must be contiguous cuda fp32 [{self.dims[0]}] each")
+        return n, mean, std
+
+    def infer(self, p, X, n: int, idx: Optional[torch.Tensor] = None, Y: Optional[torch.Tensor] = None,
+              loss: str = "ce", logits_out: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
+              pred_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, norm=None,
+              grid: Optional[int] = None, stream: Optional[int] = None,
+              class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
+              activation: str = "relu", hidden_norm: Optional[str] = None, residual: bool = False):
+        """One forward-only launch over rows ``idx[0 .. n)`` of ``X`` (``idx=None``: rows ``0 .. n - 1``).
+
+        Per-row outputs, each optional: ``logits_out`` / ``probs_out`` fp32 [n, C], ``pred_out`` int32 [n] (argmax,
+        lowest index on ties).  ``norm=(mean, std)``: cuda fp32 [D0] each, the gather computes ``(x - mean) / std``
+        (the caller replaces a zero std by 1).  With labels ``Y`` (int32, indexed like X's rows) the launch also
+        writes ``stats_out``, ONE cuda int64 buffer of ``2 + C * C`` words: word 0 holds the bits of the fp64 loss sum
+        (``stats_out[:1].view(torch.float64)``), word 1 the correct count, words ``2 + y * C + pred`` the confusion
+        matrix (rows = label, columns = prediction); ``infer_stats`` unpacks it.  The statistics depend on the inputs
+        and ``n`` only - not on ``grid``, not on the run.  Without ``Y`` nothing is written to ``stats_out``.
+
+        ``class_weight`` (cuda fp32 [C]) / ``label_smoothing`` as in ``train`` (CE only): word 0 is then the numerator
+        ``sum_i num_i`` of torch's weighted mean; ``weighted_infer_stats`` divides it by ``W``.
+
+        ``activation``: the model's hidden activation, as in ``train``.  ``hidden_norm``: ``train``'s ``norm`` (the
+        keyword ``norm`` is the input normalisation here): ``"layer"`` / ``"rms"`` for a model with LayerNorm / RMSNorm in its hidden
+        layers; ``residual``: its skip connection.  A normed model is one
+        whose ``p`` carries the gamma / beta tail."""
+        if not self.infer_supported(self.dims):
+            raise ValueError(f"the inference kernel does not take the architecture {self.dims}")
+        self._check_params(p, norm=hidden_norm)
+        if p.data_ptr() % 16:
+            raise ValueError("the flat parameter buffer must lie on a 16-byte boundary")
+        n, mean, std = self._check_infer_io(X, n, idx, Y, stats_out, logits_out, probs_out, pred_out, norm)
         wl_args = self._check_wloss(class_weight, label_smoothing, loss, p.device)
         if check_activation(activation) != "relu":
             wl_args = dict(wl_args, activation=activation)
@@ -744,6 +751,42 @@ class FusedMLPKernel:
         C = self.dims[-1]
         host = stats_out[: 2 + C * C].cpu()
         return float(host[:1].view(torch.float64)[0]), int(host[1]), host[2:].reshape(C, C).clone()
+
+    # ------------------------------------------------------------ wide bf16 inference
+    @staticmethod
+    def wide_infer_supported(dims: Sequence[int], activation: str = "relu", norm=None, residual: bool = False) -> bool:
+        """The wide bf16 inference kernel (csrc/mlp_wide_infer.hip) takes this model: 2 to 4 linear layers, D0 a
+        multiple of 32 in 32..1024, hidden widths multiples of 128 in 128..1024, 2..8 classes, ReLU or erf-GELU, no
+        hidden norm and no skip connection.  No GPU needed."""
+        if check_norm(norm) is not None or residual or check_activation(activation) not in ("relu", "gelu"):
+            return False
+        return bool(native().mlp_wide_infer_supported([int(d) for d in dims], activation))
+
+    def wide_infer(self, p, X, n: int, idx: Optional[torch.Tensor] = None, Y: Optional[torch.Tensor] = None,
+                   loss: str = "ce", logits_out: Optional[torch.Tensor] = None,
+                   probs_out: Optional[torch.Tensor] = None, pred_out: Optional[torch.Tensor] = None,
+                   stats_out: Optional[torch.Tensor] = None, norm=None, grid: Optional[int] = None,
+                   stream: Optional[int] = None, class_weight: Optional[torch.Tensor] = None,
+                   label_smoothing: float = 0.0, activation: str = "relu"):
+        """``infer`` for the wide MLPs, on the fused bf16 kernel: the same arguments, outputs and statistics words
+        (``infer_stats`` / ``weighted_infer_stats`` unpack them), bit-identical whatever the grid.
+
+        The arithmetic is the graph engine's training step's: weights, the (normalised) input and every hidden
+        activation rounded to bf16, fp32 accumulation, fp32 biases; the head in fp32 on bf16-rounded weights.  The
+        bf16 weight copy is made on the device from ``p`` at every call."""
+        if not self.wide_infer_supported(self.dims, activation):
+            raise ValueError(f"the wide inference kernel does not take the architecture {self.dims} with "
+                             f"activation {activation!r}")
+        self._check_params(p)
+        n, mean, std = self._check_infer_io(X, n, idx, Y, stats_out, logits_out, probs_out, pred_out, norm)
+        wl_args = self._check_wloss(class_weight, label_smoothing, loss, p.device)
+        self._wide_wb = wb = p.to(torch.bfloat16)  # (kept until the next call: the launch is asynchronous)
+        ws = self._infer_ws(p.device, n, wide=True) if Y is not None else None
+        native().mlp_wide_infer(self.dims, ptr(p), ptr(wb), ptr(X), X.stride(0), ptr(idx), ptr(Y), n, ptr(mean),
+                                ptr(std), LOSS_KINDS[loss], ptr(logits_out), ptr(probs_out), ptr(pred_out), ptr(ws),
+                                0 if ws is None else ws.numel() * 8, ptr(stats_out) if Y is not None else 0,
+                                int(grid or 0), stream if stream is not None else stream_handle(),
+                                activation=activation, **wl_args)
 
 
 # the current stream's raw handle without building a torch.cuda.Stream object (one C call); the

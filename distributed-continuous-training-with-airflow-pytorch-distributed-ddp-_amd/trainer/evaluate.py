@@ -12,7 +12,13 @@ ckpt_path="best")``, ``trainer.predict(model, loader)``) on two paths:
     rank's whole shard), ``predict`` returns views of one ``[n, C]`` logits tensor split by the loader's batch size, and
     ``trainer.last_confusion_matrix`` holds the int64 ``[C, C]`` confusion matrix (rows = label, columns =
     prediction) summed over ranks.
-  * generic: every other model (the wide-MLP and TabTransformer engines' models included) and the CPU -
+  * native, wide: the fused bf16 inference kernel (csrc/mlp_wide_infer.hip, ``FusedMLPKernel.wide_infer``) for the
+    wide MLPs the graph engine trains - architectures ``FusedMLPKernel.wide_infer_supported`` accepts (2 to 4 linear
+    layers, D0 a multiple of 32 up to 1024, hidden widths multiples of 128 up to 1024, up to 8 classes, ReLU or
+    GELU, no hidden norm, no skip connection), under the same conditions and with the same outputs, statistics,
+    sharding and ``input_norm`` as above.  It scores with the training step's arithmetic: bf16 weights and
+    activations, fp32 accumulation.
+  * generic: every other model (the TabTransformer engine's models included) and the CPU -
     ``model.eval()``, ``torch.no_grad()`` and the Python step loop of ``Trainer._validate``'s non-epoch-engine branch.
     ``trainer.last_confusion_matrix`` is None.
 
@@ -86,7 +92,14 @@ def native_path(model, device: torch.device, stage: str) -> bool:
         return False
     if not (_library_own(model, _STEP[stage]) and _library_own(model, "forward")):
         return False
-    return FusedMLPKernel.infer_supported(model.fused_spec()["dims"])
+    spec = model.fused_spec()
+    return FusedMLPKernel.infer_supported(spec["dims"]) or _wide(spec)
+
+
+def _wide(spec) -> bool:
+    """The model goes to the wide bf16 kernel (``FusedMLPKernel.wide_infer``)."""
+    return FusedMLPKernel.wide_infer_supported(spec["dims"], spec.get("activation", "relu"), spec.get("norm"),
+                                               bool(spec.get("residual")))
 
 
 def _prepare(trainer, model, dataloaders, ckpt_path, stage: str):
@@ -141,7 +154,8 @@ def _native_launch(trainer, model, X, Y, local, want_logits: bool):
     """One ``infer`` launch over the rank's shard: (logits or None, (loss mean, correct, confusion) or None)."""
     dev = trainer.ctx.device
     spec = model.fused_spec()
-    kern = FusedMLPKernel(spec["dims"], bmax=TILE_BMAX)
+    wide = not FusedMLPKernel.infer_supported(spec["dims"])  # (native_path let the model in: the wide kernel's then)
+    kern = FusedMLPKernel(spec["dims"], bmax=4 if wide else TILE_BMAX)
     C = spec["dims"][-1]
     n = len(local)
     Xd = X.to(dev, torch.float32).contiguous()
@@ -164,8 +178,9 @@ def _native_launch(trainer, model, X, Y, local, want_logits: bool):
         wl["hidden_norm"] = spec["norm"]
     if spec.get("residual"):  # the skip connection around the second hidden layer
         wl["residual"] = True
-    kern.infer(_flat_params(model, dev), Xd, n, idx=idx, Y=Yd, loss=spec["loss"], logits_out=logits,
-               stats_out=stats, norm=_norm_on(trainer, dev), **wl)
+    launch = kern.wide_infer if wide else kern.infer
+    launch(_flat_params(model, dev), Xd, n, idx=idx, Y=Yd, loss=spec["loss"], logits_out=logits,
+           stats_out=stats, norm=_norm_on(trainer, dev), **wl)
     if stats is None:
         return logits, None
     loss_sum, correct, conf = kern.infer_stats(stats)
