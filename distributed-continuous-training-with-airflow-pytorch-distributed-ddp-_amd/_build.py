@@ -52,6 +52,7 @@ FILE_FLAGS = {"gemm_bf16.hip": ["-fno-slp-vectorize"],
               "mlp_infer.hip": ["-fno-slp-vectorize"],
               "tt_block.hip": MAX_ILP,
               "tt_io.hip": MAX_ILP,
+              "tt_infer.hip": MAX_ILP,  # (tt_block.hip's forward phases, under the scheduler they were tuned with)
               "mlp_wave_single.hip": MAX_ILP,
               "mlp_wave_rows_x0.hip": MAX_ILP}
 

@@ -961,6 +961,50 @@ PYBIND11_MODULE(_dct_native, m) {
   m.def("tt_head_fused", [](std::vector<uintptr_t> p, int B, int T, int D, int C, float eps, uintptr_t st) {
     check(dct_tt_head_fused(p.data(), (int)p.size(), B, T, D, C, eps, reinterpret_cast<void*>(st)), "tt_head_fused");
   });
+  // whole-model TabTransformer inference (tt_infer.hip); the predicate and the workspace size need no device
+  m.def("tt_infer_supported", [](int T, int DM, int H, int FF, int L, int C) {
+    return dct_tt_infer_supported(T, DM, H, FF, L, C) != 0;
+  }, py::arg("tokens"), py::arg("d_model"), py::arg("heads"), py::arg("ffn"), py::arg("layers"), py::arg("classes"));
+  m.def("tt_infer_ws_bytes", [](int L, int C, int64_t n) { return (int64_t)dct_tt_infer_ws_bytes(L, C, n); },
+        py::arg("layers"), py::arg("classes"), py::arg("n"));
+  m.def("tt_infer",
+        [](int T, int DM, int H, int FF, int L, int C, float eps, uintptr_t X, int ldx, uintptr_t idx, uintptr_t Y,
+           int64_t n, uintptr_t norm_mean, uintptr_t norm_std, uintptr_t E, uintptr_t c, uintptr_t wimg, uintptr_t vimg,
+           uintptr_t ln_w, uintptr_t ln_b, uintptr_t head_w, uintptr_t head_b, uintptr_t logits_out,
+           uintptr_t probs_out, uintptr_t pred_out, uintptr_t ws, int64_t ws_bytes, uintptr_t stats, int grid,
+           uintptr_t stream) {
+          dct::TtInferArgs a{};
+          a.X = P<const float>(X);
+          a.ldx = ldx;
+          a.idx = P<const int>(idx);
+          a.Y = P<const int>(Y);
+          a.n = n;
+          a.norm_mean = P<const float>(norm_mean);
+          a.norm_std = P<const float>(norm_std);
+          a.E = P<const float>(E);
+          a.c = P<const float>(c);
+          a.wimg = P<const uint16_t>(wimg);
+          a.vimg = P<const float>(vimg);
+          a.ln_w = P<const float>(ln_w);
+          a.ln_b = P<const float>(ln_b);
+          a.head_w = P<const float>(head_w);
+          a.head_b = P<const float>(head_b);
+          a.L = L;
+          a.C = C;
+          a.eps = eps;
+          a.logits_out = P<float>(logits_out);
+          a.probs_out = P<float>(probs_out);
+          a.pred_out = P<int>(pred_out);
+          a.ws = P<void>(ws);
+          a.ws_bytes = ws_bytes;
+          a.stats = P<void>(stats);
+          check(dct_tt_infer(&a, T, DM, H, FF, grid, reinterpret_cast<void*>(stream)), "tt_infer");
+        },
+        py::arg("tokens"), py::arg("d_model"), py::arg("heads"), py::arg("ffn"), py::arg("layers"), py::arg("classes"),
+        py::arg("eps"), py::arg("X"), py::arg("ldx"), py::arg("idx"), py::arg("Y"), py::arg("n"), py::arg("norm_mean"),
+        py::arg("norm_std"), py::arg("E"), py::arg("c"), py::arg("wimg"), py::arg("vimg"), py::arg("ln_w"),
+        py::arg("ln_b"), py::arg("head_w"), py::arg("head_b"), py::arg("logits_out"), py::arg("probs_out"),
+        py::arg("pred_out"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stats"), py::arg("grid"), py::arg("stream"));
   m.def("gemm_bf16_dw_grouped",
         [](std::vector<uintptr_t> dz, std::vector<uintptr_t> x, std::vector<uintptr_t> c, std::vector<int> M,
            std::vector<int> N, int K, std::vector<uintptr_t> colsum, int accumulate, uintptr_t stream) {

@@ -71,6 +71,30 @@ struct AdamRange {
   const float* lr_tab;  // optional rate table (lr_table.h), last: the fields above keep their offsets
 };
 
+// One launch of the whole-model TabTransformer inference kernel (tt_infer.hip, dct_tt_infer).  Data, outputs, labels
+// and statistics as MlpInferArgs (mlp_fused.h): ws holds dct_tt_infer_ws_bytes(L, C, n) bytes, stats 2 + C * C
+// 8-byte words (fp64 loss-sum bits, correct count, confusion matrix with rows = label), both used with Y only.
+struct TtInferArgs {
+  const float* X;  // [rows][ldx] fp32 features, the first 64 of a row are read
+  int ldx;
+  const int* idx;  // optional: sample i is row idx[i]
+  const int* Y;    // optional labels, indexed like X's rows
+  long long n;
+  const float *norm_mean, *norm_std;  // optional, [64] each: (x - mean) / std in fp32
+  const float *E, *c;                 // feature-token embedding [64][64] each
+  const uint16_t* wimg;  // bf16, per block Wqkv [192][64] | Wo [64][64] | W1 [256][64] | W2 [64][256]: 49,152 elements
+  const float* vimg;     // fp32, per block ln1_w, ln1_b, bqkv, bo, ln2_w, ln2_b, b1, b2: 832 floats
+  const float *ln_w, *ln_b, *head_w, *head_b;  // final LayerNorm [64], head [C][64] and [C], fp32
+  int L, C;
+  float eps;
+  float* logits_out;  // optional [n][C]
+  float* probs_out;   // optional [n][C]
+  int* pred_out;      // optional [n]: argmax, the lowest index on ties
+  void* ws;
+  long long ws_bytes;
+  void* stats;
+};
+
 }  // namespace dct
 
 extern "C" {
@@ -180,6 +204,14 @@ int dct_tt_embed_bwd(const float* x, const float* dh, float* dE, float* dc, int 
 int dct_tt_head_fwd(const uintptr_t* p, int n_ptrs, int B, int T, int Dm, int C, float eps, void* stream);
 int dct_tt_head_bwd(const uintptr_t* p, int n_ptrs, int B, int T, int Dm, int C, float eps, void* stream);
 int dct_tt_head_fused(const uintptr_t* p, int n_ptrs, int B, int T, int Dm, int C, float eps, void* stream);
+// Whole-model forward-only TabTransformer launch (tt_infer.hip): embedding, L blocks and the classifier head of
+// samples idx[0 .. n) of X (idx null: rows 0 .. n - 1) in one kernel, per-sample outputs and the statistics
+// contract of dct_mlp_infer.  Shape: 64 features, d_model 64, 4 heads, FFN 256, 1..8 blocks, 2..8 classes.
+// hipErrorInvalidValue (nothing launched): another shape, n < 1, a null or misaligned (16-byte) parameter image,
+// norm_mean without norm_std, labels without a large enough 8-byte aligned workspace / statistics buffer.
+int dct_tt_infer_supported(int T, int DM, int H, int FF, int L, int C);
+long long dct_tt_infer_ws_bytes(int L, int C, long long n);
+int dct_tt_infer(const dct::TtInferArgs* a, int T, int DM, int H, int FF, int grid, void* stream);
 int dct_gemm_bf16_dw_grouped(int n, const uint16_t* const* dZ, const uint16_t* const* X, float* const* C,
                              const int* M, const int* N, int K, float* const* colsum, int accumulate, void* stream);
 int dct_gemm_bf16_dw_grouped_embed(int n, const uint16_t* const* dZ, const uint16_t* const* X, float* const* C,

@@ -18,12 +18,14 @@ from __future__ import annotations
 import contextlib
 import math
 import os
+from types import SimpleNamespace
 from typing import Dict, Iterable, List, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
 
-from ._native import native
+from ._native import native, ptr
+from .fused_mlp import FusedMLPKernel
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 _EPI = {ACT_NONE: 1, ACT_RELU: 2, ACT_GELU: 3}  # EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_GELU
@@ -1036,3 +1038,76 @@ def tt_head_loss(h, y, B: int, T: int, ln_w, ln_b, W, bias, eps: float = 1e-5, r
     pooled = h.reshape(B, T, h.shape[1]).mean(1)
     z = layer_norm(pooled, ln_w, ln_b, eps)
     return F.cross_entropy(linear(z, W, bias).float(), y)
+
+
+# ----------------------------------------------------------------------------- whole-model inference
+def _tt_shape(model_or_hparams):
+    """(tokens, d_model, heads, ffn, layers, classes) of a TabTransformer or of its hyper-parameter mapping."""
+    m = model_or_hparams
+    if hasattr(m, "blocks"):
+        blk = m.blocks[0] if len(m.blocks) else None
+        return (m.F, m.d, blk.heads if blk else 0, blk.fc1.out_features if blk else 0, len(m.blocks),
+                m.head.out_features)
+    hp = dict(num_features=64, d_model=64, heads=4, layers=4, ffn_mult=4, num_classes=2)  # TabTransformer's defaults
+    hp.update(m)
+    return (hp["num_features"], hp["d_model"], hp["heads"], hp["ffn_mult"] * hp["d_model"], hp["layers"],
+            hp["num_classes"])
+
+
+def tt_infer_supported(model_or_hparams) -> bool:
+    """The whole-model inference kernel (csrc/tt_infer.hip) takes this TabTransformer: 64 features, d_model 64,
+    4 heads, FFN 256, 1..8 blocks, 2..8 classes.  No GPU needed."""
+    return bool(native().tt_infer_supported(*(int(v) for v in _tt_shape(model_or_hparams))))
+
+
+_TT_INFER_WS: Dict[object, torch.Tensor] = {}
+_TT_INFER_KEEP = None  # the last launch's packed images (the launch is asynchronous)
+
+
+def tt_infer(model, X, n: int, idx: Optional[torch.Tensor] = None, Y: Optional[torch.Tensor] = None,
+             logits_out: Optional[torch.Tensor] = None, probs_out: Optional[torch.Tensor] = None,
+             pred_out: Optional[torch.Tensor] = None, stats_out: Optional[torch.Tensor] = None, norm=None,
+             grid: Optional[int] = None, stream: Optional[int] = None):
+    """One forward-only launch of a TabTransformer over rows ``idx[0 .. n)`` of ``X`` (``idx=None``: rows
+    ``0 .. n - 1``): embedding, every block and the head in one kernel, with ``FusedMLPKernel.infer``'s data, output
+    and ``norm`` arguments and its statistics words (``stats_out``: ``2 + C * C`` int64 words - the fp64 bits of the
+    cross-entropy sum, the correct count, the confusion matrix with rows = label - the same bits whatever ``grid``).
+
+    The blocks score with the training kernels' arithmetic (bf16 weights and activations at the same rounding points,
+    fp32 accumulation and residual); the head runs in fp32 on fp32 parameters, as the training head does.  The two
+    parameter images are packed from the module's parameters at every call."""
+    global _TT_INFER_KEEP
+    T, d, H, ffn, L, C = (int(v) for v in _tt_shape(model))
+    if not tt_infer_supported(model):
+        raise ValueError(f"the TabTransformer inference kernel does not take the shape (features {T}, d_model {d}, "
+                         f"heads {H}, ffn {ffn}, layers {L}, classes {C})")
+    # FusedMLPKernel's rules for an inference launch, for a model of T inputs and C classes
+    n, mean, std = FusedMLPKernel._check_infer_io(SimpleNamespace(dims=[T, C]), X, n, idx, Y, stats_out, logits_out,
+                                                  probs_out, pred_out, norm)
+    dev = X.device
+
+    def f32(t):
+        return t.detach().to(dev, torch.float32).contiguous()
+
+    # per block Wqkv | Wo | W1 | W2 in bf16 (49,152 elements; the training step's rounding, _w16) and ln1_w, ln1_b,
+    # bqkv, bo, ln2_w, ln2_b, b1, b2 in fp32 (832 floats)
+    wimg = torch.cat([f32(w).reshape(-1) for b in model.blocks
+                      for w in (b.qkv.weight, b.proj.weight, b.fc1.weight, b.fc2.weight)]).to(torch.bfloat16)
+    vimg = torch.cat([f32(v).reshape(-1) for b in model.blocks
+                      for v in (b.ln1_w, b.ln1_b, b.qkv.bias, b.proj.bias, b.ln2_w, b.ln2_b, b.fc1.bias, b.fc2.bias)])
+    E, c, ln_w, ln_b, hw, hb = rest = [f32(t) for t in (model.feat_w, model.feat_b, model.ln_w, model.ln_b,
+                                                        model.head.weight, model.head.bias)]
+    ws = None
+    if Y is not None:
+        need = int(native().tt_infer_ws_bytes(L, C, n)) // 8
+        ws = _TT_INFER_WS.get(dev)
+        if ws is None or ws.numel() < need:
+            ws = _TT_INFER_WS[dev] = torch.empty(need, dtype=torch.int64, device=dev)
+    _TT_INFER_KEEP = (wimg, vimg, rest)
+    native().tt_infer(T, d, H, ffn, L, C, 1e-5, ptr(X), X.stride(0), ptr(idx), ptr(Y), n, ptr(mean), ptr(std), ptr(E),
+                      ptr(c), ptr(wimg), ptr(vimg), ptr(ln_w), ptr(ln_b), ptr(hw), ptr(hb), ptr(logits_out),
+                      ptr(probs_out), ptr(pred_out), ptr(ws), 0 if ws is None else ws.numel() * 8,
+                      ptr(stats_out) if Y is not None else 0, int(grid or 0),
+                      stream if stream is not None else _stream())
+
+

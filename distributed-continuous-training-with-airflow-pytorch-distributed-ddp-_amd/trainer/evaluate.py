@@ -18,7 +18,12 @@ ckpt_path="best")``, ``trainer.predict(model, loader)``) on two paths:
     GELU, no hidden norm, no skip connection), under the same conditions and with the same outputs, statistics,
     sharding and ``input_norm`` as above.  It scores with the training step's arithmetic: bf16 weights and
     activations, fp32 accumulation.
-  * generic: every other model (the TabTransformer engine's models included) and the CPU -
+  * native, TabTransformer: the whole-model kernel (csrc/tt_infer.hip, ``ops.nn.tt_infer``) for a ``TabTransformer``
+    of the shape ``ops.nn.tt_infer_supported`` accepts (64 features, d_model 64, 4 heads, FFN 256, 1 to 8 blocks, 2
+    to 8 classes), under the same conditions and with the same outputs, statistics, sharding and ``input_norm`` as
+    above.  The blocks score with the training kernels' arithmetic; the head runs in fp32 as the training head does
+    (the generic path rounds its LayerNorm output and weights to bf16).
+  * generic: every other model (other TabTransformer shapes included) and the CPU -
     ``model.eval()``, ``torch.no_grad()`` and the Python step loop of ``Trainer._validate``'s non-epoch-engine branch.
     ``trainer.last_confusion_matrix`` is None.
 
@@ -40,7 +45,9 @@ import torch
 from ..ckpt.lightning_io import load_checkpoint
 from ..data.dataset import dataset_tensors
 from ..data.sampler import distributed_indices
+from ..models.tabtransformer import TabTransformer
 from ..ops.fused_mlp import TILE_BMAX, FusedMLPKernel, weighted_infer_stats
+from ..ops.nn import tt_infer, tt_infer_supported
 from ..parallel.dist import init_distributed
 
 _STEP = {"val": "validation_step", "test": "test_step", "predict": "predict_step"}
@@ -88,10 +95,13 @@ def _library_own(model, name: str) -> bool:
 
 def native_path(model, device: torch.device, stage: str) -> bool:
     """The three conditions of the native path (module docstring)."""
-    if device.type != "cuda" or not hasattr(model, "fused_spec"):
+    tt = isinstance(model, TabTransformer)
+    if device.type != "cuda" or not (tt or hasattr(model, "fused_spec")):
         return False
     if not (_library_own(model, _STEP[stage]) and _library_own(model, "forward")):
         return False
+    if tt:
+        return tt_infer_supported(model)
     spec = model.fused_spec()
     return FusedMLPKernel.infer_supported(spec["dims"]) or _wide(spec)
 
@@ -153,6 +163,8 @@ def _flat_params(model, device) -> torch.Tensor:
 def _native_launch(trainer, model, X, Y, local, want_logits: bool):
     """One ``infer`` launch over the rank's shard: (logits or None, (loss mean, correct, confusion) or None)."""
     dev = trainer.ctx.device
+    if isinstance(model, TabTransformer):
+        return _tt_launch(trainer, model, X, Y, local, want_logits)
     spec = model.fused_spec()
     wide = not FusedMLPKernel.infer_supported(spec["dims"])  # (native_path let the model in: the wide kernel's then)
     kern = FusedMLPKernel(spec["dims"], bmax=4 if wide else TILE_BMAX)
@@ -187,6 +199,22 @@ def _native_launch(trainer, model, X, Y, local, want_logits: bool):
     if weighted:
         return logits, weighted_infer_stats(loss_sum, correct, conf, cw)
     return logits, (loss_sum / max(1, n), correct, conf)
+
+
+def _tt_launch(trainer, model, X, Y, local, want_logits: bool):
+    """``_native_launch`` for a TabTransformer: one ``tt_infer`` launch, the same returns."""
+    dev = trainer.ctx.device
+    C, n = model.head.out_features, len(local)
+    Xd = X.to(dev, torch.float32).contiguous()
+    Yd = Y.to(dev, torch.int32).contiguous() if Y is not None else None
+    idx = None if trainer.world_size == 1 else local.to(dev, torch.int32)
+    logits = torch.empty(n, C, dtype=torch.float32, device=dev) if want_logits else None
+    stats = torch.zeros(2 + C * C, dtype=torch.int64, device=dev) if Yd is not None else None
+    tt_infer(model, Xd, n, idx=idx, Y=Yd, logits_out=logits, stats_out=stats, norm=_norm_on(trainer, dev))
+    if stats is None:
+        return logits, None
+    host = stats.cpu()
+    return logits, (float(host[:1].view(torch.float64)[0]) / max(1, n), int(host[1]), host[2:].reshape(C, C).clone())
 
 
 def _batches(trainer, model, X, Y, local, B: int):
